@@ -14,10 +14,12 @@ BASELINE configs[3] names (mixed_gnn_vn7e2: RU backbone on the page image at 683
 correction, all 40 000 ordered pairs).  Pages are independent, so ranks shard the page list (weak scaling) and the only
 collective is the weight broadcast at start-up.
 
-Prints ONE JSON line on rank 0: BASELINE.json's metric + `roofline` (dominant kernel, timed live with HIP events on
-the launch streams: in situ = in the real schedule beside the other streams, and isolated) + `cpu_baseline` (the CPU
-oracle timed on this box's host cores on a bounded sample; rank 0, N == 1 only).  scripts/roofline_from_profiles.py
-recomputes the roofline block from the rocprofv3 summaries under profiles/<tag>/.
+Prints ONE JSON line on rank 0: BASELINE.json's metric (`value`, `ms_per_step`, ...).  A plain run does only what that
+figure needs: set-up, warm-up, the timed steps, the outputs of the last step with --dump-outputs DIR, the line.
+With --full the line also carries `roofline` (dominant kernel, timed live with HIP events on the launch streams: in situ
+= in the real schedule beside the other streams, and isolated), `cpu_baseline` (the CPU oracle timed on this box's host
+cores on a bounded sample; rank 0, N == 1 only), the secondary figures and the split-product agreement check.
+scripts/roofline_from_profiles.py recomputes the roofline block from the rocprofv3 summaries under profiles/<tag>/.
 """
 import argparse
 import ctypes as C
@@ -102,12 +104,21 @@ def parse_args():
                     help="timed steps of the secondary step on the PLAIN fp32 kernels (compute_dtype f32; 50 x 16 pages >= 6 s at its rate; 0 = skip)")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary measurements (bf16 variant, heading net + stroke-width fusion, visual GNN)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the per-kernel event passes (roofline, kernel "
+                         "table), the secondary figures and the split-product agreement check; without it the other options that select "
+                         "these have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (probability maps, their uint8 / threshold forms, the "
+                         "relation nets' confidences; a fixed sample of the pixels, whole-map float64 sums) as DIR/<name>.npy, < 64 MB in all")
     ap.add_argument("--cpu-sample-height", type=int, default=0,
                     help="rows of a page for the CPU baseline (0 = one whole page per worker on boxes with >= 64 cores, "
                          "a third of a page on smaller ones)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 300 if args.dtype == "bf16" else 80
+    if not args.full:                  # a plain run: the headline figure only
+        args.no_cpu_baseline, args.no_secondary, args.kernel_timing = True, True, "none"
     return args
 
 
@@ -530,7 +541,7 @@ def secondary_measurements(args, lib, dev, imgs, pages_u8, graphs, visual_pages)
             import subprocess
             cmd = [sys.executable, os.path.abspath(__file__), "--dtype", "bf16", "--steps", str(args.bf16_steps), "--warmup", "2",
                    "--pages-per-step", str(args.pages_per_step), "--height", str(H), "--width", str(W), "--gnn", args.gnn,
-                   "--no-cpu-baseline", "--no-secondary", "--event-steps", "2"]
+                   "--no-cpu-baseline", "--no-secondary", "--event-steps", "2", "--full"]
             env = dict(os.environ, ASEP_BENCH_DEVICE=str(dev.index or 0))
             r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, text=True, timeout=1200)
             lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -555,7 +566,7 @@ def secondary_measurements(args, lib, dev, imgs, pages_u8, graphs, visual_pages)
             import subprocess
             cmd = [sys.executable, os.path.abspath(__file__), "--dtype", "f32", "--steps", str(args.plain_steps), "--warmup", "2",
                    "--pages-per-step", str(args.pages_per_step), "--height", str(H), "--width", str(W), "--gnn", args.gnn,
-                   "--no-cpu-baseline", "--no-secondary", "--event-steps", "2"]
+                   "--no-cpu-baseline", "--no-secondary", "--event-steps", "2", "--full"]
             env = dict(os.environ, ASEP_BENCH_DEVICE=str(dev.index or 0))
             r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, text=True, timeout=1200)
             lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -741,6 +752,34 @@ def build_roofline(args, dom, d_iso, d_situ, kernels, exec_flops_page, pages_per
     return r, detail
 
 
+DUMP_PIXELS = 65536              # sampled pixels per page of --dump-outputs
+DUMP_MAX_PAGES = 32              # pages of --dump-outputs (32 x 1.9 MB at the default sizes: < 64 MB)
+
+
+def dump_outputs(d, H, W, out_prob, out_u8, out_mask, out_conf):
+    """--dump-outputs DIR: what the timed path handed its caller in the last step, for comparing two builds output by output.  Per page
+    (the first DUMP_MAX_PAGES): the probability map, its uint8 form and the threshold mask at DUMP_PIXELS pixels drawn once with a fixed
+    seed (the same for every page and run), the float64 sums of the whole probability map per class, and the relation net's confidences."""
+    torch.cuda.synchronize()
+    os.makedirs(d, exist_ok=True)
+    P = min(len(out_prob), DUMP_MAX_PAGES)
+    ncls = out_prob[0].shape[-1]
+    idx = np.sort(np.random.default_rng(20261016).choice(H * W, size=min(H * W, DUMP_PIXELS), replace=False))
+    d_idx = torch.from_numpy(idx).to(out_prob[0].device)
+    pick = lambda t: t.reshape(-1, ncls).index_select(0, d_idx).float().cpu().numpy()
+    arrays = {
+        "pixel_index": idx.astype(np.float64),
+        "prob_sample": np.stack([pick(out_prob[k]) for k in range(P)]),
+        "prob_u8_sample": np.stack([pick(out_u8[k]) for k in range(P)]),
+        "mask_sample": np.stack([pick(out_mask[k]) for k in range(P)]),
+        "prob_sum": np.stack([torch.sum(out_prob[k], dim=(0, 1), dtype=torch.float64).cpu().numpy() for k in range(P)]),
+    }
+    if out_conf is not None:
+        arrays["relation_probs"] = np.stack([out_conf[k].cpu().numpy() for k in range(P)]).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), a)
+
+
 def main():
     global torch
     args = parse_args()
@@ -910,6 +949,8 @@ def main():
         dt = sharding.max_over_ranks(dt, dev if dist.get_backend() == "nccl" else torch.device("cpu"))
     pages = world * B * args.steps
     value = pages / dt
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, H, W, out_prob, out_u8, out_mask, out_conf if not args.no_gnn else None)
 
     # ---- per-kernel timing with HIP events on the launch streams (same workload, separate passes so that the events do not
     #      perturb `value`): "in situ" = the real schedule (attention branch on its side stream, relation nets on theirs: what
@@ -1025,7 +1066,7 @@ def main():
     # --dtype f32s: the step's own outputs against the plain fp32 kernels of the same library on the same pages (in the measured process, after
     # the timed region): what "fp32 with split products" means for THIS run's numbers, not only for the test suite's
     agreement = None
-    if rank == 0 and args.dtype == "f32s":
+    if rank == 0 and args.dtype == "f32s" and args.full:
         step(with_gnn=False)
         torch.cuda.synchronize()
         g32 = AruGraph(aru.tensors, AruConfig(compute_dtype="f32"))

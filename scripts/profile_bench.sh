@@ -19,7 +19,7 @@ cd /tmp && export TMPDIR=/tmp
 # lanes rocprofv3's AverageNs sat 5-20 % above the HIP-event averages of the same run (profiles/r6final first cut).  The whole traced process on one lane:
 # both sources describe the same launches.  (The un-traced default lines, bench_first.json / bench.json, run the product's default.)
 export ASEP_LANES=1
-BENCH="python3 $R/bench.py --steps 1 --warmup 1 --event-steps 10 --no-cpu-baseline --no-secondary --kernel-timing in-situ $*"
+BENCH="python3 $R/bench.py --full --steps 1 --warmup 1 --event-steps 10 --no-cpu-baseline --no-secondary --kernel-timing in-situ $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/bench_under_trace.json 2> $OUT/trace.log
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $BENCH > /dev/null 2> $OUT/pmc_fetch.log
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- $BENCH > /dev/null 2> $OUT/pmc_write.log

@@ -8,7 +8,8 @@ TAG=${1:-r3}
 COMMIT=${2:-n/a}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
-for T in "$TAG:" "${TAG}_bf16:--dtype bf16" "${TAG}_f32:--dtype f32"; do
+# --full: the bench lines carry the roofline block and the kernel table (a plain bench run times the steps only)
+for T in "$TAG:--full" "${TAG}_bf16:--full --dtype bf16" "${TAG}_f32:--full --dtype f32"; do
     D=${T%%:*}; FL=${T#*:}
     mkdir -p gpurun_out/$D
     # the un-traced default line names the dominant kernel; the traced runs report the same one
@@ -19,7 +20,7 @@ for T in "$TAG:" "${TAG}_bf16:--dtype bf16" "${TAG}_f32:--dtype f32"; do
         python3 scripts/make_traffic_json.py gpurun_out/$D $COMMIT > gpurun_out/$D/traffic.log 2>&1
     done
     python3 bench.py $FL > gpurun_out/$D/bench.json 2> gpurun_out/$D/bench.err
-    DT=f32s; [ -n "$FL" ] && DT=${FL#--dtype }
+    DT=f32s; [ "$FL" != "--full" ] && DT=${FL#--full --dtype }
     python3 scripts/gpu_layer_profile.py 4500 3000 $DT > gpurun_out/$D/layers_one_page.log 2>&1
 done
 cp profiles/traffic_per_kernel*.json gpurun_out/

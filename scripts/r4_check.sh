@@ -4,6 +4,7 @@
 set -u
 TAG=${1:-r4a}; shift
 PYT=${1:-}; shift || true
+set -- "$@" --full            # the bench lines below carry the roofline block (a plain bench run times the steps only)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 mkdir -p gpurun_out/$TAG

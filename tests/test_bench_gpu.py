@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +41,7 @@ def r_src(line):
 
 def test_single_process_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--pages-per-step", "3", "--e2e-pages", "6", "--bf16-steps", "3", "--plain-steps", "2"], cwd=ROOT, capture_output=True,
+                        "--full", "--pages-per-step", "3", "--e2e-pages", "6", "--bf16-steps", "3", "--plain-steps", "2"], cwd=ROOT, capture_output=True,
                        text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     line = _one_json_line(r.stdout)
@@ -92,11 +93,38 @@ def test_single_process_line():
     assert set(r["kernel"].split("+")) <= {k["kernel"] for k in line["kernels"]} and "<" in "".join(k["kernel"] for k in line["kernels"])
 
 
+def test_plain_line_times_the_steps_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline figure alone (no event passes, CPU baseline or secondary figures); --dump-outputs
+    writes what the last timed step computed, float32 / float64 only, identical inputs from run to run."""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--pages-per-step", "2",
+                            "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines[:3]
+        line = json.loads(lines[0])
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line) and line["steps"] == 3
+        assert line["unit"] == "pages/s" and line["higher_is_better"] is True and line["dtype"] == "f32s" and line["ms_per_step"] > 0
+        assert abs(line["value"] - 2 * 1e3 / line["ms_per_step"]) < 1e-2 * line["value"]
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["secondary"] is None and line["kernels"] == []
+        arrays = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert set(arrays) == {"pixel_index", "prob_sample", "prob_u8_sample", "mask_sample", "prob_sum", "relation_probs"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        p = arrays["prob_sample"]
+        assert p.shape[0] == 2 and p.shape[2] == 2 and np.all(np.isfinite(p)) and np.allclose(p.sum(axis=2), 1.0, atol=1e-4)
+        assert arrays["relation_probs"].shape[0] == 2 and np.all(np.isfinite(arrays["relation_probs"]))
+        dumps.append(arrays)
+    assert np.array_equal(dumps[0]["pixel_index"], dumps[1]["pixel_index"])
+    assert np.allclose(dumps[0]["prob_sample"], dumps[1]["prob_sample"], atol=1e-4)           # the fp32 parity gate
+
+
 def test_rccl_path_with_one_rank_keeps_stdout_clean():
     env = dict(os.environ, ASEP_BENCH_FORCE_DIST="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-secondary", "--pages-per-step", "2"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--no-secondary", "--pages-per-step", "2", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     _one_json_line(r.stdout)
 
@@ -145,7 +173,7 @@ def test_gpus_2_reports_the_files_leg_with_two_gpu_owners():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["ASEP_BENCH_DEVICE"] = "0"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--pages-per-step", "2", "--kernel-timing", "none", "--e2e-n-pages-per-owner", "12"], cwd=ROOT, env=env,
+                        "--pages-per-step", "2", "--kernel-timing", "none", "--e2e-n-pages-per-owner", "12", "--full"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]

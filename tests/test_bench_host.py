@@ -2,6 +2,8 @@
 ranks (VERDICT r3 next #1a), and the shape of the roofline block (<= 20 keys, the HBM keys in front, strings below 120 characters)."""
 import json
 import os
+import shutil
+import subprocess
 import sys
 import types
 
@@ -10,6 +12,15 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+
+
+def _is_tracked(path):
+    """git's index holds `path`.  The checkout may belong to another user than the one running the suite (git then refuses the
+    repository unless it is named safe); a checkout without git metadata holds tracked files only, so there presence is the answer."""
+    if not os.path.exists(os.path.join(ROOT, ".git")) or shutil.which("git") is None:
+        return os.path.isfile(os.path.join(ROOT, path))
+    r = subprocess.run(["git", "-c", f"safe.directory={ROOT}", "ls-files", "--error-unmatch", path], cwd=ROOT, capture_output=True)
+    return r.returncode == 0
 
 
 def test_gpus_n_without_torchrun_environment_spawns_a_child_and_relays_its_line(monkeypatch, capsys):
@@ -153,7 +164,7 @@ def test_dominant_kernel_is_ranked_in_situ_and_the_traffic_label_names_a_tracked
         assert r["traffic"] is not None, r["traffic_source"]
         path = r["traffic_source"].split("offline PMC: ")[1].split(" @")[0]
         assert path.startswith("profiles/") and os.path.exists(os.path.join(ROOT, path)) and "being collected" not in r["traffic_source"]
-        assert os.system(f"cd {ROOT} && git ls-files --error-unmatch {path} > /dev/null 2>&1") == 0, f"{path} is not tracked"
+        assert _is_tracked(path), f"{path} is not tracked"
 
 
 def test_every_bf16_mfma_kernel_of_the_bf16_header_is_priced_against_the_bf16_pipe():
@@ -177,3 +188,18 @@ def test_every_bf16_mfma_kernel_of_the_bf16_header_is_priced_against_the_bf16_pi
         pipe, peak = bench.pipe_of(n + "<1,2>", "bf16")
         assert pipe == "bf16 MFMA" and peak == bench.PEAK_BF16_MFMA_TFLOPS, n
         assert bench.bound_of(pipe, False) == "mfma_bf16"
+
+
+def test_a_plain_run_measures_the_headline_only_and_full_keeps_the_rest(monkeypatch):
+    """a plain `bench.py --gpus 1 --steps N --warmup W` times the steps and prints the line; the CPU baseline, the event passes and the secondary
+    figures run with --full only, with the options that select them as before"""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert a.no_cpu_baseline and a.no_secondary and a.kernel_timing == "none"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--full", "--dump-outputs", "d"])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == "d" and not a.no_cpu_baseline and not a.no_secondary and a.kernel_timing == "both"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--kernel-timing", "in-situ", "--no-secondary"])
+    a = bench.parse_args()
+    assert a.kernel_timing == "in-situ" and a.no_secondary and a.steps == 80
