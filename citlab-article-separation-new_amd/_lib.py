@@ -107,6 +107,10 @@ SIGNATURES = {
     "asep_swt_distance_transform_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "asep_swt_line_features": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "asep_swt_line_features_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "asep_textblock_interline_dists": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_double, C.c_double, _P]),
+    "asep_textblock_neighbour_words": (C.c_longlong, [C.c_int, _P]),
+    "asep_textblock_neighbours": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_double, _P, C.c_longlong]),
+    "asep_textblock_last_kernel_us": (C.c_double, [C.c_int]),
 }
 
 _lib = None

@@ -109,6 +109,9 @@ struct asep_post {
     }
 };
 
+hipStream_t asep::post_stream(asep_post* p) { return p->s; }
+BufferPool& asep::post_pool(asep_post* p) { return p->pool; }
+
 namespace {
 
 int cv_round(double v) { return (int)lrint(v); }

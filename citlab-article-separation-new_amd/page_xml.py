@@ -147,6 +147,23 @@ class TextLine:
     def get_semantic_type(self):
         return self.custom.get("structure", {}).get("semantic_type")
 
+    def has_coords(self):
+        return self.node.find(self._page._q("Coords")) is not None
+
+    def set_coords(self, points):
+        """The line's surrounding polygon (a Coords child is created in front of the other children if missing)."""
+        q = self._page._q("Coords")
+        nd = self.node.find(q)
+        if nd is None:
+            nd = ET.Element(q)
+            self.node.insert(0, nd)
+        nd.set("points", format_points(points))
+        self.surr_p = [(int(x), int(y)) for x, y in points]
+
+    def set_reading_order(self, index):
+        """textregion_generation.py:97-99: custom readingOrder {index:n;} (replaced in place when present)."""
+        self.custom["readingOrder"] = {"index": int(index)}
+
     def set_structure_attribute(self, name, value):
         self.custom.setdefault("structure", {})[name] = str(value)
 
@@ -328,6 +345,14 @@ class Page:
     def get_textlines(self):
         return [TextLine(n, self) for n in self._page_node.iter(self._q("TextLine"))]
 
+    def get_article_dict(self, textlines=None):
+        """page.py:388-403: {article id (None for lines without one): [TextLine, ...]} in document order (over
+        ``textlines``, the page's lines by default)."""
+        out = {}
+        for tl in (self.get_textlines() if textlines is None else textlines):
+            out.setdefault(tl.get_article_id(), []).append(tl)
+        return out
+
     def get_ids(self):
         return {n.get("id") for n in self._tree.getroot().iter() if n.get("id")} | {r[0] for r in self.__dict__.get("_sep_fast") or ()}
 
@@ -352,6 +377,27 @@ class Page:
         """Write the (modified) region / line objects back into their DOM nodes (page.py:682-700)."""
         for r in text_regions:
             r.flush()
+
+    def replace_text_regions(self, regions):
+        """page.py:682-700 set_text_regions(overwrite=True) with the regions of textregion_generation.py:102-126: every
+        TextRegion of the page is removed and each (id, points, [TextLine], reading order) becomes a TextRegion of type
+        paragraph at the end of <Page> (page_objects.py:157-200): custom readingOrder, Coords, the lines (moved, with
+        their attributes flushed) and a TextEquiv joining the lines' non-empty texts."""
+        self.remove_regions("TextRegion")
+        q = self._q
+        for rid, points, lines, ro in regions:
+            nd = ET.SubElement(self.page_node, q("TextRegion"),
+                               {"id": rid, "custom": format_custom_attr({"readingOrder": {"index": int(ro)}})})
+            nd.set("type", "paragraph")
+            ET.SubElement(nd, q("Coords"), {"points": format_points(points)})
+            text = ""
+            for tl in lines:
+                tl.flush()
+                nd.append(tl.node)
+                text = "\n".join([text, tl.text]) if text else tl.text
+            if text:
+                te = ET.SubElement(nd, q("TextEquiv"))
+                ET.SubElement(te, q("Unicode")).text = text
 
     def set_textline_attr(self, textlines):
         for tl in textlines:

@@ -1,0 +1,296 @@
+"""Text block detection (the reference's README "Text Block Detection" stage) on the GPU.
+
+    interline_distances      dbscan_baselines.py:35-110 (use_java_code=False)     -> asep_textblock_interline_dists
+    neighbour_lists          dbscan_baselines.py:253-307 region_query, all rows    -> asep_textblock_neighbours
+    DBSCAN labels            dbscan_baselines.py:113-251, 309-333                  (host, over the device neighbour lists)
+    text regions             textregion_generation.py:17-172                       (host alpha shapes)
+
+Every function takes a BATCH of pages (one list of polygons per page) so that one kernel launch serves all of them.
+The results are those of the reference's Python path; the Java class the reference can call instead
+(``use_java_code=True``) is not used.  No CPU fallback: without the HIP library every device function
+raises ``AsepError``.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib
+from . import textblock_geometry as geo
+
+_handles = {}
+
+
+def _handle(device=0):
+    lib = _lib.init_device(device)
+    if device not in _handles:
+        h = lib.asep_post_create()
+        if not h:
+            raise _lib.AsepError("asep_post_create failed: " + _lib.last_error())
+        _handles[device] = h
+    return lib, _handles[device]
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+class NormedPage:
+    """The normed polygons of one page with what the distance kernel reads: CSR points, boxes and (cos, sin)."""
+
+    def __init__(self, normed):
+        normed = [(np.asarray(xs, np.int64), np.asarray(ys, np.int64)) for xs, ys in normed]
+        self.polys = normed
+        self.n = len(normed)
+        if any(len(xs) == 0 for xs, _ in normed):
+            # the reference indexes x_points[0] of every normed polygon (an IndexError there)
+            raise ValueError("a baseline whose bounding box exceeds 100000 px has no normed points")
+        self.boxes = np.array([geo.bounds(xs, ys) for xs, ys in normed], np.int32).reshape(-1, 4)
+        self.angles = np.array([geo.calc_reg_line_angle(xs, ys) for xs, ys in normed], np.float64)
+        self.orient = np.array([(math.cos(a), math.sin(a)) for a in self.angles], np.float64).reshape(-1, 2)
+
+
+def normed_pages(pages_polys, des_dist):
+    return [NormedPage(geo.norm_poly_dists(polys, des_dist)) for polys in pages_polys]
+
+
+def normed_pages_or_errors(pages_polys, des_dist):
+    """normed_pages, with the exception of a page that cannot be normed (a baseline box over 100000 px, malformed
+    points) in that page's place: one bad page of a batch fails alone, as a file of the reference's per-file runs does."""
+    out = []
+    for polys in pages_polys:
+        try:
+            out.append(NormedPage(geo.norm_poly_dists(polys, des_dist)))
+        except Exception as e:      # noqa: BLE001 (reported per file by the command lines)
+            out.append(e)
+    return out
+
+
+def interline_distances_or_errors(pages, des_dist=5, max_d=500, device=0):
+    """interline_distances over the NormedPage entries of ``pages`` (one launch); exceptions are passed through."""
+    good = [p for p in pages if not isinstance(p, Exception)]
+    dists = iter(interline_distances(good, des_dist, max_d, device))
+    return [p if isinstance(p, Exception) else next(dists) for p in pages]
+
+
+def interline_distances(pages, des_dist=5, max_d=500, device=0):
+    """``pages``: list of NormedPage.  Returns one float64 array of interline distances per page (one launch)."""
+    lib, h = _handle(device)
+    page_off = np.zeros(len(pages) + 1, np.int32)
+    page_off[1:] = np.cumsum([p.n for p in pages])
+    n_polys = int(page_off[-1])
+    lens = [len(xs) for p in pages for xs, _ in p.polys]
+    poly_off = np.zeros(n_polys + 1, np.int32)
+    poly_off[1:] = np.cumsum(lens)
+    pts = np.zeros((int(poly_off[-1]), 2), np.int32)
+    if n_polys:
+        pts[:, 0] = np.concatenate([xs for p in pages for xs, _ in p.polys])
+        pts[:, 1] = np.concatenate([ys for p in pages for _, ys in p.polys])
+    boxes = np.ascontiguousarray(np.concatenate([p.boxes for p in pages]) if pages else np.zeros((0, 4), np.int32))
+    orient = np.ascontiguousarray(np.concatenate([p.orient for p in pages]) if pages else np.zeros((0, 2)))
+    out = np.zeros(n_polys, np.float64)
+    _lib.check(lib.asep_textblock_interline_dists(h, len(pages), _ptr(page_off), _ptr(poly_off), _ptr(pts), _ptr(boxes),
+                                                  _ptr(orient), float(des_dist), float(max_d), _ptr(out)),
+               "asep_textblock_interline_dists")
+    return [out[page_off[k]:page_off[k + 1]] for k in range(len(pages))]
+
+
+def neighbour_lists(pages, dists, avgs, fac=1.25, device=0):
+    """region_query of every polygon of every page (one launch): per page a list of index-ordered neighbour lists."""
+    lib, h = _handle(device)
+    page_off = np.zeros(len(pages) + 1, np.int32)
+    page_off[1:] = np.cumsum([p.n for p in pages])
+    words = int(lib.asep_textblock_neighbour_words(len(pages), _ptr(page_off)))
+    bits = np.zeros(max(words, 1), np.uint32)
+    boxes = np.ascontiguousarray(np.concatenate([p.boxes for p in pages]) if pages else np.zeros((0, 4), np.int32))
+    d = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float64) for x in dists]) if pages else np.zeros(0))
+    av = np.asarray(avgs, np.float64)
+    _lib.check(lib.asep_textblock_neighbours(h, len(pages), _ptr(page_off), _ptr(boxes), _ptr(d), _ptr(av), float(fac),
+                                             _ptr(bits), words), "asep_textblock_neighbours")
+    out, off = [], 0
+    for p in pages:
+        n = p.n
+        w = (n + 31) // 32
+        m = np.unpackbits(bits[off:off + n * w].view(np.uint8), bitorder="little").reshape(n, w * 32)[:, :n]
+        out.append([np.flatnonzero(row).tolist() for row in m])
+        off += n * w
+    return out
+
+
+def last_kernel_us(which):
+    """device time of the last distance (0) / neighbour (1) kernel of this thread, microseconds"""
+    return float(_lib.load_library().asep_textblock_last_kernel_us(which))
+
+
+# ---- DBSCAN (host) ----------------------------------------------------------------------------------------------------
+
+def average_positive(dists, eps=0.0):
+    """``1 / (len + eps) * sum`` over the positive distances (dbscan_baselines.py:135, 151, 160)."""
+    al = [float(v) for v in dists if v > 0]
+    return 1 / (len(al) + eps) * sum(al) if eps else 1 / len(al) * sum(al)
+
+
+def dbscan_prepare(pages_polys, des_dist=5, max_d=500, target_average_interline_distance=50, device=0):
+    """DBSCANBaselines.__init__ (dbscan_baselines.py:113-172) for a batch of pages: two device passes over all pages.
+    Returns per page a dict with the normed polygons (a NormedPage), the distances, avg and the first pass, or the
+    exception that stopped that page."""
+    first = normed_pages_or_errors(pages_polys, des_dist)
+    d1 = interline_distances_or_errors(first, des_dist, max_d, device)
+    out = [None] * len(pages_polys)
+    rescale = []
+    for k, polys in enumerate(pages_polys):
+        if isinstance(first[k], Exception):
+            out[k] = first[k]
+            continue
+        al = [v for v in d1[k].tolist() if v > 0]
+        rec = {"first": first[k], "dists1": d1[k]}
+        if target_average_interline_distance > 0 and len(al) > 0:
+            avg1 = 1 / len(al) * sum(al)
+            rec["avg1"] = avg1
+            rec["scale_fac"] = target_average_interline_distance / avg1
+            rescale.append(k)
+        else:
+            rec["normed"], rec["dists"] = first[k], d1[k]
+            rec["avg"] = 1 / (len(al) + 1e-8) * sum(al)
+        out[k] = rec
+    if rescale:
+        second = normed_pages_or_errors([geo.scale_polygons(pages_polys[k], out[k]["scale_fac"]) for k in rescale],
+                                        des_dist)
+        d2 = interline_distances_or_errors(second, des_dist, max_d, device)
+        for j, k in enumerate(rescale):
+            if isinstance(second[j], Exception):
+                out[k] = second[j]
+                continue
+            al = [v for v in d2[j].tolist() if v > 0]
+            out[k]["normed"], out[k]["dists"] = second[j], d2[j]
+            out[k]["avg"] = 1 / (len(al) + 1e-8) * sum(al)
+    return out
+
+
+def dbscan_labels(neighbours, min_polygons_for_cluster=2):
+    """clustering_polygons + grow_cluster (dbscan_baselines.py:185-251): the FIFO of neighbour indices may hold duplicates."""
+    labels = [0] * len(neighbours)
+    label = 0
+    for idx in range(len(neighbours)):
+        if labels[idx] != 0:
+            continue
+        queue = list(neighbours[idx])
+        if len(queue) < min_polygons_for_cluster:
+            labels[idx] = -1
+            continue
+        label += 1
+        labels[idx] = label
+        i = 0
+        while i < len(queue):
+            k = queue[i]
+            if labels[k] == -1:
+                labels[k] = label
+            elif labels[k] == 0:
+                labels[k] = label
+                nxt = neighbours[k]
+                if len(nxt) >= min_polygons_for_cluster:
+                    queue += nxt
+            i += 1
+    return labels
+
+
+def cluster_of_polygons(labels, min_polygons_for_article=1):
+    """get_cluster_of_polygons (dbscan_baselines.py:309-333).  Returns (labels, number of articles incl. noise)."""
+    labels = list(labels)
+    if min_polygons_for_article == 1:
+        noise_id = max(labels) + 1                     # (a ValueError on a page without baselines, as in the reference)
+        for index, lab in enumerate(labels):
+            if lab == -1:
+                labels[index] = noise_id
+                noise_id += 1
+    else:
+        counts = {}
+        for lab in labels:
+            counts[lab] = counts.get(lab, 0) + 1
+        small = {lab for lab, c in counts.items() if c < min_polygons_for_article and lab != -1}
+        labels = [-1 if x in small else x for x in labels]
+    return labels, len(set(labels))
+
+
+def cluster_baselines(pages_polys, min_polygons_for_cluster=2, min_polygons_for_article=1, rectangle_interline_factor=1.25,
+                      des_dist=5, max_d=500, target_average_interline_distance=50, device=0):
+    """baseline_clustering.py:66-99 cluster_baselines_dbscan for a batch of pages: per page (labels, n_articles) or the
+    exception that stops that page (the reference's for a page without baselines, or one from norming)."""
+    prep = dbscan_prepare(pages_polys, des_dist, max_d, target_average_interline_distance, device)
+    good = [r for r in prep if not isinstance(r, Exception)]
+    neigh = iter(neighbour_lists([r["normed"] for r in good], [r["dists"] for r in good], [r["avg"] for r in good],
+                                 rectangle_interline_factor, device))
+    out = []
+    for r in prep:
+        if isinstance(r, Exception):
+            out.append(r)
+            continue
+        labels = dbscan_labels(next(neigh), min_polygons_for_cluster)
+        try:
+            out.append(cluster_of_polygons(labels, min_polygons_for_article))
+        except ValueError as e:
+            out.append(e)
+    return out
+
+
+# ---- text regions (host) ----------------------------------------------------------------------------------------------
+
+def shifted_outline(xs, ys, dist):
+    """textregion_generation.py:59-66 / 141-148: the normed points and a copy shifted right by 1 and up by
+    max(int(0.95 * dist), 1); returns the shifted x / y lists."""
+    y_shift = max(int(0.95 * float(dist)), 1)
+    return [int(x) + 1 for x in xs], [int(y) - y_shift for y in ys]
+
+
+def synthetic_coords(xs, ys, dist):
+    """textregion_generation.py:56-72: the surrounding polygon of a line without Coords."""
+    xsh, ysh = shifted_outline(xs, ys, dist)
+    return list(zip([int(x) for x in xs] + xsh[::-1], [int(y) for y in ys] + ysh[::-1]))
+
+
+def create_text_regions(art_lines, line_geom, alpha=75, log=print):
+    """textregion_generation.py:129-172.  ``art_lines``: {article id or None: [line id, ...]} in the page's order;
+    ``line_geom``: {line id: ((xs, ys) normed polygon, interline distance)}.  Returns
+    [("tr_<n>", boundary points, [line id, ...], n), ...]."""
+    regions = []
+    counter = 0
+
+    def outline(lid):
+        (xs, ys), d = line_geom[lid]
+        xsh, ysh = shifted_outline(xs, ys, d)
+        return list(zip([int(x) for x in xs] + xsh, [int(y) for y in ys] + ysh))
+
+    for article_id, lines in art_lines.items():
+        if article_id is None:
+            for lid in lines:
+                if lid in line_geom:
+                    bp = alpha_shape_int(outline(lid), alpha, log)
+                    regions.append(("tr_" + str(counter), bp, [lid], counter))
+                    counter += 1
+        else:
+            pts, members = [], []
+            for lid in lines:
+                if lid in line_geom:
+                    members.append(lid)
+                    pts += outline(lid)
+            if not pts:
+                raise IndexError(f"article {article_id} has no line with a baseline")   # (the reference: list index out of range)
+            bp = alpha_shape_int(pts, alpha, log)
+            regions.append(("tr_" + str(counter), bp, members, counter))
+            counter += 1
+    return regions
+
+
+def alpha_shape_int(pts, alpha, log=print):
+    return [[int(j) for j in i] for i in geo.alpha_shape(np.array(pts), alpha, log)]
+
+
+def reading_order(baselines):
+    """textregion_generation.py:80-99: the lines' indices sorted (stably) by the mean y of their baselines;
+    returns the reading order index of each line."""
+    keys = [1 / len(ys) * sum(int(y) for y in ys) for _, ys in baselines]
+    order = sorted(range(len(baselines)), key=lambda i: keys[i])
+    ro = [0] * len(baselines)
+    for r, i in enumerate(order):
+        ro[i] = r
+    return ro

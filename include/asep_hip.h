@@ -363,6 +363,32 @@ int asep_swt_line_features(asep_post* p, const uint8_t* swt, int H, int W, int n
 int asep_swt_line_features_dev(asep_post* p, const uint8_t* d_swt, int H, int W, int n_lines, const int32_t* boxes,
                                float* out_stroke_width, int32_t* out_height, int32_t* out_flag, void* stream);
 
+/* ---- text block detection (baseline DBSCAN and alpha-shape regions, SURVEY.md "text block detection") ----------------
+ * Batched over pages on the asep_post handle.  Polygons are concatenated page after page: page k holds the polygons
+ * page_off[k] .. page_off[k+1]-1 (page_off[0] = 0).  Host pointers in and out; each call returns after its results
+ * have arrived.
+ *
+ * dbscan_baselines.py:35-110 get_list_of_interline_distances (use_java_code=False) on NORMED baselines, bit for bit:
+ * polygon i holds the points points[2*poly_off[i] ..] as (x, y) int32 pairs up to poly_off[i+1] (at least one point);
+ * boxes [n_polys][4] = {x, y, w, h} of its bounding box with w = max-min+1 (polygon.py:91); orient [n_polys][2] =
+ * (cos, sin) of the calc_reg_line_stats angle, computed by the caller.  Every polygon is compared with the polygons of
+ * its own page.  out_dist [n_polys] = the distance, max_d where it is not below max_d. */
+int asep_textblock_interline_dists(asep_post* p, int n_pages, const int32_t* page_off, const int32_t* poly_off,
+                                   const int32_t* points, const int32_t* boxes, const double* orient, double des_dist,
+                                   double max_d, double* out_dist);
+/* dbscan_baselines.py:253-307 region_query for every ordered pair of every page as a bit matrix: page k with
+ * n = page_off[k+1]-page_off[k] polygons owns n rows of (n+31)/32 uint32 words, the pages one after the other; bit j
+ * of row i is set when polygon j is a neighbour of polygon i.  boxes as above, dists [n_polys] the interline
+ * distances, avg [n_pages] the page's average interline distance, fac the rectangle_interline_factor.
+ * asep_textblock_neighbour_words gives the words the matrix needs; capacity_words is the size of out_bits. */
+long long asep_textblock_neighbour_words(int n_pages, const int32_t* page_off);
+int asep_textblock_neighbours(asep_post* p, int n_pages, const int32_t* page_off, const int32_t* boxes,
+                              const double* dists, const double* avg, double fac, uint32_t* out_bits,
+                              long long capacity_words);
+/* Device time in microseconds of the kernel of the calling thread's last asep_textblock_interline_dists (which = 0)
+ * or asep_textblock_neighbours (which = 1) call; -1 for another `which`. */
+double asep_textblock_last_kernel_us(int which);
+
 #ifdef __cplusplus
 }
 #endif
