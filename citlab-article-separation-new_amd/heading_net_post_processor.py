@@ -16,7 +16,6 @@ from scipy import ndimage
 from . import _lib, image_ops
 from .host_util import rescale_points
 from .image_io import load_image_bgr
-from .net_post_processing_helper import get_scaling_factor
 from .path_util import get_page_path
 from .region_to_page_writer import RegionToPageWriter
 from .separator_net_post_processor import RegionNetPostProcessor
@@ -282,42 +281,8 @@ class HeadingNetPostProcessor(RegionNetPostProcessor):
 
     def heading_probability(self, image):
         """decoded image -> uint8 net output [h,w,n_cls] at the scaled size (:285-288), device resident in between."""
-        import torch
-        dev = self.device
-        lib = _lib.init_device(dev)
-        tdev = torch.device("cuda", dev)
-        image = np.require(image, dtype=np.uint8, requirements=['C', 'W'])   # Pillow hands out read-only views
-        if image.ndim == 2:
-            image = image[:, :, None]
-        H, W, Cn = image.shape
-        sc = get_scaling_factor(H, W, self.scaling_factor, fixed_height=self.fixed_height)
-        h, w = image_ops.scaled_size(H, W, sc)
-        ncls = self.pb_graph.cfg.n_classes
-        _, ws = image_ops._workspace(dev)
-        with torch.cuda.device(tdev):
-            sp = C.c_void_p(torch.cuda.current_stream(tdev).cuda_stream)
-            d_img = torch.from_numpy(image).to(tdev)
-            d_gray = torch.empty((h, w), dtype=torch.float32, device=tdev)
-            _lib.check(lib.asep_prep_scale_gray_dev(ws, d_img.data_ptr(), H, W, Cn, float(sc), None,
-                                                    d_gray.data_ptr(), sp), "asep_prep_scale_gray_dev")
-            d_out = torch.empty((h, w, ncls), dtype=torch.float32, device=tdev)
-            d_u8 = torch.empty((h, w, ncls), dtype=torch.uint8, device=tdev)
-            _lib.check(lib.asep_aru_forward_dev(self.pb_graph.handle(dev), d_gray.data_ptr(), h, w, d_out.data_ptr(),
-                                                d_u8.data_ptr(), None, 0.0, sp), "asep_aru_forward_dev")
-            return d_u8.cpu().numpy()
-
-    PAGE_LANES = 2                     # lanes of the pipelined run(): stream, model instance and scratch arena each
-
-    def _lane_stream(self, tdev, lane):
-        import torch
-        if lane == 0:
-            return torch.cuda.current_stream(tdev)
-        streams = self.__dict__.setdefault("_lane_streams", {})
-        if (tdev.index, lane) not in streams:
-            streams[(tdev.index, lane)] = torch.cuda.Stream(tdev)
-        return streams[(tdev.index, lane)]
-
-    PAGE_GROUP = 4                     # pages per batched net call of the pipelined run() (asep_aru_forward_batch_dev2: any sizes)
+        t, = self._enqueue_net([image])
+        return t["d_u8"].cpu().numpy()
 
     def enqueue_page(self, image, lane=0):
         """One page = a group of one (see :meth:`enqueue_group`)."""
@@ -329,58 +294,13 @@ class HeadingNetPostProcessor(RegionNetPostProcessor):
         launches), then per page full-size gray + stroke-width distance transform (swt_dist_trafo.py:18-29) -- and return the tickets for
         :meth:`collect_page`.  Neither the net output nor the distance transform leaves HBM."""
         import torch
-        dev = self.device
-        lib = _lib.init_device(dev)
-        tdev = torch.device("cuda", dev)
-        ncls = self.pb_graph.cfg.n_classes
-        _, ws = image_ops._workspace(dev, 0 if lane == 0 else 10 + lane)     # (arena 1 belongs to collect_boxes' side stream)
-        tickets = []
-        with torch.cuda.device(tdev), torch.cuda.stream(self._lane_stream(tdev, lane)):
-            stream = torch.cuda.current_stream(tdev)
-            sp = C.c_void_p(stream.cuda_stream)
+        tickets = self._enqueue_net(images, lane, net=self.weight_dict['net'] > 0)
+        with self._on_lane(lane) as (lib, ws, tdev, stream, sp):
             if getattr(self, "_side_stream", None) is None or self._side_stream.device != tdev:
                 self._side_stream = torch.cuda.Stream(tdev)
-            use_net = self.weight_dict['net'] > 0
-            for image in images:
-                image = np.require(image, dtype=np.uint8, requirements=['C', 'W'])   # Pillow hands out read-only views
-                if image.ndim == 2:
-                    image = image[:, :, None]
-                H, W, Cn = image.shape
-                sc = get_scaling_factor(H, W, self.scaling_factor, fixed_height=self.fixed_height)
-                h, w = image_ops.scaled_size(H, W, sc)
-                t = {"sc": sc, "size": (h, w, ncls), "device": dev, "full": (H, W, Cn)}
-                # the upload is queued like everything else (a page is 0.3 ms of PCIe; a copy on a second stream ended up behind the
-                # engine's kernels in a shared hardware queue and made the host wait for them): ``image`` must stay valid until its
-                # upload has run -- DecodePool(hold=...) guarantees that for its slots, pageable arrays are staged by the runtime
-                # before the call returns
-                d_img = torch.empty((H, W, Cn), dtype=torch.uint8, device=tdev)
-                d_img.copy_(torch.from_numpy(image), non_blocking=True)
-                t["uploaded"] = torch.cuda.Event()
-                t["uploaded"].record(stream)
-                t["d_img"] = d_img
-                if use_net:
-                    d_gray = torch.empty((h, w), dtype=torch.float32, device=tdev)
-                    _lib.check(lib.asep_prep_scale_gray_dev(ws, d_img.data_ptr(), H, W, Cn, float(sc), None,
-                                                            d_gray.data_ptr(), sp), "asep_prep_scale_gray_dev")
-                    t["d_u8"] = torch.empty((h, w, ncls), dtype=torch.uint8, device=tdev)
-                    t["keep"] = (d_gray, torch.empty((h, w, ncls), dtype=torch.float32, device=tdev))
-                tickets.append(t)
-            if use_net:
-                n = len(tickets)
-                handle = self.pb_graph.handle(dev, lane)
-                if n == 1:
-                    t = tickets[0]
-                    _lib.check(lib.asep_aru_forward_dev(handle, t["keep"][0].data_ptr(), t["size"][0], t["size"][1], t["keep"][1].data_ptr(),
-                                                        t["d_u8"].data_ptr(), None, 0.0, sp), "asep_aru_forward_dev")
-                else:
-                    Arr, Ints = C.c_void_p * n, C.c_int32 * n
-                    _lib.check(lib.asep_aru_forward_batch_dev2(
-                        handle, n, Arr(*[t["keep"][0].data_ptr() for t in tickets]), Ints(*[t["size"][0] for t in tickets]),
-                        Ints(*[t["size"][1] for t in tickets]), Arr(*[t["keep"][1].data_ptr() for t in tickets]),
-                        Arr(*[t["d_u8"].data_ptr() for t in tickets]), None, 0.0, sp), "asep_aru_forward_batch_dev2")
             for t in tickets:
-                H, W, Cn = t.pop("full")
-                d_img = t.pop("d_img")
+                d_img = t["d_img"]
+                H, W, Cn = d_img.shape
                 if Cn == 1:
                     d_g8 = d_img
                 else:
@@ -389,8 +309,8 @@ class HeadingNetPostProcessor(RegionNetPostProcessor):
                 d_swt = torch.empty((H, W), dtype=torch.uint8, device=tdev)
                 _lib.check(lib.asep_swt_distance_transform_dev(ws, d_g8.data_ptr(), H, W, d_swt.data_ptr(), sp),
                            "asep_swt_distance_transform_dev")
-                t["swt"] = image_ops.DeviceImage(d_swt, dev)
-                t["inputs"] = (d_img, d_g8)
+                t["swt"] = image_ops.DeviceImage(d_swt, tdev.index)
+                t["d_g8"] = d_g8
                 t["done"] = torch.cuda.Event()
                 t["done"].record(stream)
         return tickets
@@ -410,7 +330,7 @@ class HeadingNetPostProcessor(RegionNetPostProcessor):
         import torch
         dev = t["device"]
         tdev = torch.device("cuda", dev)
-        h, w, ncls = t["size"]
+        h, w = t["size"]
         sc = t["sc"]
         sel = np.flatnonzero(has)
         bx = boxes[sel]
@@ -430,7 +350,7 @@ class HeadingNetPostProcessor(RegionNetPostProcessor):
                 size = hi - lo + 1                                      # nominal width, height
                 x0, x1 = _slice_bounds(lo[:, 0], size[:, 0], w)
                 y0, y1 = _slice_bounds(lo[:, 1], size[:, 1], h)
-                sums = image_ops.box_sums_dev(t["d_u8"].data_ptr(), (h, w, ncls), np.stack([x0, y0, x1, y1], axis=1), channel=0,
+                sums = image_ops.box_sums_dev(t["d_u8"].data_ptr(), tuple(t["d_u8"].shape), np.stack([x0, y0, x1, y1], axis=1), channel=0,
                                               device=dev, stream=sp, lane=1)
                 prob[sel] = sums / 255 / (size[:, 0] * size[:, 1]).astype(np.float64)
             else:
@@ -446,8 +366,7 @@ class HeadingNetPostProcessor(RegionNetPostProcessor):
         # images are decoded ahead of the GPU by worker processes when host_workers > 1 (host_pipeline.py); the fusion
         # itself needs the device again (per-line statistics), so the PAGE-XML part stays in this process
         from .host_pipeline import DecodePool, WritePool, pin_callbacks, single_threaded_children
-        from .net_post_processing_helper import get_scaling_factor
-        pipelined = getattr(self, "host_workers", 0) > 1 and not self.keep_outputs
+        pipelined = self.host_workers > 1 and not self.keep_outputs
         reg, unreg = pin_callbacks(self.device) if pipelined else (None, None)
         n_workers = self.host_workers if pipelined else 0
         geometry = {}                                        # page path -> future of read_line_geometry, a few pages ahead
@@ -467,7 +386,6 @@ class HeadingNetPostProcessor(RegionNetPostProcessor):
                                 geometry[nxt] = parsers.submit(read_line_geometry, get_page_path(nxt))
                 if pipelined:
                     prefetch_geometry(2 * n_workers)
-                pending, n_enqueued = [], 0
 
                 def finish(image_path, ticket):
                     # the GPU owner only measures; parsing happened in a worker, fusion + tags + XML go to a worker
@@ -480,38 +398,25 @@ class HeadingNetPostProcessor(RegionNetPostProcessor):
                     writers.submit(write_heading_page, page_path, image_path, self.fixed_height, self.scaling_factor,
                                    list(values), self.weight_dict, self.threshold, self.thresh_dict, self.text_line_percentage)
 
-                group = self.PAGE_GROUP if pipelined else 1
-                keep = max(2, (self.PAGE_LANES - 1) * group)  # pages queued behind the one whose lines are being measured
-                batch, n_groups, n_paths = [], 0, len(self.image_paths)
-                for n_seen, (image_path, image) in enumerate(DecodePool(self.image_paths, n_workers, register=reg, unregister=unreg,
-                                                                         hold=group + 1 if pipelined else 3), 1):
-                    if pipelined:
-                        # behind the GPU: PAGE_GROUP decoded pages go through ONE batched net call, consecutive groups on alternating lanes; the next
-                        # group is uploaded and queued before a page's lines are measured (the measuring calls wait for their small kernels; the chip
-                        # has the next nets to work on meanwhile).  The last pages are uploaded HERE: the pool releases its slots when it ends.
-                        batch.append((image_path, image))
-                        if len(batch) >= group or n_seen == n_paths:
-                            tickets = self.enqueue_group([img for _, img in batch], lane=n_groups % self.PAGE_LANES)
-                            n_groups += 1
-                            pending.extend((pth, t) for (pth, _), t in zip(batch, tickets))
-                            while len(pending) > keep:
-                                finish(*pending.pop(0))
-                            tickets[-1]["uploaded"].synchronize()    # the images' slots may be recycled from here on
-                            batch.clear()
-                        continue
-                    if self.weight_dict['net'] > 0:
-                        net_output = self.heading_probability(image)
-                        net_output_post = self.post_process(net_output)
-                        if self.keep_outputs:
-                            self.net_outputs.append(net_output)
-                            self.net_outputs_post.append(net_output_post)
-                    else:
-                        net_output_post = None
-                    swt_feature_image = self.SWT.distance_transform(image, on_device=True)
-                    new_page_objects.append(self.to_page_xml(get_page_path(image_path), image_path, net_output_post,
-                                                             swt_feature_image))
-                for item in pending:
-                    finish(*item)
+                decode = DecodePool(self.image_paths, n_workers, register=reg, unregister=unreg,
+                                    hold=self.PAGE_GROUP + 1 if pipelined else 3)
+                if pipelined:
+                    # behind the GPU: the next group is uploaded and queued before a page's lines are measured (the measuring calls
+                    # wait for their small kernels; the chip has the next nets to work on meanwhile)
+                    self._run_groups(decode, len(self.image_paths), self.PAGE_GROUP, self.PAGE_LANES, self.enqueue_group, finish)
+                else:
+                    for image_path, image in decode:
+                        if self.weight_dict['net'] > 0:
+                            net_output = self.heading_probability(image)
+                            net_output_post = self.post_process(net_output)
+                            if self.keep_outputs:
+                                self.net_outputs.append(net_output)
+                                self.net_outputs_post.append(net_output_post)
+                        else:
+                            net_output_post = None
+                        swt_feature_image = self.SWT.distance_transform(image, on_device=True)
+                        new_page_objects.append(self.to_page_xml(get_page_path(image_path), image_path, net_output_post,
+                                                                 swt_feature_image))
             finally:
                 if pipelined:
                     parsers.shutdown()

@@ -6,6 +6,7 @@ base class ``region_net_post_processor_base.py`` (same class / method names, arg
 GPU: uint8 upload -> resize + gray (a1) -> ARU-Net with fused uint8 / threshold epilogue (a3-a8) -> CC filter and
 rectangular openings on bit planes (a9); only the two masks come back for polygon extraction (a10).
 """
+import contextlib
 import ctypes as C
 import time
 
@@ -13,9 +14,7 @@ import numpy as np
 
 from . import _lib, image_ops, polygonize
 from .host_util import rescale_points
-from .image_io import load_image_bgr
-from .net_post_processing_helper import (AruGraph, _device_of, apply_threshold, get_net_output, get_scaling_factor,
-                                         load_graph)
+from .net_post_processing_helper import _device_of, get_scaling_factor, load_graph
 from .path_util import get_page_path, load_list_file
 from .region_to_page_writer import SEPARATOR_REGION, SeparatorRegionToPageWriter
 
@@ -69,6 +68,110 @@ class RegionNetPostProcessor:
                                           for polygon in polygon_list]
         return polygons_dict
 
+    # -- the device pipeline both net post-processors share --------------------------------------------------------
+    PAGE_LANES = 2                     # pages in flight of the pipelined run() (= streams / model instances / scratch arenas)
+    PAGE_GROUP = 4                     # pages per batched net call of the pipelined run() (asep_aru_forward_batch_dev2: any sizes)
+
+    def _lane_stream(self, tdev, lane):
+        """lane 0 works on the caller's current stream; further lanes own a stream (and a model instance and a scratch
+        arena), so that pages of different lanes share the chip"""
+        import torch
+        if lane == 0:
+            return torch.cuda.current_stream(tdev)
+        streams = self.__dict__.setdefault("_lane_streams", {})
+        if (tdev.index, lane) not in streams:
+            streams[(tdev.index, lane)] = torch.cuda.Stream(tdev)
+        return streams[(tdev.index, lane)]
+
+    @contextlib.contextmanager
+    def _on_lane(self, lane):
+        """``lane``'s stream made current on the device -> (library, the lane's scratch arena, torch device, stream, stream
+        handle).  Lane 0 uses arena 0, lane l > 0 arena 10 + l (arena 1 belongs to the heading's collect_boxes side stream)."""
+        import torch
+        dev = self.device
+        tdev = torch.device("cuda", dev)
+        _, ws = image_ops._workspace(dev, 0 if lane == 0 else 10 + lane)
+        with torch.cuda.device(tdev), torch.cuda.stream(self._lane_stream(tdev, lane)):
+            stream = torch.cuda.current_stream(tdev)
+            yield _lib.init_device(dev), ws, tdev, stream, C.c_void_p(stream.cuda_stream)
+
+    def _enqueue_net(self, images, lane=0, net=True, mask=False):
+        """Queue the front end of a group of decoded pages of ANY sizes on ``lane``'s stream: per page the upload, resize + gray
+        and the output buffers, then ONE batched net call for the group (asep_aru_forward_batch_dev2: the pages share every
+        layer's launches) with the uint8 epilogue and, with ``mask``, the mask thresholded at ``self.threshold``.  ``net``
+        False queues the uploads only.  ``images`` have to stay valid until their ``uploaded`` events.
+        -> one ticket per page: "sc", "size" (h, w), "device", "uploaded", "d_img"; with the net also "d_gray", "d_out",
+        "d_u8" (and "d_mask"), all kept alive by the ticket until the page is collected"""
+        import torch
+        ncls = self.pb_graph.cfg.n_classes
+        tickets = []
+        with self._on_lane(lane) as (lib, ws, tdev, stream, sp):
+            for image in images:
+                image = np.require(image, dtype=np.uint8, requirements=['C', 'W'])   # Pillow hands out read-only views
+                if image.ndim == 2:
+                    image = image[:, :, None]
+                H, W, Cn = image.shape
+                sc = get_scaling_factor(H, W, self.scaling_factor, fixed_height=self.fixed_height)
+                h, w = image_ops.scaled_size(H, W, sc)
+                # the upload is queued like everything else (a page is 0.3 ms of PCIe; a copy on a second stream ended up behind the
+                # engine's kernels in a shared hardware queue and made the host wait for them): ``image`` must stay valid until the
+                # page's upload has run -- DecodePool(hold=...) guarantees that for its slots, pageable arrays are staged by the runtime
+                # before the call returns
+                d_img = torch.empty((H, W, Cn), dtype=torch.uint8, device=tdev)
+                d_img.copy_(torch.from_numpy(image), non_blocking=True)
+                t = {"sc": sc, "size": (h, w), "device": tdev.index, "d_img": d_img, "uploaded": torch.cuda.Event()}
+                t["uploaded"].record(stream)
+                if net:
+                    t["d_gray"] = torch.empty((h, w), dtype=torch.float32, device=tdev)
+                    _lib.check(lib.asep_prep_scale_gray_dev(ws, d_img.data_ptr(), H, W, Cn, float(sc), None,
+                                                            t["d_gray"].data_ptr(), sp), "asep_prep_scale_gray_dev")
+                    t["d_out"] = torch.empty((h, w, ncls), dtype=torch.float32, device=tdev)
+                    t["d_u8"] = torch.empty((h, w, ncls), dtype=torch.uint8, device=tdev)
+                    if mask:
+                        t["d_mask"] = torch.empty((h, w, ncls), dtype=torch.uint8, device=tdev)
+                tickets.append(t)
+            if net:
+                n = len(tickets)
+                Arr, Ints = C.c_void_p * n, C.c_int32 * n
+
+                def ptrs(key):
+                    return Arr(*[t[key].data_ptr() for t in tickets])
+                _lib.check(lib.asep_aru_forward_batch_dev2(
+                    self.pb_graph.handle(tdev.index, lane), n, ptrs("d_gray"), Ints(*[t["size"][0] for t in tickets]),
+                    Ints(*[t["size"][1] for t in tickets]), ptrs("d_out"), ptrs("d_u8"), ptrs("d_mask") if mask else None,
+                    float(self.threshold) if mask else 0.0, sp), "asep_aru_forward_batch_dev2")
+        return tickets
+
+    def _run_groups(self, decode, n_paths, group, lanes, enqueue, finish):
+        """Drive the device stages over ``decode``, an iterator of ``n_paths`` decoded (path, image) pages: ``group`` consecutive
+        pages go through ``enqueue(images, lane) -> tickets`` together, consecutive groups on alternating lanes (streams, model
+        instances, scratch arenas), and ``finish(path, ticket)`` takes the pages in order while up to ``(lanes - 1) * group``
+        newer pages stay in flight -- the chip works on the next groups' nets while a group's classical stages, small kernels
+        that do not fill it, run and while this process finishes pages on the host."""
+        keep = max(1, (lanes - 1) * group)
+        pending, batch, n_groups, n_seen = [], [], 0, 0
+        t_prev = t_run = time.perf_counter()
+        for n_seen, (path, image) in enumerate(decode, 1):
+            t_dev = time.perf_counter()
+            if self.first_page_seconds is None:          # worker start-up + slot page-locking + the first decode
+                self.first_page_seconds = t_dev - t_run
+            self.wait_seconds += t_dev - t_prev
+            batch.append((path, image))
+            if len(batch) >= group or n_seen == n_paths:   # (the last pages are uploaded HERE: a DecodePool releases its slots when it ends)
+                tickets = enqueue([img for _, img in batch], n_groups % lanes)
+                n_groups += 1
+                self.device_seconds += time.perf_counter() - t_dev
+                pending.extend((p, t) for (p, _), t in zip(batch, tickets))
+                while len(pending) > keep:
+                    finish(*pending.pop(0))
+                tickets[-1]["uploaded"].synchronize()        # (long done) the images' slots may be recycled from here on
+                batch.clear()
+            t_prev = time.perf_counter()
+        if n_seen != n_paths:
+            raise RuntimeError(f"the decoder yielded {n_seen} of {n_paths} pages")
+        for item in pending:
+            finish(*item)
+
 
 def write_separator_page(page_path, image_path, fixed_height, scaling_factor, polygons_dict):
     """:120-133 as a plain function (runs in a WritePool worker): regions into the PAGE-XML next to the image"""
@@ -98,20 +201,6 @@ class SeparatorNetPostProcessor(RegionNetPostProcessor):
 
     # -- the fused device path ---------------------------------------------------------------------------------
     SEGMENT_CAPACITY = 1 << 14         # boundary segments per mask copied back without asking (a page has a few hundred)
-    PAGE_LANES = 2                     # pages in flight of the pipelined run() (= streams / model instances / scratch arenas)
-
-    def _lane_stream(self, tdev, lane):
-        """lane 0 works on the caller's current stream; further lanes own a stream (and, below, a model instance and a scratch
-        arena), so that pages of different lanes share the chip"""
-        import torch
-        if lane == 0:
-            return torch.cuda.current_stream(tdev)
-        streams = self.__dict__.setdefault("_lane_streams", {})
-        if (tdev.index, lane) not in streams:
-            streams[(tdev.index, lane)] = torch.cuda.Stream(tdev)
-        return streams[(tdev.index, lane)]
-
-    PAGE_GROUP = 4                     # pages per batched net call of the pipelined run() (asep_aru_forward_batch_dev2: any sizes)
 
     def enqueue_page(self, image, edges_only=True, lane=0):
         """One page = a group of one (see :meth:`enqueue_group`)."""
@@ -127,62 +216,18 @@ class SeparatorNetPostProcessor(RegionNetPostProcessor):
         the segment keys into page-locked host memory -- so ``image`` has to stay valid until the ticket is collected.  Same arithmetic as load_and_scale_image ->
         get_net_output -> uint8(x*255) -> apply_threshold -> post_process (:141-151), executed without leaving HBM."""
         import torch
-        dev = self.device
-        lib = _lib.init_device(dev)
-        tdev = torch.device("cuda", dev)
+        tickets = self._enqueue_net(images, lane, mask=True)
         ncls = self.pb_graph.cfg.n_classes
-        _, ws = image_ops._workspace(dev, lane)
-        tickets = []
-        with torch.cuda.device(tdev), torch.cuda.stream(self._lane_stream(tdev, lane)):
-            stream = torch.cuda.current_stream(tdev)
-            sp = C.c_void_p(stream.cuda_stream)
-            for image in images:
-                image = np.require(image, dtype=np.uint8, requirements=['C', 'W'])   # Pillow hands out read-only views
-                if image.ndim == 2:
-                    image = image[:, :, None]
-                H, W, Cn = image.shape
-                sc = get_scaling_factor(H, W, self.scaling_factor, fixed_height=self.fixed_height)
-                h, w = image_ops.scaled_size(H, W, sc)
-                t = {"sc": sc, "size": (h, w), "edges_only": edges_only, "device": dev}
-                # the upload is queued like everything else (a page is 0.3 ms of PCIe; a copy on a second stream ended up behind the
-                # engine's kernels in a shared hardware queue and made the host wait for them): ``image`` must stay valid until the
-                # page's upload has run -- DecodePool(hold=...) guarantees that for its slots, pageable arrays are staged by the runtime
-                # before the call returns
-                d_img = torch.empty((H, W, Cn), dtype=torch.uint8, device=tdev)
-                d_img.copy_(torch.from_numpy(image), non_blocking=True)
-                t["uploaded"] = torch.cuda.Event()
-                t["uploaded"].record(stream)
-                d_gray = torch.empty((h, w), dtype=torch.float32, device=tdev)
-                _lib.check(lib.asep_prep_scale_gray_dev(ws, d_img.data_ptr(), H, W, Cn, float(sc), None,
-                                                        d_gray.data_ptr(), sp), "asep_prep_scale_gray_dev")
-                d_out = torch.empty((h, w, ncls), dtype=torch.float32, device=tdev)
-                d_u8 = torch.empty((h, w, ncls), dtype=torch.uint8, device=tdev)
-                d_mask = torch.empty((h, w, ncls), dtype=torch.uint8, device=tdev)
-                t["keep"] = (d_img, d_gray, d_out, d_u8, d_mask)          # alive until the page is collected
-                tickets.append(t)
-            n = len(tickets)
-            handle = self.pb_graph.handle(dev, lane)
-            if n == 1:
-                d_img, d_gray, d_out, d_u8, d_mask = tickets[0]["keep"]
-                h, w = tickets[0]["size"]
-                _lib.check(lib.asep_aru_forward_dev(handle, d_gray.data_ptr(), h, w, d_out.data_ptr(), d_u8.data_ptr(), d_mask.data_ptr(),
-                                                    float(self.threshold), sp), "asep_aru_forward_dev")
-            else:
-                Arr, Ints = C.c_void_p * n, C.c_int32 * n
-                keep = [t["keep"] for t in tickets]
-                _lib.check(lib.asep_aru_forward_batch_dev2(
-                    handle, n, Arr(*[k[1].data_ptr() for k in keep]), Ints(*[t["size"][0] for t in tickets]), Ints(*[t["size"][1] for t in tickets]),
-                    Arr(*[k[2].data_ptr() for k in keep]), Arr(*[k[3].data_ptr() for k in keep]), Arr(*[k[4].data_ptr() for k in keep]),
-                    float(self.threshold), sp), "asep_aru_forward_batch_dev2")
+        with self._on_lane(lane) as (lib, ws, tdev, stream, sp):
             for t in tickets:
-                d_img, d_gray, d_out, d_u8, d_mask = t["keep"]
+                t["edges_only"] = edges_only
                 h, w = t["size"]
                 size = h * w
                 min_size = int(size * (1 / size * 100))
                 k_h, k_v, k_c = image_ops.separator_kernel_sizes(h, w)
                 d_hz = torch.empty((h, w), dtype=torch.uint8, device=tdev)
                 d_vt = torch.empty((h, w), dtype=torch.uint8, device=tdev)
-                _lib.check(lib.asep_post_separator_dev(ws, d_mask.data_ptr(), h, w, ncls, 0, min_size, k_h, k_v, k_c,
+                _lib.check(lib.asep_post_separator_dev(ws, t["d_mask"].data_ptr(), h, w, ncls, 0, min_size, k_h, k_v, k_c,
                                                        d_hz.data_ptr(), d_vt.data_ptr(), sp), "asep_post_separator_dev")
                 t["masks"] = {"horizontal": d_hz, "vertical": d_vt}
                 if edges_only:
@@ -204,7 +249,7 @@ class SeparatorNetPostProcessor(RegionNetPostProcessor):
                         t["h_masks"][k].copy_(d_m, non_blocking=True)
                 if self.keep_outputs:
                     t["h_u8"] = torch.empty((h, w, ncls), dtype=torch.uint8, pin_memory=True)
-                    t["h_u8"].copy_(d_u8, non_blocking=True)
+                    t["h_u8"].copy_(t["d_u8"], non_blocking=True)
                 t["done"] = torch.cuda.Event()
                 t["done"].record(stream)
         return tickets
@@ -283,42 +328,9 @@ class SeparatorNetPostProcessor(RegionNetPostProcessor):
         group = self.PAGE_GROUP if pipelined else 1
         decode = DecodePool(self.image_paths, self.host_workers if pipelined else 0, register=reg, unregister=unreg, hold=group + 1)
         with WritePool(self.host_workers if pipelined else 0) as writers:
-            t_prev = t_run = time.perf_counter()
-            pending, n_groups = [], 0
-            lanes = self.PAGE_LANES if pipelined else 1
-            batch = []
-
-            def flush():
-                """the decoded pages waiting in ``batch`` as ONE group on the next lane; a lane's previous group has been collected before"""
-                nonlocal n_groups, t_prev
-                t_dev = time.perf_counter()
-                tickets = self.enqueue_group([img for _, img in batch], edges_only=not self.keep_outputs, lane=n_groups % lanes)
-                n_groups += 1
-                self.device_seconds += time.perf_counter() - t_dev
-                pending.extend((path, t) for (path, _), t in zip(batch, tickets))
-                while len(pending) > max(1, (lanes - 1) * group):    # (the newest group stays in flight while older pages' rings are chained)
-                    self._finish_page(*pending.pop(0), writers, pipelined, page_objects)
-                tickets[-1]["uploaded"].synchronize()        # (long done) the images' slots may be recycled from here on
-                batch.clear()
-                t_prev = time.perf_counter()
-
-            n_paths = len(self.image_paths)
-            for n_seen, (image_path, image) in enumerate(decode, 1):
-                t_dev = time.perf_counter()
-                if self.first_page_seconds is None:          # worker start-up + slot page-locking + the first decode
-                    self.first_page_seconds = t_dev - t_run
-                self.wait_seconds += t_dev - t_prev
-                # pipelined: PAGE_GROUP consecutive pages per batched net call, consecutive groups on alternating lanes (streams, model
-                # instances, scratch arenas): the chip works on the next group's nets while a group's classical stages -- small kernels that do
-                # not fill it -- run, and while this process chains rings
-                batch.append((image_path, image))
-                if len(batch) >= group or n_seen == n_paths:   # (the last pages are uploaded HERE: the pool releases its slots when it ends)
-                    flush()
-                else:
-                    t_prev = time.perf_counter()
-            assert not batch
-            for item in pending:
-                self._finish_page(*item, writers, pipelined, page_objects)
+            self._run_groups(decode, len(self.image_paths), group, self.PAGE_LANES if pipelined else 1,
+                             lambda images, lane: self.enqueue_group(images, edges_only=not self.keep_outputs, lane=lane),
+                             lambda path, t: self._finish_page(path, t, writers, pipelined, page_objects))
         return page_objects
 
 

@@ -219,6 +219,58 @@ def test_heading_without_net_weight_uses_only_swt(tmp_path):
     assert {r.region_type for r in out.get_text_regions()} == {"paragraph"}
 
 
+def _run_groups_logged(proc, n_paths, n_yield, group, lanes):
+    """RegionNetPostProcessor._run_groups over ``n_yield`` fake decoded pages with a fake enqueue and a recording finish
+    -> (event log, the most pages pending at once)"""
+    class Uploaded:
+        def synchronize(self):
+            pass
+    log, pending, most = [], set(), [0]
+
+    def decode():
+        for k in range(n_yield):
+            log.append(("next", k))
+            yield f"p{k}", k
+        log.append(("end",))
+
+    def enqueue(images, lane):
+        log.append(("enqueue", tuple(images), lane))
+        pending.update(images)
+        most[0] = max(most[0], len(pending))
+        return [{"page": k, "uploaded": Uploaded()} for k in images]
+
+    def finish(path, ticket):
+        assert path == f"p{ticket['page']}"
+        pending.remove(ticket["page"])
+        log.append(("finish", ticket["page"]))
+    proc._run_groups(decode(), n_paths, group, lanes, enqueue, finish)
+    return log, most[0]
+
+
+@pytest.mark.parametrize("group,lanes", [(4, 2), (1, 1), (3, 3)])
+def test_grouping_loop_finishes_every_page_once_in_order(tmp_path, group, lanes):
+    """the pipelined run() of both net post-processors: groups of ``group`` pages on alternating lanes, at most
+    keep = max(1, (lanes - 1) * group) pages left in flight behind the newest group; the last, partial group is enqueued
+    before the decoder is asked for another page (a DecodePool releases its slots when it ends)"""
+    proc = _heading_processor(tmp_path)
+    n = 10
+    log, most = _run_groups_logged(proc, n, n, group, lanes)
+    assert [e[1] for e in log if e[0] == "finish"] == list(range(n))
+    groups = [e for e in log if e[0] == "enqueue"]
+    assert [k for g in groups for k in g[1]] == list(range(n))
+    assert [g[2] for g in groups] == [i % lanes for i in range(len(groups))]
+    assert all(len(g[1]) == group for g in groups[:-1]) and 1 <= len(groups[-1][1]) <= group
+    assert most <= max(1, (lanes - 1) * group) + group
+    assert log.index(groups[-1]) == log.index(("next", n - 1)) + 1 and log.index(groups[-1]) < log.index(("end",))
+    assert proc.first_page_seconds is not None
+
+
+@pytest.mark.parametrize("n_yield", [7, 8, 0])
+def test_grouping_loop_raises_when_the_decoder_yields_too_few_pages(tmp_path, n_yield):
+    with pytest.raises(RuntimeError, match=f"{n_yield} of 10"):
+        _run_groups_logged(_heading_processor(tmp_path), 10, n_yield, 4, 2)
+
+
 def test_swt_component_cleaning():
     from citlab_article_separation_new_amd.heading_net_post_processor import StrokeWidthDistanceTransform
     s = StrokeWidthDistanceTransform()
