@@ -10,6 +10,7 @@
 #include "res8v_kernels.h"
 #include "bf16_kernels.h"
 #include "res8w_kernels.h"
+#include "res8ws_kernels.h"
 #include "convr_kernels.h"
 #include "split_kernels.h"
 #include "asep_common.h"
@@ -99,6 +100,11 @@ struct asep_aru {
     float* d_r8v_up_w1 = nullptr;    // [2][R8V_FILTER]
     float* d_r8v_up_wr = nullptr;    // [3][R8V_FILTER]
     bool r8_valu = true;             // fp32 only; ASEP_R8_VALU=0 runs the fp32 MFMA variants instead
+    // f32s engine, ReLU graph: the level-0 blocks as split-product strip walkers (res8ws_kernels.h); three-part pair fragments [..][part 3][64][8]
+    bool use_split_walk = true;      // ASEP_SPLIT_WALK=0: f32s level 0 on res8v_*_kernel instead
+    bf16_t* d_r8ws_down_w = nullptr; // [3 convs][3 ky][3 parts][64][8]
+    bf16_t* d_r8ws_up_w = nullptr;   // [3 convs][3 ky][3 parts][64][8]
+    bf16_t* d_r8ws_up_w1 = nullptr;  // conv1 of unet_up_0 [3 ky][2 sources][3 parts][64][8]
     bool use_fused8 = true;          // ASEP_FUSED8=0 falls back to the layer-by-layer kernels
     bool fused8_wanted = true;       // what ASEP_FUSED8 said (use_fused8 is also switched off for the graph variants)
     bool fused8_var = false;         // elu / leaky RESIDUAL graphs: the level-0 blocks on res8v_*_kernel<activation> (round 4)
@@ -954,6 +960,84 @@ bool r8v_fits(const TL& l) {
     return true;
 }
 
+// f32s level 0 on the split-product strip walkers (res8ws_kernels.h): pages with room for four strips and two 16-row bands (and 32-bit
+// element offsets for the vector-ALU frame), ReLU graph only
+bool r8ws_fits(const Tensor& t) {
+    return (t.W - 4 - R8W_X0) / R8W_TW >= 4 && t.H - 4 - R8W_Y0 >= 32 && (size_t)t.H * t.W < ((size_t)1 << 28);
+}
+bool r8ws_on(asep_aru* m) { return m->split && m->use_split_walk && m->r8_valu && m->cfg.activation == 0 && m->d_r8ws_down_w; }
+// the work units of a res8v launch over `a` (unit height R8_OH * R8_NP) that the strip walkers do not cover: for a page in `walk`, the units
+// that touch the frame around its walker region (res8ws_kernels.h), for the other pages all units.  Cached device list; nullptr on failure.
+const int32_t* r8ws_frame_units(asep_aru* m, const Res8Args& a, const std::vector<bool>& walk, int* count) {
+    std::string key = "f";
+    for (int i = 0; i < a.nprob; ++i) key += ":" + std::to_string(a.p[i].H) + "x" + std::to_string(a.p[i].W) + (walk[i] ? "w" : "t");
+    std::vector<int32_t> units;
+    constexpr int UH = R8_OH * R8_NP;
+    for (int i = 0; i < a.nprob; ++i) {
+        const Res8Prob& p = a.p[i];
+        const int ty = cdiv(p.H, UH), tx = p.tiles_x;
+        const int xr = R8W_X0 + R8W_TW * ((p.W - 4 - R8W_X0) / R8W_TW), ye = R8W_Y0 + 2 * ((p.H - 4 - R8W_Y0) / 2);
+        for (int y = 0; y < ty; ++y)
+            for (int x = 0; x < tx; ++x) {
+                const int ux0 = x * R8_OW, ux1 = std::min(ux0 + R8_OW, p.W), uy0 = y * UH, uy1 = std::min(uy0 + UH, p.H);
+                const bool frame = !walk[i] || ux0 < R8W_X0 || ux1 > xr || uy0 < R8W_Y0 || uy1 > ye;
+                if (frame) units.push_back(p.tile_begin + y * tx + x);
+            }
+    }
+    *count = (int)units.size();
+    auto it = m->sched_cache.find(key);
+    if (it != m->sched_cache.end()) return it->second;
+    int32_t* d = nullptr;
+    if (units.empty() || hipMalloc((void**)&d, units.size() * sizeof(int32_t)) != hipSuccess) return nullptr;
+    if (hipMemcpy(d, units.data(), units.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
+    m->owned.push_back(d);
+    m->sched_cache[key] = d;
+    return d;
+}
+
+// the walker launch for the pages of a (a.p[i] for walk[i]); the frame units must have been launched before it on the same stream
+void run_res8ws(asep_aru* m, bool up, const Res8Args& a, const std::vector<bool>& walk, const std::string& what) {
+    Res8WSArgs wa{};
+    int n = 0, items = 0;
+    double flops = 0, bytes = 0;
+    long strip_rows = 0;
+    for (int i = 0; i < a.nprob; ++i) {
+        if (!walk[i]) continue;
+        const Res8Prob& q = a.p[i];
+        Res8WSProb& p = wa.p[n++];
+        if (up) { p.skip = q.img; p.dec = q.in1; }
+        else { p.img = q.img; p.stats = q.stats; p.pool = q.pool; }
+        p.out = q.out;
+        p.H = q.H; p.W = q.W;
+        p.n_strips = (p.W - 4 - R8W_X0) / R8W_TW;
+        p.y_end = R8W_Y0 + 2 * ((p.H - 4 - R8W_Y0) / 2);
+        strip_rows += (long)p.n_strips * (p.y_end - R8W_Y0);
+        const double px = (double)p.n_strips * R8W_TW * (p.y_end - R8W_Y0);
+        flops += 2.0 * px * (9.0 * (up ? 16 : 1) * 8 + 3 * 9.0 * 64);
+        bytes += px * ((up ? 64.0 : 4.0) + 32.0 + (p.pool ? 8.0 : 0.0));
+    }
+    if (!n) return;
+    // rows of an item: ~6 items per resident wave of the chip (four waves per CU), so that the block dispatch balances the tail
+    const long slots = 4L * m->num_cus;
+    int band = (int)std::min<long>(256, std::max<long>(32, strip_rows / (6 * slots)));
+    band = (band + 1) & ~1;
+    for (int i = 0; i < n; ++i) {
+        Res8WSProb& p = wa.p[i];
+        p.band = band;
+        p.tile_begin = items;
+        items += p.n_strips * cdiv(p.y_end - R8W_Y0, band);
+    }
+    wa.nprob = n;
+    if (up) { wa.b1 = m->d_r8_up_b1; wa.w1s = (const u32x4*)m->d_r8ws_up_w1; wa.ws = (const u32x4*)m->d_r8ws_up_w; wa.bias = m->d_r8_up_br; }
+    else { wa.b1 = m->det_first.d_b; wa.w1f = m->det_first.d_w; wa.ws = (const u32x4*)m->d_r8ws_down_w; wa.bias = m->d_r8_down_br; }
+    int units = items;
+    wa.xm = oneshot_map(m, items, &units);
+    ProfScope ps(m, up ? "res8ws_kernel<true>" : "res8ws_kernel<false>", flops, what);
+    ps.bytes = bytes;
+    if (up) hipLaunchKernelGGL(res8ws_kernel<true>, dim3(units), dim3(64), 0, m->stream, wa);
+    else hipLaunchKernelGGL(res8ws_kernel<false>, dim3(units), dim3(64), 0, m->stream, wa);
+}
+
 void run_res8_down(asep_aru* m, const TL& imgs, const std::vector<const float*>& stats, bool want_pool, TL* d_out, TL* pool_out) {
     for (const Tensor& t : imgs) {
         d_out->push_back(new_tensor(m, t.H, t.W, 8));
@@ -983,9 +1067,30 @@ void run_res8_down(asep_aru* m, const TL& imgs, const std::vector<const float*>&
         a.wr = (const f32x4*)(valu ? m->d_r8v_down_wr : m->d_r8_down_wr); a.br = m->d_r8_down_br;
         TL sub(imgs.begin() + b0, imgs.begin() + b1);
         const std::string pname = valu ? std::string("res8v_down_kernel<0>") : std::string("res8_down_kernel<false>");   // (rocprofv3's names: template arguments spelled out)
+        a.sched = tile_schedule(m, a, std::min(tiles, m->num_cus), R8_OH * R8_NP);
+        if (valu && r8ws_on(m)) {
+            // the frame units on res8v_down_kernel, then the split-product walkers over the rest of the pages that have room for them
+            std::vector<bool> walk(a.nprob);
+            bool any = false;
+            for (int i = 0; i < a.nprob; ++i) { walk[i] = r8ws_fits(imgs[b0 + i]); any = any || walk[i]; }
+            if (any) {
+                int nu = 0;
+                Res8Args f = a;
+                f.sched = r8ws_frame_units(m, a, walk, &nu);
+                if (!f.sched) { set_error("level-0 frame schedule: device allocation failed"); throw ArgError(); }
+                f.total_tiles = nu;
+                {
+                    const double share = (double)nu / tiles;          // (the frame units' share of the launch's work units)
+                    ProfScope ps(m, pname, flops * share, "unet_down_0 frame " + dims_of(sub));
+                    ps.bytes = bytes * share;
+                    hipLaunchKernelGGL(res8v_down_kernel<0>, dim3(std::min(nu, m->num_cus)), dim3(R8_THREADS), R8_DOWN_LDS, m->stream, f);
+                }
+                run_res8ws(m, false, a, walk, "unet_down_0 (conv1+3xconvR+add+pool) " + dims_of(sub));
+                continue;
+            }
+        }
         ProfScope ps(m, pname, flops, "unet_down_0 (conv1+3xconvR+add+pool) " + dims_of(sub));
         ps.bytes = bytes;
-        a.sched = tile_schedule(m, a, std::min(tiles, m->num_cus), R8_OH * R8_NP);
         const dim3 gd(std::min(tiles, m->num_cus));
         const int actv = m->cfg.activation;                  // graph variants (fused8_var): the same block with elu / leaky (vector-ALU form only)
         if (actv && !valu) { set_error("level-0 block of an elu / leaky graph: image too large for the vector-ALU kernel"); throw ArgError(); }
@@ -1023,9 +1128,29 @@ TL run_res8_up(asep_aru* m, const TL& skip, const TL& v) {
         a.wr = (const f32x4*)(valu ? m->d_r8v_up_wr : m->d_r8_up_wr); a.br = m->d_r8_up_br;
         TL sub(skip.begin() + b0, skip.begin() + b1);
         const std::string pname = valu ? std::string("res8v_up_kernel<0>") : std::string("res8_up_kernel<false>");
+        a.sched = tile_schedule(m, a, std::min(tiles, m->num_cus), R8_OH * R8_NP);
+        if (valu && r8ws_on(m) && m->d_r8ws_up_w1) {
+            std::vector<bool> walk(a.nprob);
+            bool any = false;
+            for (int i = 0; i < a.nprob; ++i) { walk[i] = r8ws_fits(skip[b0 + i]); any = any || walk[i]; }
+            if (any) {
+                int nu = 0;
+                Res8Args f = a;
+                f.sched = r8ws_frame_units(m, a, walk, &nu);
+                if (!f.sched) { set_error("level-0 frame schedule: device allocation failed"); throw ArgError(); }
+                f.total_tiles = nu;
+                {
+                    const double share = (double)nu / tiles;          // (the frame units' share of the launch's work units)
+                    ProfScope ps(m, pname, flops * share, "unet_up_0 frame " + dims_of(sub));
+                    ps.bytes = bytes * share;
+                    hipLaunchKernelGGL(res8v_up_kernel<0>, dim3(std::min(nu, m->num_cus)), dim3(R8_THREADS), R8_UP_LDS, m->stream, f);
+                }
+                run_res8ws(m, true, a, walk, "unet_up_0 (conv1[16->8]+3xconvR+add) " + dims_of(sub));
+                continue;
+            }
+        }
         ProfScope ps(m, pname, flops, "unet_up_0 (conv1[16->8]+3xconvR+add) " + dims_of(sub));
         ps.bytes = bytes;
-        a.sched = tile_schedule(m, a, std::min(tiles, m->num_cus), R8_OH * R8_NP);
         const dim3 grid(std::min(tiles, m->num_cus));
         const int actv = m->cfg.activation;
         if (actv && !valu) { set_error("level-0 block of an elu / leaky graph: image too large for the vector-ALU kernel"); throw ArgError(); }
@@ -1264,6 +1389,58 @@ void pack_pair_frags(const HostTensor& w, int cin, std::vector<bf16_t>& dst) {
                     const int kx = p - e;
                     dst.push_back(f2bf((kx >= 0 && kx <= 2) ? w.data[(((size_t)ky * 3 + kx) * cin + ci) * 8 + co] : 0.f));
                 }
+}
+
+// three-part pair fragments of the 8 input channels ci0 .. ci0 + 7 of a 3 x 3 filter W[3][3][cin][8], one filter row: [part 3][64 lanes][8]
+// (res8ws_kernels.h; the pair-window mapping of pack_pair_frags, the cut of pack_conv_split)
+void pack_pair_split(const HostTensor& w, int cin, int ci0, int ky, std::vector<bf16_t>& dst) {
+    auto bfval = [](bf16_t b) { uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; };
+    std::vector<bf16_t> part[3];
+    for (int lane = 0; lane < 64; ++lane)
+        for (int i = 0; i < 8; ++i) {
+            const int mr = lane & 15, kk = lane >> 4, e = mr >> 3, co = mr & 7, kx = kk - e;
+            const float v = (kx >= 0 && kx <= 2) ? w.data[(((size_t)ky * 3 + kx) * cin + ci0 + i) * 8 + co] : 0.f;
+            const bf16_t h = f2bf(v);
+            const float r = v - bfval(h);
+            const bf16_t mm = f2bf(r);
+            part[0].push_back(h); part[1].push_back(mm); part[2].push_back(f2bf(r - bfval(mm)));
+        }
+    for (int p = 0; p < 3; ++p) dst.insert(dst.end(), part[p].begin(), part[p].end());
+}
+
+// the split-product walkers' filters (f32s engine): both level-0 tails and the UP block's conv1; left unset (the walkers off) for other shapes
+int pack_res8ws(asep_aru* m, const std::map<std::string, HostTensor>& blob) {
+    auto tail = [&](const std::string& scope, std::vector<bf16_t>& pk) -> bool {
+        for (int r = 0; r < 3; ++r) {
+            auto wi = blob.find(scope + "/convR_" + std::to_string(r) + "/weights");
+            if (wi == blob.end()) return false;
+            const HostTensor& w = wi->second;
+            if (w.dims.size() != 4 || w.dims[0] != 3 || w.dims[1] != 3 || w.dims[2] != 8 || w.dims[3] != 8) return false;
+            for (int ky = 0; ky < 3; ++ky) pack_pair_split(w, 8, 0, ky, pk);
+        }
+        return true;
+    };
+    std::vector<bf16_t> dw, uw, u1;
+    if (!tail("aru_net/featMapG/unet_down_0", dw)) return ASEP_OK;
+    if (m->cfg.scale_space_num > 1) {
+        const std::string u = "aru_net/featMapG/unet_up_0";
+        auto w1 = blob.find(u + "/conv1/weights");
+        if (!tail(u, uw) || w1 == blob.end()) return ASEP_OK;
+        const HostTensor& w = w1->second;
+        if (w.dims.size() != 4 || w.dims[0] != 3 || w.dims[1] != 3 || w.dims[2] != 16 || w.dims[3] != 8) return ASEP_OK;
+        for (int ky = 0; ky < 3; ++ky)
+            for (int src = 0; src < 2; ++src) pack_pair_split(w, 16, 8 * src, ky, u1);
+        int rc = upload_bf(uw, &m->d_r8ws_up_w);
+        if (rc) return rc;
+        m->owned.push_back(m->d_r8ws_up_w);
+        rc = upload_bf(u1, &m->d_r8ws_up_w1);
+        if (rc) return rc;
+        m->owned.push_back(m->d_r8ws_up_w1);
+    }
+    int rc = upload_bf(dw, &m->d_r8ws_down_w);
+    if (rc) return rc;
+    m->owned.push_back(m->d_r8ws_down_w);
+    return ASEP_OK;
 }
 
 int pack_res8b(asep_aru* m, const std::map<std::string, HostTensor>& blob) {
@@ -2386,6 +2563,7 @@ asep_aru* asep_aru_load(const void* weight_blob, size_t nbytes, const asep_aru_c
     if (const char* e = getenv("ASEP_BF_RES32")) m->use_res32 = atoi(e) != 0;
     if (const char* e = getenv("ASEP_BF_CONVR")) m->use_convr = atoi(e) != 0;
     if (const char* e = getenv("ASEP_SPLIT_DECONV")) m->use_deconvs = atoi(e) != 0;
+    if (const char* e = getenv("ASEP_SPLIT_WALK")) m->use_split_walk = atoi(e) != 0;
     if (const char* e = getenv("ASEP_BF_WALK")) { m->walk_mode = atoi(e); m->use_walk = m->walk_mode != 0; }
     if (const char* e = getenv("ASEP_LANES")) { m->num_lanes = std::max(1, std::min(4, atoi(e))); m->lanes_forced = true; }
     for (int l = 0; l < m->num_lanes; ++l) {
@@ -2447,6 +2625,7 @@ asep_aru* asep_aru_load(const void* weight_blob, size_t nbytes, const asep_aru_c
             rc = pack_conv(m.get(), blob, s + "/convR_" + std::to_string(r), "biases", false);
     }
     if (!rc && (!variant || m->fused8_var) && !m->bf16 && cfg->feat_root == 8 && cfg->res_depth == 3 && m->det_first.k == 3) rc = pack_res8(m.get(), blob);
+    if (!rc && m->split && !variant && m->d_r8_down_wr) rc = pack_res8ws(m.get(), blob);
     // (bf16 path, elu / leaky / 'U' graphs -- round 5: layer by layer on convb_kernel / deconvb_kernel with the activation in their general
     //  epilogues; the fused blocks below bake the ReLU into packed-bf16 maxima and serve the ReLU residual graphs)
     // (round 6: the elu / leaky RESIDUAL graphs take the GENERAL fused forms of the 8- and 16-channel levels -- res8b_tile / resb_tail_tile apply the

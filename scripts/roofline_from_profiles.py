@@ -105,6 +105,38 @@ def recompute(tagdir):
     return line, out, table
 
 
+# f32s level 0: the split-product strip walkers and the res8v_* launches over the frame units around them are ONE level-0 entry,
+# priced against the pipe the walkers run on -- six bf16 MFMA products per fp32 product: the dense bf16 peak / 6 (bench.py's pipe_of prices
+# res8ws_* against the fp32 MFMA peak until its own labels follow).  The res8v_* launches of a walker build are the frame units only.
+PEAK_BF16_MFMA_TFLOPS = 2500.0
+LEVEL0_SPLIT_WALK = ("res8ws_kernel<false>", "res8ws_kernel<true>", "res8v_down_kernel<0>", "res8v_up_kernel<0>")
+
+
+def level0_table(stats, steps, pages_per_step, flops_page=None):
+    """per-step / per-page level-0 time of a kernel_stats table (kernel_key -> calls, total_ns): the pair of res8ws walkers and the res8v
+    frame launches if the walkers ran, else the res8v blocks alone.  flops_page: useful level-0 FLOPs of a page (direct-convolution
+    count) -> the walkers' rate against mfma_bf16_split6."""
+    walk = any(k.startswith("res8ws_kernel") for k in stats)
+    rows = []
+    for k in LEVEL0_SPLIT_WALK:
+        if k in stats:
+            v = stats[k]
+            rows.append({"kernel": k, "calls": v["calls"], "us_per_step": round(v["total_ns"] / 1e3 / steps, 1),
+                         "us_per_page": round(v["total_ns"] / 1e3 / (steps * pages_per_step), 1),
+                         "role": ("walker" if k.startswith("res8ws") else ("frame units" if walk else "whole block"))})
+    total_page_us = sum(r["us_per_page"] for r in rows)
+    out = {"form": "split-product strip walkers + res8v frame" if walk else "res8v blocks", "kernels": rows,
+           "level0_us_per_page": round(total_page_us, 1)}
+    if walk and flops_page:
+        wk_s = sum(stats[k]["total_ns"] for k in LEVEL0_SPLIT_WALK[:2] if k in stats) / 1e9 / (steps * pages_per_step)
+        out["pipe"] = "mfma_bf16_split6"
+        out["peak_tflops"] = PEAK_BF16_MFMA_TFLOPS / 6.0
+        out["level0_tflops"] = flops_page / (total_page_us * 1e-6) / 1e12
+        out["level0_frac"] = out["level0_tflops"] / out["peak_tflops"]
+        out["walker_s_per_page"] = wk_s
+    return out
+
+
 def compare(line, rec, tol):
     r = block(line)
     pairs = {"avg_launch_us": r.get("avg_launch_us_in_situ") or r["avg_launch_us"],
@@ -134,6 +166,19 @@ def compare(line, rec, tol):
 
 
 def main(argv):
+    if argv[1] == "--level0":
+        # python scripts/roofline_from_profiles.py --level0 <kernel_stats.csv> <bench line .json>: the level-0 table of a traced bench run
+        stats = {}
+        for row in csv.DictReader(open(argv[2])):
+            if "asep::" in row["Name"]:
+                stats[kernel_key(row["Name"])] = {"calls": int(row["Calls"]), "total_ns": float(row["TotalDurationNs"])}
+        line = load_line(argv[3])
+        H, W = line["config"].get("height", 4500), line["config"].get("width", 3000)
+        # useful level-0 work of a page at its three scales: DOWN 9 * 8 + 27 * 64, UP 9 * 128 + 27 * 64 products per pixel
+        px = sum(-(-H // 2 ** s) * -(-W // 2 ** s) for s in range(3))
+        flops_page = 2.0 * px * ((9 * 8 + 27 * 64) + (9 * 128 + 27 * 64))
+        print(json.dumps(level0_table(stats, line["warmup"] + line["steps"], line["config"]["pages_per_step_per_gpu"], flops_page), indent=1))
+        return 0
     tagdir = argv[1].rstrip("/")
     tol = float(argv[argv.index("--tol") + 1]) if "--tol" in argv else 0.03
     line, rec, table = recompute(tagdir)
