@@ -389,6 +389,41 @@ int asep_textblock_neighbours(asep_post* p, int n_pages, const int32_t* page_off
  * or asep_textblock_neighbours (which = 1) call; -1 for another `which`. */
 double asep_textblock_last_kernel_us(int which);
 
+/* ---- article separation measure (eval_measure.py count_rel_hits / count_rel_hits_list, Python path) -------------------
+ * Batched over file pairs on the asep_post handle.  Truth and reco (hypothesis) polygons are NORMED baselines in the
+ * layout of asep_textblock_interline_dists (points as (x, y) int32 pairs, poly_off, boxes {x, y, w, h}); file k holds
+ * the truth polygons t_file_off[k] .. t_file_off[k+1]-1, the reco polygons r_file_off[k] .. and the reco articles
+ * art_file_off[k] ..  The reco polygons of a file are grouped by article: article a holds the reco polygons
+ * art_off[a] .. art_off[a+1]-1 (art_off [n_arts + 1], tiling each file); art_has_id[a] = 0 marks the group of lines
+ * without an article id.  tols [n_truth][n_tols]: the tolerances of each truth polygon (ticks, or one value per truth
+ * subset it is scored in); a value <= 0 yields 0.  dmax = floor(3 * largest tolerance), at most 4094; a truth polygon
+ * holds at most 4096 points.
+ *
+ * A (reco i, truth j) pair, or a (truth j, article a) record, is a candidate when the bounding boxes are at most dmax
+ * apart in x and in y; everything else has no distance <= dmax and contributes nothing.  Memory and output are bounded
+ * by the candidates.  Per candidate pair: count_rel_hits(reco i, truth j, tols[j]) -- sum_p h(d_p) / n_points over the
+ * points p of i with d_p the minimum L1 distance to the points of j.  Per record: count_rel_hits_list(truth j, polygons
+ * of article a, tols[j]).  Per truth polygon: the same against all reco polygons of the file (slot 0) and against those
+ * of the articles with an id (slot 1).  Every value is evaluated from the histogram of the integer distances over
+ * ascending distance, so it depends on the multiset of distances, the point count and the tolerance only.
+ *
+ * asep_measure_run computes everything and returns the number of candidate pairs (out_counts = {pairs, records});
+ * asep_measure_fetch, called next on the same thread and handle, copies the results to host arrays sized from those
+ * counts (any pointer may be null): pair_ij [pairs][2] = (i, j) ordered by i then j, pair_hits [pairs][n_tols],
+ * rec_ja [records][2] = (j, article index within the file) ordered by j then a, rec_hits [records][n_tols],
+ * truth_hits [n_truth][2][n_tols]; with want_hist the distance histograms behind them ([..][dmax + 2] uint32, last
+ * bin = distances above dmax).  Host pointers in and out; each call returns after its results have arrived. */
+long long asep_measure_run(asep_post* p, int n_files, const int32_t* t_file_off, const int32_t* r_file_off,
+                           const int32_t* t_poly_off, const int32_t* t_points, const int32_t* t_boxes,
+                           const int32_t* r_poly_off, const int32_t* r_points, const int32_t* r_boxes,
+                           const int32_t* art_file_off, const int32_t* art_off, const int32_t* art_has_id, int n_tols,
+                           const double* tols, int dmax, int want_hist, long long* out_counts);
+int asep_measure_fetch(asep_post* p, int32_t* pair_ij, double* pair_hits, int32_t* rec_ja, double* rec_hits,
+                       double* truth_hits, uint32_t* pair_hist, uint32_t* rec_hist, uint32_t* truth_hist);
+/* Device time in microseconds of the kernels of the calling thread's last asep_measure_run: which = 0 candidate count,
+ * 1 pair (precision) kernel, 2 recall kernel; -1 for another `which`. */
+double asep_measure_last_kernel_us(int which);
+
 #ifdef __cplusplus
 }
 #endif
