@@ -114,6 +114,8 @@ SIGNATURES = {
     "asep_measure_run": (C.c_longlong, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
     "asep_measure_fetch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "asep_measure_last_kernel_us": (C.c_double, [C.c_int]),
+    "asep_heading_grid_eval": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
+    "asep_heading_grid_last_kernel_us": (C.c_double, []),
 }
 
 _lib = None

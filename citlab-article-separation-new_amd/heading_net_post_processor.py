@@ -293,8 +293,13 @@ class HeadingNetPostProcessor(RegionNetPostProcessor):
         resize + gray per page, ONE batched heading-net call for the group with uint8 epilogue (:285-288; round 6: the pages share every layer's
         launches), then per page full-size gray + stroke-width distance transform (swt_dist_trafo.py:18-29) -- and return the tickets for
         :meth:`collect_page`.  Neither the net output nor the distance transform leaves HBM."""
-        import torch
         tickets = self._enqueue_net(images, lane, net=self.weight_dict['net'] > 0)
+        return self._enqueue_swt(tickets, lane)
+
+    def _enqueue_swt(self, tickets, lane=0):
+        """The per-page half of :meth:`enqueue_group` on uploaded tickets: full-size gray + stroke-width distance transform, then
+        the ``done`` event the measurements wait for."""
+        import torch
         with self._on_lane(lane) as (lib, ws, tdev, stream, sp):
             if getattr(self, "_side_stream", None) is None or self._side_stream.device != tdev:
                 self._side_stream = torch.cuda.Stream(tdev)
@@ -341,9 +346,10 @@ class HeadingNetPostProcessor(RegionNetPostProcessor):
             side = self._side_stream
             side.wait_event(t["done"])
             sp = C.c_void_p(side.cuda_stream)
-            crop = np.stack([bx[:, 0], bx[:, 1], bx[:, 2] + 2, bx[:, 3] + 2], axis=1) if len(sel) else np.zeros((0, 4), np.int64)
-            sws, hts = image_ops.swt_line_features(t["swt"], crop, device=dev, stream=sp, lane=1)
-            sw[sel], ht[sel] = sws, hts
+            if "swt" in t:                                          # (a net-only ticket of the evaluation grid has none)
+                crop = np.stack([bx[:, 0], bx[:, 1], bx[:, 2] + 2, bx[:, 3] + 2], axis=1) if len(sel) else np.zeros((0, 4), np.int64)
+                sws, hts = image_ops.swt_line_features(t["swt"], crop, device=dev, stream=sp, lane=1)
+                sw[sel], ht[sel] = sws, hts
             if "d_u8" in t and len(sel):
                 lo = (bx[:, :2] * sc).astype(np.int64)                  # rescale_points: int(p * sc), truncation towards zero
                 hi = (bx[:, 2:] * sc).astype(np.int64)

@@ -95,11 +95,12 @@ class RegionNetPostProcessor:
             stream = torch.cuda.current_stream(tdev)
             yield _lib.init_device(dev), ws, tdev, stream, C.c_void_p(stream.cuda_stream)
 
-    def _enqueue_net(self, images, lane=0, net=True, mask=False):
+    def _enqueue_net(self, images, lane=0, net=True, mask=False, reuse=None):
         """Queue the front end of a group of decoded pages of ANY sizes on ``lane``'s stream: per page the upload, resize + gray
         and the output buffers, then ONE batched net call for the group (asep_aru_forward_batch_dev2: the pages share every
         layer's launches) with the uint8 epilogue and, with ``mask``, the mask thresholded at ``self.threshold``.  ``net``
-        False queues the uploads only.  ``images`` have to stay valid until their ``uploaded`` events.
+        False queues the uploads only.  ``images`` have to stay valid until their ``uploaded`` events.  ``reuse``: tickets of an
+        earlier call for the same pages on the same lane, whose uploaded images are used instead of uploading them again.
         -> one ticket per page: "sc", "size" (h, w), "device", "uploaded", "d_img"; with the net also "d_gray", "d_out",
         "d_u8" (and "d_mask"), all kept alive by the ticket until the page is collected"""
         import torch
@@ -117,10 +118,15 @@ class RegionNetPostProcessor:
                 # engine's kernels in a shared hardware queue and made the host wait for them): ``image`` must stay valid until the
                 # page's upload has run -- DecodePool(hold=...) guarantees that for its slots, pageable arrays are staged by the runtime
                 # before the call returns
-                d_img = torch.empty((H, W, Cn), dtype=torch.uint8, device=tdev)
-                d_img.copy_(torch.from_numpy(image), non_blocking=True)
-                t = {"sc": sc, "size": (h, w), "device": tdev.index, "d_img": d_img, "uploaded": torch.cuda.Event()}
-                t["uploaded"].record(stream)
+                if reuse is None:
+                    d_img = torch.empty((H, W, Cn), dtype=torch.uint8, device=tdev)
+                    d_img.copy_(torch.from_numpy(image), non_blocking=True)
+                    t = {"sc": sc, "size": (h, w), "device": tdev.index, "d_img": d_img, "uploaded": torch.cuda.Event()}
+                    t["uploaded"].record(stream)
+                else:
+                    prev = reuse[len(tickets)]
+                    d_img = prev["d_img"]
+                    t = {"sc": sc, "size": (h, w), "device": tdev.index, "d_img": d_img, "uploaded": prev["uploaded"]}
                 if net:
                     t["d_gray"] = torch.empty((h, w), dtype=torch.float32, device=tdev)
                     _lib.check(lib.asep_prep_scale_gray_dev(ws, d_img.data_ptr(), H, W, Cn, float(sc), None,

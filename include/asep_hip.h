@@ -424,6 +424,26 @@ int asep_measure_fetch(asep_post* p, int32_t* pair_ij, double* pair_hits, int32_
  * 1 pair (precision) kernel, 2 recall kernel; -1 for another `which`. */
 double asep_measure_last_kernel_us(int which);
 
+/* ---- heading detection evaluation (heading_evaluation.py / heading_evaluation_grid_search.py) --------------------------
+ * Scores many settings of the heading fusion rule (heading_net_post_processor.py:110-195) at once on the asep_post
+ * handle.  Page k holds the lines line_off[k] .. line_off[k+1]-1 and the text regions reg_off[k] .. reg_off[k+1]-1;
+ * region r lists the lines reg_lines[reg_line_off[r] .. reg_line_off[r+1]-1] as indices within its page.  Per line the
+ * normalised confidences sw_conf, th_conf, net_conf (doubles) and line_tagged (may be null: a line that already carries
+ * the heading tag counts as a heading line under every setting); per page use_swt (0: the confidence is net_conf); per
+ * region gt_heading (the ground truth label).  settings [n_settings][9] are numbers of tenths in 0..10: threshold,
+ * net_w, sw_w, th_w, net_thresh, sw_thresh, th_thresh, sw_th_thresh, text_line_percentage, each turned into k / 10.0.
+ * A line is a heading when (conf > threshold), conf = 1.0 if sw >= sw_thresh, th >= th_thresh, (sw + th) / 2 >=
+ * sw_th_thresh or net >= net_thresh, else net_w * net + sw_w * sw + th_w * th; with net_w = 0 every net confidence is 0.
+ * A region is a heading when it has lines and (double)headings / lines >= text_line_percentage.
+ * out_counts [n_settings][n_pages][4] = TP, FP, FN, TN of the region labels.  Bad offsets, indices or settings return a
+ * negative code (asep_last_error) and launch nothing.  Host pointers in and out; returns after the counts have arrived. */
+int asep_heading_grid_eval(asep_post* p, int n_pages, const int32_t* line_off, const double* sw_conf, const double* th_conf,
+                           const double* net_conf, const uint8_t* line_tagged, const uint8_t* use_swt, const int32_t* reg_off,
+                           const int32_t* reg_line_off, const int32_t* reg_lines, const uint8_t* gt_heading, int n_settings,
+                           const int32_t* settings, int32_t* out_counts);
+/* Device time in microseconds of the kernel of the calling thread's last asep_heading_grid_eval (0 if nothing ran). */
+double asep_heading_grid_last_kernel_us(void);
+
 #ifdef __cplusplus
 }
 #endif
