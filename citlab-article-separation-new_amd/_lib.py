@@ -116,6 +116,16 @@ SIGNATURES = {
     "asep_measure_last_kernel_us": (C.c_double, [C.c_int]),
     "asep_heading_grid_eval": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
     "asep_heading_grid_last_kernel_us": (C.c_double, []),
+    "asep_releval_create": (_P, []),
+    "asep_releval_free": (None, [_P]),
+    "asep_releval_reset": (C.c_int, [_P, _P]),
+    "asep_releval_reserve": (C.c_int, [_P, C.c_longlong, _P]),
+    "asep_releval_count": (C.c_longlong, [_P]),
+    "asep_releval_append_dev": (C.c_int, [_P, _P, C.c_int, C.c_longlong, _P, C.c_int, C.c_int, _P]),
+    "asep_releval_append_host": (C.c_int, [_P, _P, _P, C.c_longlong, _P]),
+    "asep_releval_finish": (C.c_int, [_P, _P, C.POINTER(C.c_longlong)]),
+    "asep_releval_fetch": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "asep_releval_stage_us": (C.c_double, [_P, C.c_int]),
 }
 
 _lib = None

@@ -113,9 +113,13 @@ class InputGNN(object):
             return mask_features(feats, mask)
         return feats
 
-    def feed_from_json(self, json_path, image=None):
-        """-> feed dict keyed by the exported placeholder names (batch size 1), ready for ``GnnSession.run``."""
+    def feed_from_json(self, json_path, image=None, targets=None):
+        """-> feed dict keyed by the exported placeholder names (batch size 1), ready for ``GnnSession.run``.  ``targets`` (a dict)
+        receives the json's ``gt_relations`` [G, 3] and ``gt_num_relations``: what an evaluation scores the output against."""
         d = get_input_and_target_from_json(json_path)
+        if targets is not None:
+            targets["gt_relations"] = d["gt_relations"].reshape(-1, 3)
+            targets["gt_num_relations"] = d["gt_num_relations"]
         n = int(d["num_nodes"])
         feed = {
             "num_nodes:0": np.array([n], np.int32),

@@ -79,6 +79,13 @@ def _prepare_page(input_fn, flags, json_path):
     if not os.path.isfile(json_path):
         logging.warning(f"No json file found to given pageXML {page_path}. Skipping.")
         return None
+    feed, n = _prepare_feed(input_fn, flags, json_path)
+    return page_path, feed, n
+
+
+def _prepare_feed(input_fn, flags, json_path, targets=None):
+    """the feed dict of one graph json (+ its scan for a graph exported with image_input) and its number of nodes; ``targets``
+    (a dict) receives the json's ground truth relations (lav_rel)"""
     image = None
     if flags.image_input:
         from PIL import Image
@@ -91,9 +98,9 @@ def _prepare_page(input_fn, flags, json_path):
         if image is None or image.ndim != 2:
             with Image.open(img_path) as im:
                 image = np.asarray(im.convert("L"))                      # uint8; widened after the resize's gathers
-    feed = input_fn.feed_from_json(json_path, image)
+    feed = input_fn.feed_from_json(json_path, image, targets)
     n = feed["node_features:0"].shape[1] if "node_features:0" in feed else int(feed["num_nodes:0"][0])
-    return page_path, feed, n
+    return feed, n
 
 
 def _finish_page(tb, flags, output, n, page_path):

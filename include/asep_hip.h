@@ -444,6 +444,43 @@ int asep_heading_grid_eval(asep_post* p, int n_pages, const int32_t* line_off, c
 /* Device time in microseconds of the kernel of the calling thread's last asep_heading_grid_eval (0 if nothing ran). */
 double asep_heading_grid_last_kernel_us(void);
 
+/* ---- relation net evaluation (article_separation/gnn/trainer/lav_rel.py) ----------------------------------------------
+ * An accumulator of (score, label) pairs in HBM and sklearn's _binary_clf_curve over them: what precision_recall_curve,
+ * roc_auc_score and accuracy_score of lav_rel.py:190-229 are computed from, without a probability leaving the device.
+ * A pair is one 32-bit key (float_bits(p) << 1) | label; asep_releval_finish sorts the keys (radix sort, 8 bits x 4 stable
+ * passes of three launches each: digit histograms per tile, a scan of the digit x tile table, the scatter) and writes, per
+ * distinct score in DESCENDING order, the score (thresholds), tps and fps = the number of pairs of label 1 / label 0 whose
+ * score is >= it.  All of it is integer work: the results are exact and do not depend on the launch geometry.
+ * One accumulator holds fewer than 2^31 pairs (every count is a 32-bit number on the device); more is refused with
+ * ASEP_ERR_UNSUPPORTED.  The calls of one accumulator go to one stream, or the caller orders them. */
+typedef struct asep_releval asep_releval;
+asep_releval* asep_releval_create(void);
+void asep_releval_free(asep_releval* h);
+/* forget the pairs and the counters; buffers are kept */
+int asep_releval_reset(asep_releval* h, void* stream);
+/* room for total_pairs pairs.  Optional: the key buffer doubles when it is full (that synchronises `stream` once). */
+int asep_releval_reserve(asep_releval* h, long long total_pairs, void* stream);
+long long asep_releval_count(const asep_releval* h);
+/* One page behind its forward, queued on `stream`, no host synchronisation (unless the buffer has to grow): d_probs
+ * [R, num_classes] is the net's output, the LAST class column is the score (lav_rel.py:183); R must be N * N, pair (i, j) at
+ * row i * N + j (input_dataset.py:444-457).  d_gt_relations [G, 3]: a row (., i, j) gives pair (i, j) label 1, duplicates are
+ * harmless.  The call also counts what the host refuses at the end: scores that are NaN, negative or above 1, and rows of
+ * d_gt_relations that name a node outside 0..N-1; and the positives and the pairs with (p > 0.5) == label. */
+int asep_releval_append_dev(asep_releval* h, const float* d_probs, int num_classes, long long R, const int32_t* d_gt_relations,
+                            int G, int N, void* stream);
+/* The same from host arrays: probs [n] are the scores, labels [n] their labels (0 / non-zero).  Returns after the copy. */
+int asep_releval_append_host(asep_releval* h, const float* probs, const uint8_t* labels, long long n, void* stream);
+/* Sort and curve; *out_thresholds = T, the number of distinct scores (0 for an empty accumulator).  Synchronises `stream`. */
+int asep_releval_finish(asep_releval* h, void* stream, long long* out_thresholds);
+/* After finish: thresholds [T] float32, tps [T], fps [T] int64 (any may be null) and counters [8] = {pairs, refused scores,
+ * positives counted by the appends, pairs with (p > 0.5) == label, refused ground truth rows,
+ * A2 = sum_k (fps_k - fps_{k-1}) (tps_k + tps_{k-1}) with tps_{-1} = fps_{-1} = 0, T, positives counted in the sorted keys}.
+ * AUC-ROC = A2 / (2 P (pairs - P)): one division of exact integers. */
+int asep_releval_fetch(asep_releval* h, void* stream, float* thresholds, int64_t* tps, int64_t* fps, uint64_t* counters);
+/* Device time in microseconds of stage `which` of the last finish: 3 * pass + {0 histogram, 1 scan, 2 scatter} for the
+ * passes 0..3, 12 / 13 / 14 = curve count / scan / write, 15 = A2; -1 for another `which`. */
+double asep_releval_stage_us(const asep_releval* h, int which);
+
 #ifdef __cplusplus
 }
 #endif
