@@ -11,6 +11,7 @@
 #include "bf16_kernels.h"
 #include "res8w_kernels.h"
 #include "res8ws_kernels.h"
+#include "level0_plan.h"
 #include "convr_kernels.h"
 #include "split_kernels.h"
 #include "asep_common.h"
@@ -384,6 +385,13 @@ int pack_direct(asep_aru* m, const std::map<std::string, HostTensor>& blob, cons
 
 struct TileDims { int tx, ty, begin; };
 
+// XCD-aware order of the persistent fused kernels' tiles.  Workgroups are dealt round-robin to the 8 XCDs (block b
+// runs on XCD b % 8, each with its own 4 MB L2).  The tiles of every problem are first put into "super-tile" order
+// (groups of 4 x 8 tiles, groups walked down a column of groups first), the concatenated list is cut into 8 equal
+// chunks, and the k-th unit of work (k = block + i * grid) takes the (k / 8)-th tile of chunk k % 8: the 32 blocks of
+// an XCD work on spatially adjacent tiles at the same time, and on the rows just below right after, so the 8-row /
+// 14-column halo overlap of neighbouring tiles is served by that XCD's L2 instead of being fetched again.
+//
 // work unit -> tile table of the PERSISTENT kernels (res8v_*, res32_tail_kernel: resident blocks walk the units with a grid stride) for the
 // problems' tile grids `probs` (tile numbers begin + ty * tx + x, `total` tiles in all): the tiles of every problem in 4 x 8 super-tile
 // order, cut into eight chunks, unit k = the (k / 8)-th tile of chunk k mod 8 (block b runs on XCD b mod 8).  nullptr on failure: identity.
@@ -946,44 +954,28 @@ int pack_res8(asep_aru* m, const std::map<std::string, HostTensor>& blob) {
     return ASEP_OK;
 }
 
-// fused level-0 down block: images -> d0 (and maxpool2(d0) if want_pool)
-// XCD-aware order of the persistent fused kernels' tiles.  Workgroups are dealt round-robin to the 8 XCDs (block b
-// runs on XCD b % 8, each with its own 4 MB L2).  The tiles of every problem are first put into "super-tile" order
-// (groups of 4 x 8 tiles, groups walked down a column of groups first), the concatenated list is cut into 8 equal
-// chunks, and the k-th unit of work (k = block + i * grid) takes the (k / 8)-th tile of chunk k % 8: the 32 blocks of
-// an XCD work on spatially adjacent tiles at the same time, and on the rows just below right after, so the 8-row /
-// 14-column halo overlap of neighbouring tiles is served by that XCD's L2 instead of being fetched again.
-// the vector-ALU level-0 kernels address their tensors with 32-bit element offsets (< 2^28 pixels per tensor)
+// the profiler's layer text of a level-0 block over the pages `l`
+std::string res8_what(bool up, const TL& l) {
+    return (up ? "unet_up_0 (conv1[16->8]+3xconvR+add) " : "unet_down_0 (conv1+3xconvR+add+pool) ") + dims_of(l);
+}
+
+// the vector-ALU level-0 kernels address their tensors with 32-bit element offsets: below 2^28 pixels per tensor (2^31 elements at 8 channels)
 bool r8v_fits(const TL& l) {
     for (const Tensor& t : l)
         if ((size_t)t.H * t.W >= ((size_t)1 << 28)) return false;
     return true;
 }
 
-// f32s level 0 on the split-product strip walkers (res8ws_kernels.h): pages with room for four strips and two 16-row bands (and 32-bit
-// element offsets for the vector-ALU frame), ReLU graph only
-bool r8ws_fits(const Tensor& t) {
-    return (t.W - 4 - R8W_X0) / R8W_TW >= 4 && t.H - 4 - R8W_Y0 >= 32 && (size_t)t.H * t.W < ((size_t)1 << 28);
-}
+// f32s level 0 on the split-product strip walkers (res8ws_kernels.h): pages with room for the walker's region (level0_plan.h), ReLU graph only
+bool r8ws_fits(const Tensor& t) { return walk_region(t.H, t.W).fits; }
 bool r8ws_on(asep_aru* m) { return m->split && m->use_split_walk && m->r8_valu && m->cfg.activation == 0 && m->d_r8ws_down_w; }
 // the work units of a res8v launch over `a` (unit height R8_OH * R8_NP) that the strip walkers do not cover: for a page in `walk`, the units
-// that touch the frame around its walker region (res8ws_kernels.h), for the other pages all units.  Cached device list; nullptr on failure.
+// that touch the frame around its walker region (level0_plan.h), for the other pages all units.  Cached device list; nullptr on failure.
 const int32_t* r8ws_frame_units(asep_aru* m, const Res8Args& a, const std::vector<bool>& walk, int* count) {
     std::string key = "f";
     for (int i = 0; i < a.nprob; ++i) key += ":" + std::to_string(a.p[i].H) + "x" + std::to_string(a.p[i].W) + (walk[i] ? "w" : "t");
     std::vector<int32_t> units;
-    constexpr int UH = R8_OH * R8_NP;
-    for (int i = 0; i < a.nprob; ++i) {
-        const Res8Prob& p = a.p[i];
-        const int ty = cdiv(p.H, UH), tx = p.tiles_x;
-        const int xr = R8W_X0 + R8W_TW * ((p.W - 4 - R8W_X0) / R8W_TW), ye = R8W_Y0 + 2 * ((p.H - 4 - R8W_Y0) / 2);
-        for (int y = 0; y < ty; ++y)
-            for (int x = 0; x < tx; ++x) {
-                const int ux0 = x * R8_OW, ux1 = std::min(ux0 + R8_OW, p.W), uy0 = y * UH, uy1 = std::min(uy0 + UH, p.H);
-                const bool frame = !walk[i] || ux0 < R8W_X0 || ux1 > xr || uy0 < R8W_Y0 || uy1 > ye;
-                if (frame) units.push_back(p.tile_begin + y * tx + x);
-            }
-    }
+    for (int i = 0; i < a.nprob; ++i) frame_units(a.p[i].H, a.p[i].W, a.p[i].tiles_x, a.p[i].tile_begin, walk[i], R8_OW, R8_OH * R8_NP, &units);
     *count = (int)units.size();
     auto it = m->sched_cache.find(key);
     if (it != m->sched_cache.end()) return it->second;
@@ -1009,23 +1001,20 @@ void run_res8ws(asep_aru* m, bool up, const Res8Args& a, const std::vector<bool>
         else { p.img = q.img; p.stats = q.stats; p.pool = q.pool; }
         p.out = q.out;
         p.H = q.H; p.W = q.W;
-        p.n_strips = (p.W - 4 - R8W_X0) / R8W_TW;
-        p.y_end = R8W_Y0 + 2 * ((p.H - 4 - R8W_Y0) / 2);
-        strip_rows += (long)p.n_strips * (p.y_end - R8W_Y0);
-        const double px = (double)p.n_strips * R8W_TW * (p.y_end - R8W_Y0);
-        flops += 2.0 * px * (9.0 * (up ? 16 : 1) * 8 + 3 * 9.0 * 64);
-        bytes += px * ((up ? 64.0 : 4.0) + 32.0 + (p.pool ? 8.0 : 0.0));
+        const WalkRegion r = walk_region(p.H, p.W);
+        p.n_strips = r.n_strips;
+        p.y_end = r.y_end;
+        strip_rows += (long)r.n_strips * r.rows();
+        flops += 2.0 * r.pixels() * (9.0 * (up ? 16 : 1) * 8 + 3 * 9.0 * 64);
+        bytes += r.pixels() * ((up ? 64.0 : 4.0) + 32.0 + (p.pool ? 8.0 : 0.0));
     }
     if (!n) return;
-    // rows of an item: ~6 items per resident wave of the chip (four waves per CU), so that the block dispatch balances the tail
-    const long slots = 4L * m->num_cus;
-    int band = (int)std::min<long>(256, std::max<long>(32, strip_rows / (6 * slots)));
-    band = (band + 1) & ~1;
+    const int band = walk_band(strip_rows, m->num_cus, 4);   // (four waves per CU)
     for (int i = 0; i < n; ++i) {
         Res8WSProb& p = wa.p[i];
         p.band = band;
         p.tile_begin = items;
-        items += p.n_strips * cdiv(p.y_end - R8W_Y0, band);
+        items += walk_region(p.H, p.W).items(band);
     }
     wa.nprob = n;
     if (up) { wa.b1 = m->d_r8_up_b1; wa.w1s = (const u32x4*)m->d_r8ws_up_w1; wa.ws = (const u32x4*)m->d_r8ws_up_w; wa.bias = m->d_r8_up_br; }
@@ -1038,101 +1027,58 @@ void run_res8ws(asep_aru* m, bool up, const Res8Args& a, const std::vector<bool>
     else hipLaunchKernelGGL(res8ws_kernel<false>, dim3(units), dim3(64), 0, m->stream, wa);
 }
 
-void run_res8_down(asep_aru* m, const TL& imgs, const std::vector<const float*>& stats, bool want_pool, TL* d_out, TL* pool_out) {
-    for (const Tensor& t : imgs) {
+// the kernel of a fused fp32 level-0 block with rocprofv3's name for it (template arguments spelled out): the vector-ALU form with the graph's
+// activation (0 ReLU, 1 elu, 2 leaky), or the MFMA form (ReLU only)
+struct Res8Kernel { void (*fn)(const Res8Args); const char* name; };
+Res8Kernel res8_kernel(bool up, bool valu, int actv) {
+    static const Res8Kernel k[2][4] = {
+        {{res8v_down_kernel<0>, "res8v_down_kernel<0>"}, {res8v_down_kernel<1>, "res8v_down_kernel<1>"}, {res8v_down_kernel<2>, "res8v_down_kernel<2>"},
+         {res8_down_kernel<false>, "res8_down_kernel<false>"}},
+        {{res8v_up_kernel<0>, "res8v_up_kernel<0>"}, {res8v_up_kernel<1>, "res8v_up_kernel<1>"}, {res8v_up_kernel<2>, "res8v_up_kernel<2>"},
+         {res8_up_kernel<false>, "res8_up_kernel<false>"}}};
+    return k[up][valu ? actv : 3];
+}
+
+// fused fp32 level-0 block.  down: images in0 -> d0 (and maxpool2(d0) if want_pool); up: [skip in0, deconv *in1] -> block output
+void run_res8(asep_aru* m, bool up, const TL& in0, const TL* in1, const std::vector<const float*>& stats, bool want_pool, TL* d_out, TL* pool_out) {
+    for (const Tensor& t : in0) {
         d_out->push_back(new_tensor(m, t.H, t.W, 8));
         if (want_pool) pool_out->push_back(new_tensor(m, cdiv(t.H, 2), cdiv(t.W, 2), 8));
     }
-    for (size_t b0 = 0; b0 < imgs.size(); b0 += MAXP) {
-        const size_t b1 = std::min(imgs.size(), b0 + MAXP);
+    const size_t lds = up ? R8_UP_LDS : R8_DOWN_LDS;
+    const char* layer = up ? "unet_up_0" : "unet_down_0";
+    for (size_t b0 = 0; b0 < in0.size(); b0 += MAXP) {
+        const size_t b1 = std::min(in0.size(), b0 + MAXP);
         Res8Args a{};
         int tiles = 0;
         double flops = 0, bytes = 0;
         for (size_t i = b0; i < b1; ++i) {
-            bytes += tbytes(imgs[i]) + tbytes((*d_out)[i]) + (want_pool ? tbytes((*pool_out)[i]) : 0.0);
+            bytes += tbytes(in0[i]) + (up ? tbytes((*in1)[i]) : 0.0) + tbytes((*d_out)[i]) + (want_pool ? tbytes((*pool_out)[i]) : 0.0);
             Res8Prob& p = a.p[i - b0];
-            p.img = imgs[i].p; p.in1 = nullptr; p.stats = stats.empty() ? nullptr : stats[i];
+            p.img = in0[i].p; p.in1 = up ? (*in1)[i].p : nullptr; p.stats = stats.empty() ? nullptr : stats[i];
             p.out = (*d_out)[i].p; p.pool = want_pool ? (*pool_out)[i].p : nullptr;
-            p.H = imgs[i].H; p.W = imgs[i].W;
-            p.tiles_x = cdiv(imgs[i].W, R8_OW);
+            p.H = in0[i].H; p.W = in0[i].W;
+            p.tiles_x = cdiv(in0[i].W, R8_OW);
             p.tile_begin = tiles;
-            tiles += p.tiles_x * cdiv(imgs[i].H, R8_OH * R8_NP);
-            flops += 2.0 * imgs[i].H * imgs[i].W * (9.0 * 8 + 3 * 9.0 * 64);
+            tiles += p.tiles_x * cdiv(in0[i].H, R8_OH * R8_NP);
+            flops += 2.0 * in0[i].H * in0[i].W * (9.0 * (up ? 16 : 1) * 8 + 3 * 9.0 * 64);
         }
         a.nprob = (int)(b1 - b0);
         a.total_tiles = tiles;
-        a.w1 = m->det_first.d_w; a.b1 = m->det_first.d_b;
-        bool valu = m->r8_valu;                  // vector-ALU kernels (32-bit element offsets: < 2^29 pixels per tensor)
-        for (size_t i = b0; i < b1; ++i) valu = valu && (size_t)imgs[i].H * imgs[i].W < ((size_t)1 << 28);
-        a.wr = (const f32x4*)(valu ? m->d_r8v_down_wr : m->d_r8_down_wr); a.br = m->d_r8_down_br;
-        TL sub(imgs.begin() + b0, imgs.begin() + b1);
-        const std::string pname = valu ? std::string("res8v_down_kernel<0>") : std::string("res8_down_kernel<false>");   // (rocprofv3's names: template arguments spelled out)
-        a.sched = tile_schedule(m, a, std::min(tiles, m->num_cus), R8_OH * R8_NP);
-        if (valu && r8ws_on(m)) {
-            // the frame units on res8v_down_kernel, then the split-product walkers over the rest of the pages that have room for them
-            std::vector<bool> walk(a.nprob);
-            bool any = false;
-            for (int i = 0; i < a.nprob; ++i) { walk[i] = r8ws_fits(imgs[b0 + i]); any = any || walk[i]; }
-            if (any) {
-                int nu = 0;
-                Res8Args f = a;
-                f.sched = r8ws_frame_units(m, a, walk, &nu);
-                if (!f.sched) { set_error("level-0 frame schedule: device allocation failed"); throw ArgError(); }
-                f.total_tiles = nu;
-                {
-                    const double share = (double)nu / tiles;          // (the frame units' share of the launch's work units)
-                    ProfScope ps(m, pname, flops * share, "unet_down_0 frame " + dims_of(sub));
-                    ps.bytes = bytes * share;
-                    hipLaunchKernelGGL(res8v_down_kernel<0>, dim3(std::min(nu, m->num_cus)), dim3(R8_THREADS), R8_DOWN_LDS, m->stream, f);
-                }
-                run_res8ws(m, false, a, walk, "unet_down_0 (conv1+3xconvR+add+pool) " + dims_of(sub));
-                continue;
-            }
-        }
-        ProfScope ps(m, pname, flops, "unet_down_0 (conv1+3xconvR+add+pool) " + dims_of(sub));
-        ps.bytes = bytes;
-        const dim3 gd(std::min(tiles, m->num_cus));
+        TL sub(in0.begin() + b0, in0.begin() + b1);
+        const bool valu = m->r8_valu && r8v_fits(sub);       // vector-ALU kernels, with weights in their own order
+        if (up) { a.w1 = valu ? m->d_r8v_up_w1 : m->d_r8_up_w1; a.b1 = m->d_r8_up_b1; }
+        else { a.w1 = m->det_first.d_w; a.b1 = m->det_first.d_b; }
+        a.wr = (const f32x4*)(up ? (valu ? m->d_r8v_up_wr : m->d_r8_up_wr) : (valu ? m->d_r8v_down_wr : m->d_r8_down_wr));
+        a.br = up ? m->d_r8_up_br : m->d_r8_down_br;
         const int actv = m->cfg.activation;                  // graph variants (fused8_var): the same block with elu / leaky (vector-ALU form only)
-        if (actv && !valu) { set_error("level-0 block of an elu / leaky graph: image too large for the vector-ALU kernel"); throw ArgError(); }
-        if (valu && actv == 1) { ps.set_name("res8v_down_kernel<1>"); hipLaunchKernelGGL(res8v_down_kernel<1>, gd, dim3(R8_THREADS), R8_DOWN_LDS, m->stream, a); }
-        else if (valu && actv == 2) { ps.set_name("res8v_down_kernel<2>"); hipLaunchKernelGGL(res8v_down_kernel<2>, gd, dim3(R8_THREADS), R8_DOWN_LDS, m->stream, a); }
-        else if (valu) hipLaunchKernelGGL(res8v_down_kernel<0>, gd, dim3(R8_THREADS), R8_DOWN_LDS, m->stream, a);
-        else hipLaunchKernelGGL(res8_down_kernel<false>, gd, dim3(R8_THREADS), R8_DOWN_LDS, m->stream, a);
-    }
-}
-
-// fused level-0 up block: [skip, deconv] -> block output
-TL run_res8_up(asep_aru* m, const TL& skip, const TL& v) {
-    TL out;
-    for (const Tensor& t : skip) out.push_back(new_tensor(m, t.H, t.W, 8));
-    for (size_t b0 = 0; b0 < skip.size(); b0 += MAXP) {
-        const size_t b1 = std::min(skip.size(), b0 + MAXP);
-        Res8Args a{};
-        int tiles = 0;
-        double flops = 0, bytes = 0;
-        for (size_t i = b0; i < b1; ++i) {
-            bytes += tbytes(skip[i]) + tbytes(v[i]) + tbytes(out[i]);
-            Res8Prob& p = a.p[i - b0];
-            p.img = skip[i].p; p.in1 = v[i].p; p.stats = nullptr; p.out = out[i].p; p.pool = nullptr;
-            p.H = skip[i].H; p.W = skip[i].W;
-            p.tiles_x = cdiv(skip[i].W, R8_OW);
-            p.tile_begin = tiles;
-            tiles += p.tiles_x * cdiv(skip[i].H, R8_OH * R8_NP);
-            flops += 2.0 * skip[i].H * skip[i].W * (9.0 * 16 * 8 + 3 * 9.0 * 64);
-        }
-        a.nprob = (int)(b1 - b0);
-        a.total_tiles = tiles;
-        bool valu = m->r8_valu;                  // vector-ALU kernels (32-bit element offsets: < 2^29 pixels per tensor)
-        for (size_t i = b0; i < b1; ++i) valu = valu && (size_t)skip[i].H * skip[i].W < ((size_t)1 << 28);
-        a.w1 = valu ? m->d_r8v_up_w1 : m->d_r8_up_w1; a.b1 = m->d_r8_up_b1;
-        a.wr = (const f32x4*)(valu ? m->d_r8v_up_wr : m->d_r8_up_wr); a.br = m->d_r8_up_br;
-        TL sub(skip.begin() + b0, skip.begin() + b1);
-        const std::string pname = valu ? std::string("res8v_up_kernel<0>") : std::string("res8_up_kernel<false>");
+        const Res8Kernel k = res8_kernel(up, valu, actv);
         a.sched = tile_schedule(m, a, std::min(tiles, m->num_cus), R8_OH * R8_NP);
-        if (valu && r8ws_on(m) && m->d_r8ws_up_w1) {
+        if (valu && r8ws_on(m) && (!up || m->d_r8ws_up_w1)) {
+            // the frame units on the res8v kernel, then the split-product walkers over the rest of the pages that have room for them
             std::vector<bool> walk(a.nprob);
             bool any = false;
-            for (int i = 0; i < a.nprob; ++i) { walk[i] = r8ws_fits(skip[b0 + i]); any = any || walk[i]; }
+            for (int i = 0; i < a.nprob; ++i) { walk[i] = r8ws_fits(sub[i]); any = any || walk[i]; }
             if (any) {
                 int nu = 0;
                 Res8Args f = a;
@@ -1141,25 +1087,19 @@ TL run_res8_up(asep_aru* m, const TL& skip, const TL& v) {
                 f.total_tiles = nu;
                 {
                     const double share = (double)nu / tiles;          // (the frame units' share of the launch's work units)
-                    ProfScope ps(m, pname, flops * share, "unet_up_0 frame " + dims_of(sub));
+                    ProfScope ps(m, k.name, flops * share, std::string(layer) + " frame " + dims_of(sub));
                     ps.bytes = bytes * share;
-                    hipLaunchKernelGGL(res8v_up_kernel<0>, dim3(std::min(nu, m->num_cus)), dim3(R8_THREADS), R8_UP_LDS, m->stream, f);
+                    hipLaunchKernelGGL(k.fn, dim3(std::min(nu, m->num_cus)), dim3(R8_THREADS), lds, m->stream, f);
                 }
-                run_res8ws(m, true, a, walk, "unet_up_0 (conv1[16->8]+3xconvR+add) " + dims_of(sub));
+                run_res8ws(m, up, a, walk, res8_what(up, sub));
                 continue;
             }
         }
-        ProfScope ps(m, pname, flops, "unet_up_0 (conv1[16->8]+3xconvR+add) " + dims_of(sub));
+        ProfScope ps(m, k.name, flops, res8_what(up, sub));
         ps.bytes = bytes;
-        const dim3 grid(std::min(tiles, m->num_cus));
-        const int actv = m->cfg.activation;
         if (actv && !valu) { set_error("level-0 block of an elu / leaky graph: image too large for the vector-ALU kernel"); throw ArgError(); }
-        if (valu && actv == 1) { ps.set_name("res8v_up_kernel<1>"); hipLaunchKernelGGL(res8v_up_kernel<1>, grid, dim3(R8_THREADS), R8_UP_LDS, m->stream, a); }
-        else if (valu && actv == 2) { ps.set_name("res8v_up_kernel<2>"); hipLaunchKernelGGL(res8v_up_kernel<2>, grid, dim3(R8_THREADS), R8_UP_LDS, m->stream, a); }
-        else if (valu) hipLaunchKernelGGL(res8v_up_kernel<0>, grid, dim3(R8_THREADS), R8_UP_LDS, m->stream, a);
-        else hipLaunchKernelGGL(res8_up_kernel<false>, grid, dim3(R8_THREADS), R8_UP_LDS, m->stream, a);
+        hipLaunchKernelGGL(k.fn, dim3(std::min(tiles, m->num_cus)), dim3(R8_THREADS), lds, m->stream, a);
     }
-    return out;
 }
 
 // ================================================================================================
@@ -1543,19 +1483,17 @@ void run_res8w(asep_aru* m, bool up, const TL& in0, const TL* dec, const std::ve
             else { p.img = in0[i].p; p.stats = stats.empty() ? nullptr : stats[i]; p.pool = pools ? (*pools)[i].bp() : nullptr; }
             p.out = outs[i].bp();
             p.H = in0[i].H; p.W = in0[i].W;
-            p.n_strips = (p.W - 4 - R8W_X0) / R8W_TW;
-            p.y_end = R8W_Y0 + 2 * ((p.H - 4 - R8W_Y0) / 2);
-            strip_rows += (long)p.n_strips * (p.y_end - R8W_Y0);
+            const WalkRegion r = walk_region(p.H, p.W);
+            p.n_strips = r.n_strips;
+            p.y_end = r.y_end;
+            strip_rows += (long)r.n_strips * r.rows();
             bytes += tbytes(in0[i]) + (up ? tbytes((*dec)[i]) : 0.0) + tbytes(outs[i]) + (pools ? tbytes((*pools)[i]) : 0.0);
             flops += 2.0 * p.H * p.W * (9.0 * (up ? 16 : 1) * 8 + 3 * 9.0 * 64);
-            wshare += (double)p.n_strips * R8W_TW * (p.y_end - R8W_Y0);
+            wshare += r.pixels();
         }
-        // rows of an item: ~6 items per resident wave of the chip (eight waves per CU), so that the hardware's block dispatch balances the tail;
-        // an item's head and tail cost about fifteen iterations of the general form (profiles/r6_walk: 64 / 128 / 256 / 400 / 800 rows per item =
-        // 952 / 798 / 747 / 752 / 739 us per 4-page launch)
-        const long slots = 8L * m->num_cus;
-        int band = (int)std::min<long>(256, std::max<long>(32, strip_rows / (6 * slots)));
-        band = (band + 1) & ~1;
+        // rows of an item (eight waves per CU): an item's head and tail cost about fifteen iterations of the general form (profiles/r6_walk:
+        // 64 / 128 / 256 / 400 / 800 rows per item = 952 / 798 / 747 / 752 / 739 us per 4-page launch)
+        int band = walk_band(strip_rows, m->num_cus, 8);
 #ifdef ASEP_ABLATION
         if (const char* e = getenv("ASEP_BF_WALK_BAND")) band = std::max(2, atoi(e) & ~1);      // (measurement knob of ablation builds)
 #endif
@@ -1564,13 +1502,14 @@ void run_res8w(asep_aru* m, bool up, const TL& in0, const TL* dec, const std::ve
             Res8WProb& p = wa.p[i - b0];
             p.band = band;
             p.tile_begin = items;
-            items += p.n_strips * cdiv(p.y_end - R8W_Y0, band);
+            items += walk_region(p.H, p.W).items(band);
             Res8BProb& q = ba.b.p[i - b0];
             q.skip = p.skip; q.dec = p.dec; q.img = p.img; q.stats = p.stats; q.out = p.out; q.pool = p.pool; q.H = p.H; q.W = p.W;
             q.tile_begin = btiles;
-            ba.nbx[i - b0] = cdiv(p.W, 32); ba.nby[i - b0] = cdiv(p.y_end - R8W_Y0, 16);
-            ba.y_end[i - b0] = p.y_end; ba.xr[i - b0] = R8W_X0 + R8W_TW * p.n_strips;
-            btiles += 2 * ba.nbx[i - b0] + 2 * ba.nby[i - b0];
+            const BorderPlan bp = border_plan(p.H, p.W);
+            ba.nbx[i - b0] = bp.nbx; ba.nby[i - b0] = bp.nby;
+            ba.y_end[i - b0] = bp.y_end; ba.xr[i - b0] = bp.xr;
+            btiles += bp.tiles();
         }
         wa.nprob = ba.b.nprob = (int)(b1 - b0);
         if (up) {
@@ -1581,7 +1520,7 @@ void run_res8w(asep_aru* m, bool up, const TL& in0, const TL* dec, const std::ve
             ba.b.w1 = m->d_r8b_down_w1r ? m->d_r8b_down_w1r : m->det_first.d_w; ba.b.b1 = m->det_first.d_b; ba.b.wpk = (const u32x4*)m->d_r8b_down_w; ba.b.bias = m->d_r8b_down_b;
         }
         TL sub(in0.begin() + b0, in0.begin() + b1);
-        const std::string what = (up ? "unet_up_0 (conv1[16->8]+3xconvR+add) " : "unet_down_0 (conv1+3xconvR+add+pool) ") + dims_of(sub);
+        const std::string what = res8_what(up, sub);
         double area = 0;
         for (size_t i = b0; i < b1; ++i) area += (double)in0[i].H * in0[i].W;
         const double wf = wshare / area;                     // the walker's share of the pages' pixels
@@ -1625,7 +1564,7 @@ void run_res8b(asep_aru* m, bool up, const TL& a0, const TL* a1, const std::vect
         std::vector<const float*> wst, rst;
         for (size_t i = 0; i < a0.size(); ++i) {
             const Tensor& t = a0[i];
-            const bool fits = (t.W - 4 - R8W_X0) / R8W_TW >= 4 && t.H - 4 - R8W_Y0 >= 32 && (size_t)t.H * t.W < ((size_t)1 << 28);
+            const bool fits = walk_region(t.H, t.W).fits;
             (fits ? ws : rs).push_back(t);
             if (up) (fits ? wd : rd).push_back((*a1)[i]);
             (fits ? wo : ro).push_back((*d_out)[i]);
@@ -1643,18 +1582,17 @@ void run_res8b(asep_aru* m, bool up, const TL& a0, const TL* a1, const std::vect
 
 // the tile kernels (res8f_kernel for interior tiles + res8b_tile for border tiles in one launch) on the given output tensors
 void run_res8b_tiles(asep_aru* m, bool up, const TL& a0, const TL* a1, const std::vector<const float*>& stats, bool want_pool, const TL& outs, const TL* pool_out) {
-    const TL* d_out = &outs;
     for (size_t b0 = 0; b0 < a0.size(); b0 += MAXP) {
         const size_t b1 = std::min(a0.size(), b0 + MAXP);
         Res8BArgs a{};
         int tiles = 0;
         double flops = 0, bytes = 0;
         for (size_t i = b0; i < b1; ++i) {
-            bytes += tbytes(a0[i]) + (up ? tbytes((*a1)[i]) : 0.0) + tbytes((*d_out)[i]) + (want_pool ? tbytes((*pool_out)[i]) : 0.0);
+            bytes += tbytes(a0[i]) + (up ? tbytes((*a1)[i]) : 0.0) + tbytes(outs[i]) + (want_pool ? tbytes((*pool_out)[i]) : 0.0);
             Res8BProb& p = a.p[i - b0];
             if (up) { p.skip = a0[i].bp(); p.dec = (*a1)[i].bp(); }
             else { p.img = a0[i].p; p.stats = stats.empty() ? nullptr : stats[i]; }
-            p.out = (*d_out)[i].bp(); p.pool = want_pool ? (*pool_out)[i].bp() : nullptr;
+            p.out = outs[i].bp(); p.pool = want_pool ? (*pool_out)[i].bp() : nullptr;
             p.H = a0[i].H; p.W = a0[i].W;
             p.tiles_x = cdiv(a0[i].W, 32);
             p.tile_begin = tiles;
@@ -1667,7 +1605,7 @@ void run_res8b_tiles(asep_aru* m, bool up, const TL& a0, const TL* a1, const std
         TL sub(a0.begin() + b0, a0.begin() + b1);
         int units = tiles;
         a.xm = oneshot_map(m, tiles, &units);
-        const std::string what = (up ? "unet_up_0 (conv1[16->8]+3xconvR+add) " : "unet_down_0 (conv1+3xconvR+add+pool) ") + dims_of(sub);
+        const std::string what = res8_what(up, sub);
         bool small = true;                                   // res8f_kernel addresses its tensors with 32-bit byte offsets (16 bytes per pixel)
         for (size_t i = b0; i < b1; ++i) small = small && (size_t)a0[i].H * a0[i].W < ((size_t)1 << 28);
         if (m->fused_act) {                                  // elu / leaky: the general form for every tile
@@ -2171,7 +2109,7 @@ TL det_cnn(asep_aru* m, const TL& imgs, const std::vector<std::string>& names, c
         }
         if (l == 0 && (m->use_fused8 || (m->fused8_var && r8v_fits(imgs))) && m->d_r8_down_wr) {
             TL d, pooled;
-            run_res8_down(m, imgs, stats, n > 1, &d, &pooled);
+            run_res8(m, false, imgs, nullptr, stats, n > 1, &d, &pooled);
             skips.push_back(d);
             publish(d, "_unet_down_0_conv");
             u = n > 1 ? pooled : d;
@@ -2206,7 +2144,9 @@ TL det_cnn(asep_aru* m, const TL& imgs, const std::vector<std::string>& names, c
             TL t = run_convb(m, scope + "/conv1", skip, &v, false, false, nullptr);   // concat [skip, deconv]
             u = res_block_tail(m, scope, t);
         } else if (l == 0 && (m->use_fused8 || (m->fused8_var && r8v_fits(skip))) && m->d_r8_up_w1) {
-            u = run_res8_up(m, skip, v);
+            TL d, none;
+            run_res8(m, true, skip, &v, {}, false, &d, &none);
+            u = d;
         } else if (m->cfg.plain_u) {                         // ARU_v1.py:283-288
             TL c1 = conv_act(m, scope + "/conv1", skip, &v, false, true, nullptr);
             u = conv_act(m, scope + "/conv2", c1, nullptr, false, true, nullptr);
@@ -2275,7 +2215,7 @@ TL att_cnn(asep_aru* m, const TL& imgs, const std::vector<const float*>& stats) 
             }
             a.nprob = (int)(b1 - b0);
             a.wpk = (const f32x4*)m->d_att_head; a.bias = m->att_first.d_b; a.w = m->att_first.d_w; a.act = m->cfg.activation;
-            bool valu = m->r8_valu || m->bf16;               // vector-ALU form (32-bit output offsets, see run_res8_down)
+            bool valu = m->r8_valu || m->bf16;               // vector-ALU form (32-bit output offsets, see r8v_fits)
             for (size_t i = b0; i < b1; ++i) valu = valu && (size_t)imgs[i].H * imgs[i].W < ((size_t)1 << 28);
             if (m->bf16 && !valu) { set_error("bf16 path: image too large for the attention head kernel"); throw ArgError(); }
             if (head_variant && !valu) { set_error("attention head of an elu / leaky graph: image too large for the vector-ALU kernel"); throw ArgError(); }

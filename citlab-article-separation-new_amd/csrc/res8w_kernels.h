@@ -30,15 +30,14 @@
 // res8wb_kernel with the general tile function res8b_tile (zero tests, clipped stores).  Pages too small for a strip stay on res8f_kernel.
 #pragma once
 #include "bf16_kernels.h"
+#include "level0_plan.h"           // R8W_TW, R8W_X0, R8W_Y0 and the page geometry the host launches with
 
 namespace asep {
 
 #ifndef R8W_DEPTH
 #define R8W_DEPTH 4
 #endif
-constexpr int R8W_TW = 24;             // output columns of a strip
 constexpr int R8W_D = R8W_DEPTH;               // pair slots of the input ring = input row pairs in flight
-constexpr int R8W_X0 = 32, R8W_Y0 = 16;   // the walker's region starts here (one border tile column / row in front of it)
 
 struct Res8WProb {
     const bf16_t* skip;    // UP: [H,W,8]

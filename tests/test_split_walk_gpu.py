@@ -50,7 +50,7 @@ def _rel(a, b):
 
 
 def _walks(H, W):
-    """the engine's rule (aru_engine.hip, r8ws_fits): room for four 24-column strips right of column 32 and two 16-row bands below row 16"""
+    """the engine's rule (csrc/level0_plan.h, walk_region(H, W).fits; checked on the host by test_level0_plan_host.py): room for four 24-column strips right of column 32 and two 16-row bands below row 16"""
     return (W - 4 - 32) // 24 >= 4 and H - 4 - 16 >= 32
 
 
