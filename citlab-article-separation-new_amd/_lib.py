@@ -40,6 +40,11 @@ class GnnCfg(_SizedCfg):
         "attention_hidden4", "cls_hidden3", "cls_hidden4", "lstm_use_hidden", "lstm_use_input", "visual_edge_dims")]
 
 
+class ClusterSetting(C.Structure):
+    """asep_cluster_setting (include/asep_hip.h): one setting of asep_cluster_grid_run"""
+    _fields_ = [("min_neighbors", C.c_int32), ("assign_noise", C.c_int32), ("conf_thr", C.c_double), ("agree_thr", C.c_double)]
+
+
 class GnnPage(C.Structure):
     """asep_gnn_page (include/asep_hip.h): one page of asep_gnn_forward_visual_batch_dev, device addresses"""
     _fields_ = [("N", C.c_int32), ("E", C.c_int32), ("R", C.c_int32), ("d_edges", C.c_void_p), ("d_node_feat", C.c_void_p),
@@ -116,6 +121,9 @@ SIGNATURES = {
     "asep_measure_last_kernel_us": (C.c_double, [C.c_int]),
     "asep_heading_grid_eval": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
     "asep_heading_grid_last_kernel_us": (C.c_double, []),
+    "asep_cluster_grid_run": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "asep_cluster_grid_last_kernel_us": (C.c_double, []),
+    "asep_cluster_grid_max_nodes": (C.c_int, []),
     "asep_releval_create": (_P, []),
     "asep_releval_free": (None, [_P]),
     "asep_releval_reset": (C.c_int, [_P, _P]),

@@ -444,6 +444,38 @@ int asep_heading_grid_eval(asep_post* p, int n_pages, const int32_t* line_off, c
 /* Device time in microseconds of the kernel of the calling thread's last asep_heading_grid_eval (0 if nothing ran). */
 double asep_heading_grid_last_kernel_us(void);
 
+/* ---- clustering grid (clustering/dbscan.py for many pages and settings; the counts of as_eval.py) ---------------------------
+ * Runs DBScanRelation.cluster_relations for every (page, setting) pair in one launch on the asep_post handle, one wavefront per
+ * pair; the labels equal the host class's, integer for integer.  Page k has the nodes node_off[k] .. node_off[k+1]-1 (N_k of
+ * them, at most asep_cluster_grid_max_nodes()); `conf` holds the pages' N_k x N_k matrices, row-major, one after the other, as
+ * float (conf_is_f64 0) or double (1), prepared as DBScanRelation.confidences holds them (clamped, symmetric).  The thresholds
+ * are compared in the matrix dtype: conf > (T)conf_thr for a neighbour, np.mean(conf[cand, members]) > (T)agree_thr to join.
+ * A page of two nodes follows TextblockClustering.calc instead: labels 1, 1 when conf[0][1] >= (T)conf_thr, else 1, 2; only that
+ * entry is read, so the caller passes the matrix calc tests (TextblockClustering._conf_mat, which need not be symmetric).
+ * out_labels [n_settings][node_off[n_pages]]: labels from 1, -1 for noise nodes when assign_noise is 0.
+ * The comparison tables are optional (all NULL: labels only).  Page k has the hypothesis lines line_off[k] .. line_off[k+1]-1:
+ * line_node = the node of the page the line hangs in, line_gt = the line's dense ground truth article index (below the page's
+ * number of lines) or -1 when the ground truth lacks the line; and the ground truth blocks gtblk_off[k] .. gtblk_off[k+1]-1,
+ * block b listing the lines gtblk_lines[gtblk_line_off[b] .. gtblk_line_off[b+1]-1] as indices within the page.
+ * out_counts [n_settings][n_pages][4] = hypNIs (distinct labels over the lines), n_inf (distinct (ground truth article, label)
+ * pairs over the lines with line_gt >= 0), corrects (listed blocks whose lines share one label that no other line carries), 0.
+ * With the tables given out_labels may be NULL.  Bad offsets, indices or a page above the limit return ASEP_ERR_ARG
+ * (asep_last_error) and launch nothing.  Host pointers in and out; returns after the results have arrived. */
+typedef struct asep_cluster_setting {
+    int32_t min_neighbors; /* min_neighbors_for_cluster */
+    int32_t assign_noise;  /* assign_noise_clusters */
+    double conf_thr;       /* confidence_threshold */
+    double agree_thr;      /* cluster_agreement_threshold */
+} asep_cluster_setting;
+int asep_cluster_grid_run(asep_post* p, int n_pages, const int32_t* node_off, const void* conf, int conf_is_f64, int n_settings,
+                          const asep_cluster_setting* settings, const int32_t* line_off, const int32_t* line_node,
+                          const int32_t* line_gt, const int32_t* gtblk_off, const int32_t* gtblk_line_off,
+                          const int32_t* gtblk_lines, int32_t* out_labels, int32_t* out_counts);
+/* Device time in microseconds of the kernels of the calling thread's last asep_cluster_grid_run (0 if nothing ran). */
+double asep_cluster_grid_last_kernel_us(void);
+/* Largest N_k asep_cluster_grid_run accepts. */
+int asep_cluster_grid_max_nodes(void);
+
 /* ---- relation net evaluation (article_separation/gnn/trainer/lav_rel.py) ----------------------------------------------
  * An accumulator of (score, label) pairs in HBM and sklearn's _binary_clf_curve over them: what precision_recall_curve,
  * roc_auc_score and accuracy_score of lav_rel.py:190-229 are computed from, without a probability leaving the device.
