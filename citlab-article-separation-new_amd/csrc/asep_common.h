@@ -91,6 +91,34 @@ private:
     size_t next_ = 0;
 };
 
+// n elements of host memory in the pool's next buffer (never an empty request); throws HipError
+template <class T>
+T* upload(BufferPool& pool, hipStream_t st, const T* src, size_t n) {
+    T* d = (T*)pool.get((n ? n : 1) * sizeof(T));
+    if (n) ASEP_HIP_CHECK_THROW(hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, st));
+    return d;
+}
+
+// Device time between start and stop on one stream, read once the stream has been synchronised; throws HipError
+struct KernelTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~KernelTimer() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    void start(hipStream_t st) {
+        ASEP_HIP_CHECK_THROW(hipEventCreate(&e0));
+        ASEP_HIP_CHECK_THROW(hipEventCreate(&e1));
+        ASEP_HIP_CHECK_THROW(hipEventRecord(e0, st));
+    }
+    void stop(hipStream_t st) { ASEP_HIP_CHECK_THROW(hipEventRecord(e1, st)); }
+    void read(double& us) {
+        float ms = 0.f;
+        ASEP_HIP_CHECK_THROW(hipEventElapsedTime(&ms, e0, e1));
+        us = 1000.0 * ms;
+    }
+};
+
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // Device pointer + {H, W, C} of a named end point of the last ARU forward (aru_engine.hip); library-internal.

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "asep_common.h"
+#include "batch_tables.h"
 #include "cluster_grid_kernels.h"
 
 using namespace asep;
@@ -14,35 +15,7 @@ namespace {
 
 const char* const FN = "asep_cluster_grid_run";
 
-bool check_offsets(const char* what, const int32_t* off, int n) {
-    if (off[0] != 0) {
-        set_error("%s: %s must start at 0 (starts at %d)", FN, what, off[0]);
-        return false;
-    }
-    for (int k = 0; k < n; ++k)
-        if (off[k + 1] < off[k]) {
-            set_error("%s: %s %d (%d -> %d) is decreasing", FN, what, k, off[k], off[k + 1]);
-            return false;
-        }
-    return true;
-}
-
 thread_local double g_kernel_us = 0.0;   // device time of this thread's last asep_cluster_grid_run (both kernels)
-
-template <class T>
-T* upload(BufferPool& pool, hipStream_t st, const T* src, size_t n) {
-    T* d = (T*)pool.get((n ? n : 1) * sizeof(T));
-    if (n) ASEP_HIP_CHECK_THROW(hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, st));
-    return d;
-}
-
-struct Events {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
 
 }  // namespace
 
@@ -65,7 +38,7 @@ int asep_cluster_grid_run(asep_post* p, int n_pages, const int32_t* node_off, co
                   CLG_MAX_PROBLEMS);
         return ASEP_ERR_ARG;
     }
-    if (!check_offsets("node_off", node_off, n_pages)) return ASEP_ERR_ARG;
+    if (!check_offsets(FN, "node_off", node_off, n_pages)) return ASEP_ERR_ARG;
     const int n_nodes = node_off[n_pages];
     int max_n = 0;
     std::vector<int64_t> conf_off((size_t)n_pages + 1, 0);
@@ -90,10 +63,11 @@ int asep_cluster_grid_run(asep_post* p, int n_pages, const int32_t* node_off, co
             set_error("%s: the comparison needs line_off, gtblk_off, gtblk_line_off and out_counts (all six tables or none)", FN);
             return ASEP_ERR_ARG;
         }
-        if (!check_offsets("line_off", line_off, n_pages) || !check_offsets("gtblk_off", gtblk_off, n_pages)) return ASEP_ERR_ARG;
+        if (!check_offsets(FN, "line_off", line_off, n_pages) || !check_offsets(FN, "gtblk_off", gtblk_off, n_pages))
+            return ASEP_ERR_ARG;
         n_lines = line_off[n_pages];
         n_blk = gtblk_off[n_pages];
-        if (!check_offsets("gtblk_line_off", gtblk_line_off, n_blk)) return ASEP_ERR_ARG;
+        if (!check_offsets(FN, "gtblk_line_off", gtblk_line_off, n_blk)) return ASEP_ERR_ARG;
         n_ent = gtblk_line_off[n_blk];
         if ((n_lines && (!line_node || !line_gt)) || (n_ent && !gtblk_lines)) {
             set_error("%s: null argument (line_node, line_gt or gtblk_lines)", FN);
@@ -112,14 +86,8 @@ int asep_cluster_grid_run(asep_post* p, int n_pages, const int32_t* node_off, co
                     return ASEP_ERR_ARG;
                 }
             }
-            for (int b = gtblk_off[k]; b < gtblk_off[k + 1]; ++b)
-                for (int e = gtblk_line_off[b]; e < gtblk_line_off[b + 1]; ++e)
-                    if (gtblk_lines[e] < 0 || gtblk_lines[e] >= nl) {
-                        set_error("%s: ground truth block %d of page %d lists line %d, the page has %d lines", FN, b - gtblk_off[k], k,
-                                  gtblk_lines[e], nl);
-                        return ASEP_ERR_ARG;
-                    }
         }
+        if (!check_members(FN, "ground truth block", n_pages, line_off, gtblk_off, gtblk_line_off, gtblk_lines)) return ASEP_ERR_ARG;
     }
     if (n_settings == 0 || n_pages == 0) return ASEP_OK;
     ASEP_GUARD_BEGIN
@@ -149,9 +117,8 @@ int asep_cluster_grid_run(asep_post* p, int n_pages, const int32_t* node_off, co
         d_counts = (int4*)pool.get(count_bytes);
     }
     const unsigned blocks = (unsigned)n_pages * (unsigned)n_settings;
-    Events ev;
-    for (hipEvent_t& x : ev.e) ASEP_HIP_CHECK(hipEventCreate(&x));
-    ASEP_HIP_CHECK(hipEventRecord(ev.e[0], st));
+    KernelTimer tm;
+    tm.start(st);
     if (conf_is_f64)
         cluster_grid_kernel<double><<<blocks, CLG_WAVE, (size_t)max_n * (sizeof(double) + 8), st>>>(
             (const double*)d_conf, d_conf_off, d_node_off, d_set, n_settings, n_pages, max_n, d_labels);
@@ -165,13 +132,11 @@ int asep_cluster_grid_run(asep_post* p, int n_pages, const int32_t* node_off, co
                                                                                 n_settings, n_pages, max_n, d_counts);
         ASEP_HIP_CHECK(hipGetLastError());
     }
-    ASEP_HIP_CHECK(hipEventRecord(ev.e[1], st));
+    tm.stop(st);
     if (out_labels && label_bytes) ASEP_HIP_CHECK(hipMemcpyAsync(out_labels, d_labels, label_bytes, hipMemcpyDeviceToHost, st));
     if (compare) ASEP_HIP_CHECK(hipMemcpyAsync(out_counts, d_counts, count_bytes, hipMemcpyDeviceToHost, st));
     ASEP_HIP_CHECK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    ASEP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-    g_kernel_us = 1000.0 * ms;
+    tm.read(g_kernel_us);
     return ASEP_OK;
     ASEP_GUARD_END
 }

@@ -3,41 +3,16 @@
 #include <vector>
 
 #include "asep_common.h"
+#include "batch_tables.h"
 #include "heading_eval_kernels.h"
 
 using namespace asep;
 
 namespace {
 
-bool check_offsets(const char* what, const int32_t* off, int n, int total) {
-    if (off[0] != 0 || off[n] != total) {
-        set_error("asep_heading_grid_eval: %s must run from 0 to %d (is %d .. %d)", what, total, off[0], off[n]);
-        return false;
-    }
-    for (int k = 0; k < n; ++k)
-        if (off[k + 1] < off[k]) {
-            set_error("asep_heading_grid_eval: %s %d (%d -> %d) is decreasing", what, k, off[k], off[k + 1]);
-            return false;
-        }
-    return true;
-}
+const char* const FN = "asep_heading_grid_eval";
 
 thread_local double g_kernel_us = 0.0;   // device time of this thread's last asep_heading_grid_eval launch
-
-template <class T>
-T* upload(BufferPool& pool, hipStream_t st, const T* src, size_t n) {
-    T* d = (T*)pool.get((n ? n : 1) * sizeof(T));
-    if (n) ASEP_HIP_CHECK_THROW(hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, st));
-    return d;
-}
-
-struct Events {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
 
 }  // namespace
 
@@ -54,11 +29,11 @@ int asep_heading_grid_eval(asep_post* p, int n_pages, const int32_t* line_off, c
         return ASEP_ERR_ARG;
     }
     const int n_lines = line_off[n_pages], n_regs = reg_off[n_pages];
-    if (n_lines < 0 || n_regs < 0 || !check_offsets("line_off", line_off, n_pages, n_lines) ||
-        !check_offsets("reg_off", reg_off, n_pages, n_regs))
+    if (n_lines < 0 || n_regs < 0 || !check_offsets(FN, "line_off", line_off, n_pages) ||
+        !check_offsets(FN, "reg_off", reg_off, n_pages))
         return ASEP_ERR_ARG;
     const int n_ent = reg_line_off[n_regs];
-    if (n_ent < 0 || !check_offsets("reg_line_off", reg_line_off, n_regs, n_ent)) return ASEP_ERR_ARG;
+    if (n_ent < 0 || !check_offsets(FN, "reg_line_off", reg_line_off, n_regs)) return ASEP_ERR_ARG;
     if ((n_lines && (!sw_conf || !th_conf || !net_conf)) || (n_ent && !reg_lines) || (n_regs && !gt_heading) ||
         (n_pages && !use_swt) || (n_settings && (!settings || (n_pages && !out_counts)))) {
         set_error("asep_heading_grid_eval: null argument");
@@ -70,22 +45,16 @@ int asep_heading_grid_eval(asep_post* p, int n_pages, const int32_t* line_off, c
                       i % HEVAL_FIELDS, settings[i]);
             return ASEP_ERR_ARG;
         }
+    if (!check_members(FN, "region", n_pages, line_off, reg_off, reg_line_off, reg_lines)) return ASEP_ERR_ARG;
     ASEP_GUARD_BEGIN
-    // the lines of each region, in region order, as entries the kernel walks from front to back
+    // the lines of each region, in region order, as entries the kernel walks from front to back (a page's regions are consecutive)
     std::vector<HevalEntry> ent((size_t)n_ent);
     for (int k = 0; k < n_pages; ++k) {
-        const int l0 = line_off[k], nl = line_off[k + 1] - l0;
-        for (int r = reg_off[k]; r < reg_off[k + 1]; ++r)
-            for (int e = reg_line_off[r]; e < reg_line_off[r + 1]; ++e) {
-                const int i = reg_lines[e];
-                if (i < 0 || i >= nl) {
-                    set_error("asep_heading_grid_eval: region %d of page %d lists line %d, the page has %d lines", r - reg_off[k], k,
-                              i, nl);
-                    return ASEP_ERR_ARG;
-                }
-                ent[e] = HevalEntry{sw_conf[l0 + i], th_conf[l0 + i], net_conf[l0 + i], line_tagged ? (line_tagged[l0 + i] != 0) : 0,
-                                    0};
-            }
+        const int l0 = line_off[k];
+        for (int e = reg_line_off[reg_off[k]]; e < reg_line_off[reg_off[k + 1]]; ++e) {
+            const int i = l0 + reg_lines[e];
+            ent[e] = HevalEntry{sw_conf[i], th_conf[i], net_conf[i], line_tagged ? (line_tagged[i] != 0) : 0, 0};
+        }
     }
     if (n_settings == 0 || n_pages == 0) return ASEP_OK;
     hipStream_t st = post_stream(p);
@@ -102,18 +71,15 @@ int asep_heading_grid_eval(asep_post* p, int n_pages, const int32_t* line_off, c
     int32_t* d_set = upload(pool, st, settings, (size_t)n_settings * HEVAL_FIELDS);
     const size_t out_bytes = (size_t)n_settings * n_pages * 4 * sizeof(int32_t);
     int4* d_out = (int4*)pool.get(out_bytes);
-    Events ev;
-    for (hipEvent_t& x : ev.e) ASEP_HIP_CHECK(hipEventCreate(&x));
-    ASEP_HIP_CHECK(hipEventRecord(ev.e[0], st));
+    KernelTimer tm;
+    tm.start(st);
     heval_grid_kernel<<<dim3((unsigned)cdiv(n_settings, HEVAL_BLOCK), (unsigned)n_pages), HEVAL_BLOCK, 0, st>>>(
         d_ent, d_reg_ent, d_reg_page, d_gt, d_swt, d_set, n_settings, n_pages, d_out);
     ASEP_HIP_CHECK(hipGetLastError());
-    ASEP_HIP_CHECK(hipEventRecord(ev.e[1], st));
+    tm.stop(st);
     ASEP_HIP_CHECK(hipMemcpyAsync(out_counts, d_out, out_bytes, hipMemcpyDeviceToHost, st));
     ASEP_HIP_CHECK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    ASEP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-    g_kernel_us = 1000.0 * ms;
+    tm.read(g_kernel_us);
     return ASEP_OK;
     ASEP_GUARD_END
 }

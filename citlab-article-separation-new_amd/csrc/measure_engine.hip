@@ -3,25 +3,14 @@
 #include <vector>
 
 #include "asep_common.h"
+#include "batch_tables.h"
 #include "measure_kernels.h"
 
 using namespace asep;
 
 namespace {
 
-bool check_offsets(const char* what, const int32_t* off, int n, int total, bool nonempty) {
-    if (off[0] != 0 || off[n] != total) {
-        set_error("asep_measure_run: %s must run from 0 to %d", what, total);
-        return false;
-    }
-    for (int k = 0; k < n; ++k)
-        if (off[k + 1] < off[k] + (nonempty ? 1 : 0)) {
-            set_error("asep_measure_run: %s %d (%d -> %d) is %s", what, k, off[k], off[k + 1],
-                      nonempty ? "empty or decreasing" : "decreasing");
-            return false;
-        }
-    return true;
-}
+const char* const FN = "asep_measure_run";
 
 // device time of the kernels of this thread's last asep_measure_run (0 count, 1 pair, 2 recall), microseconds
 thread_local double g_kernel_us[3] = {0.0, 0.0, 0.0};
@@ -37,21 +26,6 @@ struct Results {
     uint32_t *pair_hist = nullptr, *rec_hist = nullptr, *truth_hist = nullptr;
 };
 thread_local Results g_res;
-
-template <class T>
-T* upload(BufferPool& pool, hipStream_t st, const T* src, size_t n) {
-    T* d = (T*)pool.get((n ? n : 1) * sizeof(T));
-    if (n) ASEP_HIP_CHECK_THROW(hipMemcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, st));
-    return d;
-}
-
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
 
 }  // namespace
 
@@ -73,14 +47,17 @@ long long asep_measure_run(asep_post* p, int n_files, const int32_t* t_file_off,
         return ASEP_ERR_ARG;
     }
     const int n_truth = t_file_off[n_files], n_reco = r_file_off[n_files], n_arts = art_file_off[n_files];
-    if (n_truth < 0 || n_reco < 0 || n_arts < 0 || !check_offsets("t_file_off", t_file_off, n_files, n_truth, false) ||
-        !check_offsets("r_file_off", r_file_off, n_files, n_reco, false) ||
-        !check_offsets("art_file_off", art_file_off, n_files, n_arts, false))
+    if (n_truth < 0 || n_reco < 0 || n_arts < 0 || !check_offsets(FN, "t_file_off", t_file_off, n_files) ||
+        !check_offsets(FN, "r_file_off", r_file_off, n_files) || !check_offsets(FN, "art_file_off", art_file_off, n_files))
         return ASEP_ERR_ARG;
     const int n_tp = t_poly_off[n_truth], n_rp = r_poly_off[n_reco];
-    if (!check_offsets("t_poly_off", t_poly_off, n_truth, n_tp, true) ||
-        !check_offsets("r_poly_off", r_poly_off, n_reco, n_rp, true) || !check_offsets("art_off", art_off, n_arts, n_reco, false))
+    if (!check_offsets(FN, "t_poly_off", t_poly_off, n_truth, true) || !check_offsets(FN, "r_poly_off", r_poly_off, n_reco, true))
         return ASEP_ERR_ARG;
+    if (art_off[n_arts] != n_reco) {
+        set_error("%s: art_off ends at %d, the files hold %d reco polygons", FN, art_off[n_arts], n_reco);
+        return ASEP_ERR_ARG;
+    }
+    if (!check_offsets(FN, "art_off", art_off, n_arts)) return ASEP_ERR_ARG;
     if ((n_tp && !t_points) || (n_rp && !r_points) || (n_truth && (!t_boxes || !tols)) || (n_reco && !r_boxes) ||
         (n_arts && !art_has_id)) {
         set_error("asep_measure_run: null argument");
@@ -132,22 +109,19 @@ long long asep_measure_run(asep_post* p, int n_files, const int32_t* t_file_off,
     int* d_aid = upload(pool, st, art_has_id, (size_t)n_arts);
     double* d_tols = upload(pool, st, tols, (size_t)n_truth * n_tols);
     int* d_count = (int*)pool.get(((size_t)n_reco + n_truth + 1) * sizeof(int));
-    Events ev;
-    for (hipEvent_t& x : ev.e) ASEP_HIP_CHECK(hipEventCreate(&x));
+    KernelTimer tm_count, tm_pair, tm_recall;
 
     std::vector<int> count((size_t)n_reco + n_truth);
     std::vector<long long> off((size_t)n_reco + n_truth + 2, 0);
     if (n_reco + n_truth > 0) {
-        ASEP_HIP_CHECK(hipEventRecord(ev.e[0], st));
+        tm_count.start(st);
         ms_count_kernel<<<(unsigned)cdiv(n_reco + n_truth, MEASURE_BLOCK), MEASURE_BLOCK, 0, st>>>(
             d_tbox, d_rbox, d_rrange, d_tarts, d_aoff, n_truth, n_reco, dmax, d_count, d_count + n_reco);
         ASEP_HIP_CHECK(hipGetLastError());
-        ASEP_HIP_CHECK(hipEventRecord(ev.e[1], st));
+        tm_count.stop(st);
         ASEP_HIP_CHECK(hipMemcpyAsync(count.data(), d_count, count.size() * sizeof(int), hipMemcpyDeviceToHost, st));
         ASEP_HIP_CHECK(hipStreamSynchronize(st));
-        float ms = 0.f;
-        ASEP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        g_kernel_us[0] = 1000.0 * ms;
+        tm_count.read(g_kernel_us[0]);
     }
     // pair_off [n_reco + 1] and rec_off [n_truth + 1], one after the other
     long long* pair_off = off.data();
@@ -175,30 +149,23 @@ long long asep_measure_run(asep_post* p, int n_files, const int32_t* t_file_off,
         r.truth_hist = (uint32_t*)pool.get(((size_t)n_truth * 2 + 1) * bins * sizeof(uint32_t));
     }
     if (n_reco > 0 && n_pairs > 0) {
-        ASEP_HIP_CHECK(hipEventRecord(ev.e[0], st));
+        tm_pair.start(st);
         ms_pair_kernel<<<(unsigned)n_reco, MEASURE_BLOCK, (size_t)bins * sizeof(int), st>>>(
             d_tp, d_toff, d_tbox, d_rp, d_roff, d_rbox, d_rrange, d_tols, n_tols, dmax, d_off, r.pair_ij, r.pair_hits, r.pair_hist);
         ASEP_HIP_CHECK(hipGetLastError());
-        ASEP_HIP_CHECK(hipEventRecord(ev.e[1], st));
+        tm_pair.stop(st);
     }
     if (n_truth > 0) {
-        ASEP_HIP_CHECK(hipEventRecord(ev.e[2], st));
+        tm_recall.start(st);
         ms_recall_kernel<<<(unsigned)n_truth, MEASURE_BLOCK, ((size_t)bins + 2 * (size_t)max_points) * sizeof(int), st>>>(
             d_tp, d_toff, d_tbox, d_rp, d_roff, d_rbox, d_tarts, d_aoff, d_aid, d_tols, n_tols, dmax, max_points,
             d_off + n_reco + 1, r.rec_ja, r.rec_hits, r.truth_hits, r.rec_hist, r.truth_hist);
         ASEP_HIP_CHECK(hipGetLastError());
-        ASEP_HIP_CHECK(hipEventRecord(ev.e[3], st));
+        tm_recall.stop(st);
     }
     ASEP_HIP_CHECK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    if (n_reco > 0 && n_pairs > 0) {
-        ASEP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        g_kernel_us[1] = 1000.0 * ms;
-    }
-    if (n_truth > 0) {
-        ASEP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
-        g_kernel_us[2] = 1000.0 * ms;
-    }
+    if (n_reco > 0 && n_pairs > 0) tm_pair.read(g_kernel_us[1]);
+    if (n_truth > 0) tm_recall.read(g_kernel_us[2]);
     out_counts[0] = n_pairs;
     out_counts[1] = n_recs;
     g_res = r;
