@@ -1,4 +1,4 @@
-// ARU-Net inference engine (host side): weight packing for the MFMA fragment order, buffer
+// ARU-Net inference engine (host side): the packed weights (fragment orders: aru_pack.h) on the device, buffer
 // management and the layer schedule of ARU_v1.py:62-294.  Entry points: include/asep_hip.h.
 #include <algorithm>
 #include <cmath>
@@ -15,6 +15,7 @@
 #include "convr_kernels.h"
 #include "split_kernels.h"
 #include "asep_common.h"
+#include "aru_pack.h"
 
 using namespace asep;
 
@@ -28,26 +29,16 @@ struct Tensor {
     bf16_t* bp() const { return reinterpret_cast<bf16_t*>(p); }
 };
 
-// A convolution whose weights are packed as the A operand of v_mfma_f32_16x16x4_f32.
-struct PackedConv {
-    int kh = 0, kw = 0, cin = 0, cout = 0;
-    bool c8 = false;       // Cin == 8: two taps per 16-slot chunk
-    bool c12 = false;      // Cin == 12, 4x4 taps (attention conv2): dense rows of 48 floats = 3 chunks, no channel padding
-    bool deconv = false;
-    int groups = 0, mtiles = 0, nchunks = 0;
+// A convolution whose weights are packed as the A operand of v_mfma_f32_16x16x4_f32: its shape decisions (ConvPlan, aru_pack.h) + the packed filters
+struct PackedConv : ConvPlan {
     float* d_w = nullptr;
     float* d_b = nullptr;
     float* d_wino = nullptr;   // Winograd F(2x2,3x3) transformed weights U = G g G^T, packed [g][pos][mtile][lane][4]
     float* d_wv = nullptr;     // scalar-operand filters of the vector-ALU kernels: deconv 16 -> 8 [tap][ci][co] (deconv8v_kernel),
                                // 4x4 conv 32 -> 1 [tap][ci] (conv_c1out_kernel)
-    // native bf16 path (bf16_kernels.h): A fragments of v_mfma_f32_16x16x32_bf16, 8 bf16 per lane
-    int bmode = -1;            // convb / deconvb MODE (0: Cin 8, 1: Cin 16, 2: Cin % 32 == 0); -1: not packed
-    int bchunks = 0;
     bf16_t* d_wb = nullptr;    // conv: [chunk][mtile][lane][8]; deconv: MODE 2 [G][tap][mtile][lane][8], MODE 1 [frag 0..5][mtile][lane][8]
     bf16_t* d_wb8 = nullptr;   // deconv 16 -> 8 (level 0): the three class-pair fragments of deconvb8_kernel [3][lane][8]
-    // fp32 with split products (split_kernels.h): the filter as three bf16 parts, [chunk][part h, m, l][mtile][lane][8]
-    int smode = -1;            // 1: Cin 12 / 16 (chunk = two taps), 2: Cin % 32 == 0 (chunk = tap x 32 channels); -1: not packed
-    bf16_t* d_ws = nullptr;
+    bf16_t* d_ws = nullptr;    // the filter as three bf16 parts, [chunk][part h, m, l][mtile][lane][8]
     bf16_t* d_ws16 = nullptr;  // 3x3, Cin % 16 == 0, Cin >= 32: stages of 16 channels, chunk = two taps (convs16_kernel): [stage][chunk 5][part][mtile][lane][8]
 };
 
@@ -56,12 +47,6 @@ struct DirectConv {        // Cin == 1 first layers
     float* d_w = nullptr;  // [k*k][cout]
     float* d_b = nullptr;
 };
-
-int upload(const std::vector<float>& h, float** d) {
-    ASEP_HIP_CHECK(hipMalloc((void**)d, std::max<size_t>(h.size(), 4) * sizeof(float)));
-    ASEP_HIP_CHECK(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    return ASEP_OK;
-}
 
 }  // namespace
 
@@ -196,6 +181,22 @@ struct asep_aru {
         return (int)prof_names.size() - 1;
     }
     int feat(int l) const { return cfg.feat_root << l; }
+    // n elements of device memory that the handle owns from the moment they exist; throws HipError
+    template <class T>
+    T* alloc(size_t n) {
+        owned.push_back(nullptr);
+        ASEP_HIP_CHECK_THROW(hipMalloc(&owned.back(), n * sizeof(T)));
+        return (T*)owned.back();
+    }
+    // the one way of putting a host vector on the device (never less than 16 bytes: 4 floats, 8 bf16); throws HipError
+    template <class T>
+    T* put(const std::vector<T>& h) {
+        T* d = alloc<T>(std::max(h.size(), 16 / sizeof(T)));
+        ASEP_HIP_CHECK_THROW(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+        return d;
+    }
+    template <class T>
+    T* put_some(const std::vector<T>& h) { return h.empty() ? nullptr : put(h); }   // a vector left empty by its packer: the member stays unset
 };
 
 namespace {
@@ -235,155 +236,16 @@ std::string targs(std::initializer_list<std::string> l) {
 inline std::string tb(bool b) { return b ? "true" : "false"; }
 inline std::string ti(int i) { return std::to_string(i); }
 
-// ---- weight packing -----------------------------------------------------------------------------
-int pack_conv_bf(asep_aru* m, PackedConv& pc, const HostTensor& w);   // bf16 fragments (native bf16 path), defined further down
-int pack_conv_split(asep_aru* m, PackedConv& pc, const HostTensor& w);   // three-part bf16 fragments (split_kernels.h)
-int pack_deconv_split(asep_aru* m, PackedConv& pc, const HostTensor& w); // the same for deconvs_kernel
-
-// conv   W[kh][kw][cin][cout]  (layers.py:219);  deconv W[kh][kw][cout][cin] (layers.py:352, ARU_v1.py:257)
-int pack_conv(asep_aru* m, const std::map<std::string, HostTensor>& blob, const std::string& scope,
-              const char* bias_name, bool deconv) {
-    auto wi = blob.find(scope + "/weights");
-    auto bi = blob.find(scope + "/" + bias_name);
-    if (wi == blob.end() || bi == blob.end()) {
-        set_error("weights: missing tensor %s/{weights,%s}", scope.c_str(), bias_name);
-        return ASEP_ERR_WEIGHTS;
-    }
-    const HostTensor& w = wi->second;
-    if (w.dims.size() != 4) {
-        set_error("weights: %s/weights must have rank 4", scope.c_str());
-        return ASEP_ERR_WEIGHTS;
-    }
-    PackedConv pc;
-    pc.kh = w.dims[0];
-    pc.kw = w.dims[1];
-    pc.deconv = deconv;
-    pc.cin = deconv ? w.dims[3] : w.dims[2];
-    pc.cout = deconv ? w.dims[2] : w.dims[3];
-    if ((int)bi->second.count() != pc.cout) {
-        set_error("weights: %s bias has %zu elements, expected %d", scope.c_str(), bi->second.count(), pc.cout);
-        return ASEP_ERR_WEIGHTS;
-    }
-    if (pc.cin % 4 != 0) {
-        set_error("weights: %s has Cin=%d; the MFMA path needs Cin %% 4 == 0", scope.c_str(), pc.cin);
-        return ASEP_ERR_UNSUPPORTED;
-    }
-    const int taps = pc.kh * pc.kw;
-    pc.c8 = (!deconv && pc.cin == 8);
-    pc.c12 = (!deconv && pc.cin == 12 && pc.kh == 4 && pc.kw == 4 && pc.cout <= 16 && m->use_c12);
-    pc.mtiles = cdiv(pc.cout, 16);
-    pc.groups = (pc.c8 || pc.c12) ? 1 : cdiv(pc.cin, 16);
-    pc.nchunks = pc.c8 ? (taps + 1) / 2 : (pc.c12 ? pc.kh * (pc.kw * 12 / 16) : pc.groups * taps);
-    auto W = [&](int tap, int ci, int co) -> float {
-        if (ci >= pc.cin || co >= pc.cout || tap >= taps) return 0.f;
-        return deconv ? w.data[((size_t)tap * pc.cout + co) * pc.cin + ci]
-                      : w.data[((size_t)tap * pc.cin + ci) * pc.cout + co];
-    };
-    std::vector<float> pk((size_t)pc.nchunks * pc.mtiles * 64 * 4);
-    for (int ch = 0; ch < pc.nchunks; ++ch)
-        for (int mt = 0; mt < pc.mtiles; ++mt)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int r = 0; r < 4; ++r) {
-                    const int kk = lane >> 4, co = mt * 16 + (lane & 15);
-                    int tap, ci;
-                    if (pc.c8) {
-                        tap = 2 * ch + (kk >> 1);
-                        ci = 4 * (kk & 1) + r;
-                    } else if (pc.c12) {
-                        const int cpr = pc.kw * 12 / 16, ky = ch / cpr, flat = (ch % cpr) * 16 + 4 * kk + r;   // float of the row's run
-                        tap = ky * pc.kw + flat / 12;
-                        ci = flat % 12;
-                    } else {
-                        const int g = ch / taps;
-                        tap = ch % taps;
-                        ci = 16 * g + 4 * kk + r;
-                    }
-                    pk[(((size_t)ch * pc.mtiles + mt) * 64 + lane) * 4 + r] = W(tap, ci, co);
-                }
-    int rc = upload(pk, &pc.d_w);
-    if (rc) return rc;
-    rc = upload(bi->second.data, &pc.d_b);
-    if (rc) return rc;
-    m->owned.push_back(pc.d_w);
-    m->owned.push_back(pc.d_b);
-    if (!deconv && pc.kh == 3 && pc.kw == 3 && pc.cin % 16 == 0 && pc.cout % 16 == 0) {
-        // U[a][b] = sum_ij G[a][i] g[i][j] G[b][j], G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]] (double accumulation)
-        static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-        std::vector<float> wk((size_t)pc.groups * 16 * pc.mtiles * 64 * 4);
-        for (int g = 0; g < pc.groups; ++g)
-            for (int pos = 0; pos < 16; ++pos)
-                for (int mt = 0; mt < pc.mtiles; ++mt)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int r = 0; r < 4; ++r) {
-                            const int ci = 16 * g + 4 * (lane >> 4) + r, co = mt * 16 + (lane & 15);
-                            const int ua = pos >> 2, ub = pos & 3;
-                            double u = 0;
-                            for (int i = 0; i < 3; ++i)
-                                for (int j2 = 0; j2 < 3; ++j2) u += G[ua][i] * (double)W(i * 3 + j2, ci, co) * G[ub][j2];
-                            wk[((((size_t)g * 16 + pos) * pc.mtiles + mt) * 64 + lane) * 4 + r] = (float)u;
-                        }
-        rc = upload(wk, &pc.d_wino);
-        if (rc) return rc;
-        m->owned.push_back(pc.d_wino);
-    }
-    if (deconv && pc.kh == 3 && pc.kw == 3 && pc.cin == 16 && pc.cout == 8) {
-        std::vector<float> wv;
-        for (int tap = 0; tap < 9; ++tap)
-            for (int ci = 0; ci < 16; ++ci)
-                for (int co = 0; co < 8; ++co) wv.push_back(W(tap, ci, co));
-        rc = upload(wv, &pc.d_wv);
-        if (rc) return rc;
-        m->owned.push_back(pc.d_wv);
-    }
-    if (!deconv && pc.kh == 4 && pc.kw == 4 && pc.cin == 32 && pc.cout == 1) {
-        std::vector<float> wv;
-        for (int tap = 0; tap < 16; ++tap)
-            for (int ci = 0; ci < 32; ++ci) wv.push_back(W(tap, ci, 0));
-        rc = upload(wv, &pc.d_wv);
-        if (rc) return rc;
-        m->owned.push_back(pc.d_wv);
-    }
-    if (m->bf16) {
-        rc = pack_conv_bf(m, pc, w);
-        if (rc) return rc;
-    }
-    if (m->split && !deconv) {
-        rc = pack_conv_split(m, pc, w);
-        if (rc) return rc;
-    }
-    if (m->split && deconv) {
-        rc = pack_deconv_split(m, pc, w);
-        if (rc) return rc;
-    }
-    m->convs[scope] = pc;
-    return ASEP_OK;
-}
-
-int pack_direct(asep_aru* m, const std::map<std::string, HostTensor>& blob, const std::string& scope,
-                DirectConv* dc) {
-    auto wi = blob.find(scope + "/weights");
-    auto bi = blob.find(scope + "/biases");
-    if (wi == blob.end() || bi == blob.end()) {
-        set_error("weights: missing tensor %s/{weights,biases}", scope.c_str());
-        return ASEP_ERR_WEIGHTS;
-    }
-    const HostTensor& w = wi->second;
-    if (w.dims.size() != 4 || w.dims[2] != 1 || w.dims[0] != w.dims[1]) {
-        set_error("weights: %s must be [k,k,1,cout]", scope.c_str());
-        return ASEP_ERR_UNSUPPORTED;
-    }
-    dc->k = w.dims[0];
-    dc->cout = w.dims[3];
-    int rc = upload(w.data, &dc->d_w);
-    if (rc) return rc;
-    rc = upload(bi->second.data, &dc->d_b);
-    if (rc) return rc;
-    m->owned.push_back(dc->d_w);
-    m->owned.push_back(dc->d_b);
-    return ASEP_OK;
-}
-
 struct TileDims { int tx, ty, begin; };
+
+// a schedule table on the device, owned by the handle; nullptr when it cannot be put there (the callers' contract)
+const int32_t* put_table(asep_aru* m, const std::vector<int32_t>& t) {
+    try {
+        return m->put(t);
+    } catch (const HipError&) {
+        return nullptr;
+    }
+}
 
 // XCD-aware order of the persistent fused kernels' tiles.  Workgroups are dealt round-robin to the 8 XCDs (block b
 // runs on XCD b % 8, each with its own 4 MB L2).  The tiles of every problem are first put into "super-tile" order
@@ -416,11 +278,8 @@ const int32_t* xcd_schedule(asep_aru* m, const std::vector<TileDims>& probs, int
     off[0] = 0;
     for (int x = 0; x < 8; ++x) off[x + 1] = off[x] + (total - x + 7) / 8;
     for (int k = 0; k < total; ++k) sched[k] = order[off[k % 8] + k / 8];
-    int32_t* d = nullptr;
-    if (hipMalloc((void**)&d, (size_t)total * sizeof(int32_t)) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, sched.data(), (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
-    m->owned.push_back(d);
-    m->sched_cache[key] = d;
+    const int32_t* d = put_table(m, sched);
+    if (d) m->sched_cache[key] = d;
     return d;
 }
 
@@ -850,110 +709,6 @@ TL run_pool(asep_aru* m, const TL& in, PoolKind kind) {
 
 int grid_1d(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 256 * 8); }
 
-// pixel-pair A fragments of a 3x3 conv with 8 input channels starting at input channel ci0 of W[3][3][cin][8]:
-// rows = (pixel parity e, cout), chunk = (ky, h), slot s: kx' = 2h + (s>>3), ci = s&7, kx = kx' - e
-void pack_pair8(const HostTensor& w, int cin, int ci0, std::vector<float>& dst) {
-    for (int ky = 0; ky < 3; ++ky)
-        for (int h = 0; h < 2; ++h)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int r = 0; r < 4; ++r) {
-                    const int row = lane & 15, kk = lane >> 4, s = 4 * kk + r;
-                    const int e = row >> 3, co = row & 7;
-                    const int kx = 2 * h + (s >> 3) - e, ci = s & 7;
-                    float v = 0.f;
-                    if (kx >= 0 && kx <= 2) v = w.data[(((size_t)ky * 3 + kx) * cin + ci0 + ci) * 8 + co];
-                    dst.push_back(v);
-                }
-}
-
-// scalar layout of a 3x3 conv with 8 input channels starting at input channel ci0 of W[3][3][cin][8] (res8v_kernels.h).
-// Direct: [g = (ky*2 + hf)*3 + kx][c][co], input channel ci0 + hf*4 + c.  Winograd F(2,3) along x: [(ky*2 + hf)*4 + j][c][co],
-// U_j = sum_kx G[j][kx] g[ky][kx], G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]] (double accumulation)
-void pack_scalar8(const HostTensor& w, int cin, int ci0, std::vector<float>& dst) {
-    auto W = [&](int ky, int kx, int ci, int co) { return (double)w.data[(((size_t)ky * 3 + kx) * cin + ci0 + ci) * 8 + co]; };
-    if (R8V_WINO) {
-        static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-        for (int rh = 0; rh < 6; ++rh)
-            for (int j = 0; j < 4; ++j)
-                for (int c = 0; c < 4; ++c)
-                    for (int co = 0; co < 8; ++co) {
-                        double u = 0;
-                        for (int kx = 0; kx < 3; ++kx) u += G[j][kx] * W(rh >> 1, kx, (rh & 1) * 4 + c, co);
-                        dst.push_back((float)u);
-                    }
-        return;
-    }
-    for (int g = 0; g < 18; ++g) {
-        const int ky = g / 6, hf = (g / 3) % 2, kx = g % 3;
-        for (int c = 0; c < 4; ++c)
-            for (int co = 0; co < 8; ++co) dst.push_back((float)W(ky, kx, hf * 4 + c, co));
-    }
-}
-
-int pack_res8(asep_aru* m, const std::map<std::string, HostTensor>& blob) {
-    const std::string s = "aru_net/featMapG/unet_down_0";
-    std::vector<float> wr, br, vwr;
-    for (int r = 0; r < 3; ++r) {
-        auto wi = blob.find(s + "/convR_" + std::to_string(r) + "/weights");
-        auto bi = blob.find(s + "/convR_" + std::to_string(r) + "/biases");
-        if (wi == blob.end() || bi == blob.end()) { set_error("weights: missing %s/convR_%d", s.c_str(), r); return ASEP_ERR_WEIGHTS; }
-        pack_pair8(wi->second, 8, 0, wr);
-        pack_scalar8(wi->second, 8, 0, vwr);
-        br.insert(br.end(), bi->second.data.begin(), bi->second.data.end());
-    }
-    int rc = upload(wr, &m->d_r8_down_wr);
-    if (!rc) rc = upload(br, &m->d_r8_down_br);
-    if (!rc) rc = upload(vwr, &m->d_r8v_down_wr);
-    if (rc) return rc;
-    m->owned.push_back(m->d_r8_down_wr);
-    m->owned.push_back(m->d_r8_down_br);
-    m->owned.push_back(m->d_r8v_down_wr);
-    if (m->cfg.scale_space_num > 1) {
-        const std::string u = "aru_net/featMapG/unet_up_0";
-        auto w1 = blob.find(u + "/conv1/weights");
-        auto b1 = blob.find(u + "/conv1/biases");
-        if (w1 == blob.end() || b1 == blob.end()) { set_error("weights: missing %s/conv1", u.c_str()); return ASEP_ERR_WEIGHTS; }
-        std::vector<float> pw1, pwr, pbr, vw1, vwr2;
-        pack_pair8(w1->second, 16, 0, pw1);      // skip channels 0..7
-        pack_pair8(w1->second, 16, 8, pw1);      // deconv channels 8..15
-        pack_scalar8(w1->second, 16, 0, vw1);
-        pack_scalar8(w1->second, 16, 8, vw1);
-        for (int r = 0; r < 3; ++r) {
-            auto wi = blob.find(u + "/convR_" + std::to_string(r) + "/weights");
-            auto bi = blob.find(u + "/convR_" + std::to_string(r) + "/biases");
-            if (wi == blob.end() || bi == blob.end()) { set_error("weights: missing %s/convR_%d", u.c_str(), r); return ASEP_ERR_WEIGHTS; }
-            pack_pair8(wi->second, 8, 0, pwr);
-            pack_scalar8(wi->second, 8, 0, vwr2);
-            pbr.insert(pbr.end(), bi->second.data.begin(), bi->second.data.end());
-        }
-        rc = upload(pw1, &m->d_r8_up_w1);
-        if (!rc) rc = upload(pwr, &m->d_r8_up_wr);
-        if (!rc) rc = upload(pbr, &m->d_r8_up_br);
-        if (!rc) rc = upload(b1->second.data, &m->d_r8_up_b1);
-        if (!rc) rc = upload(vw1, &m->d_r8v_up_w1);
-        if (!rc) rc = upload(vwr2, &m->d_r8v_up_wr);
-        if (rc) return rc;
-        m->owned.push_back(m->d_r8v_up_w1); m->owned.push_back(m->d_r8v_up_wr);
-        m->owned.push_back(m->d_r8_up_w1); m->owned.push_back(m->d_r8_up_wr);
-        m->owned.push_back(m->d_r8_up_br); m->owned.push_back(m->d_r8_up_b1);
-        if (hipFuncSetAttribute((const void*)res8_up_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R8_UP_LDS) != hipSuccess ||
-            hipFuncSetAttribute((const void*)res8v_up_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R8_UP_LDS) != hipSuccess ||
-            hipFuncSetAttribute((const void*)res8v_up_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R8_UP_LDS) != hipSuccess ||
-            hipFuncSetAttribute((const void*)res8v_up_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R8_UP_LDS) != hipSuccess) {
-            set_error("cannot reserve %zu bytes of LDS for the fused up block", R8_UP_LDS);
-            return ASEP_ERR_HIP;
-        }
-    }
-    if (hipFuncSetAttribute((const void*)res8_down_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R8_DOWN_LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)res8v_down_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R8_DOWN_LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)res8v_down_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R8_DOWN_LDS) != hipSuccess ||
-        hipFuncSetAttribute((const void*)res8v_down_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R8_DOWN_LDS) != hipSuccess) {
-        set_error("cannot reserve %zu bytes of LDS for the fused residual block", R8_DOWN_LDS);
-        return ASEP_ERR_HIP;
-    }
-    return ASEP_OK;
-}
-
 // the profiler's layer text of a level-0 block over the pages `l`
 std::string res8_what(bool up, const TL& l) {
     return (up ? "unet_up_0 (conv1[16->8]+3xconvR+add) " : "unet_down_0 (conv1+3xconvR+add+pool) ") + dims_of(l);
@@ -979,11 +734,9 @@ const int32_t* r8ws_frame_units(asep_aru* m, const Res8Args& a, const std::vecto
     *count = (int)units.size();
     auto it = m->sched_cache.find(key);
     if (it != m->sched_cache.end()) return it->second;
-    int32_t* d = nullptr;
-    if (units.empty() || hipMalloc((void**)&d, units.size() * sizeof(int32_t)) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, units.data(), units.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
-    m->owned.push_back(d);
-    m->sched_cache[key] = d;
+    if (units.empty()) return nullptr;
+    const int32_t* d = put_table(m, units);
+    if (d) m->sched_cache[key] = d;
     return d;
 }
 
@@ -1103,367 +856,8 @@ void run_res8(asep_aru* m, bool up, const TL& in0, const TL* in1, const std::vec
 }
 
 // ================================================================================================
-// Native bf16 data path (cfg.compute_dtype == 1): packing and launchers of bf16_kernels.h
+// Native bf16 data path (cfg.compute_dtype == 1): launchers of bf16_kernels.h
 // ================================================================================================
-bf16_t f2bf(float f) {                                 // round-to-nearest-even like v_cvt_pk_bf16_f32 (weights have no NaN)
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (bf16_t)(u >> 16);
-}
-
-int upload_bf(const std::vector<bf16_t>& h, bf16_t** d) {
-    ASEP_HIP_CHECK(hipMalloc((void**)d, std::max<size_t>(h.size(), 8) * sizeof(bf16_t)));
-    ASEP_HIP_CHECK(hipMemcpy(*d, h.data(), h.size() * sizeof(bf16_t), hipMemcpyHostToDevice));
-    return ASEP_OK;
-}
-
-// A fragments of a conv for convb_kernel / resb_tail_kernel.  W(tap, ci, co) = weight or 0 outside the filter.
-// mode 0: chunk = ky, k = 8 kx + ci (kx = 3: zero);  mode 1: chunk c, k = 16 (tap - 2c) + ci;  mode 2: chunk = G taps + tap, k = ci - 32 G
-template <class WF>
-void pack_frags_conv(int mode, int kh, int kw, int cin, int mtiles, WF W, std::vector<bf16_t>& dst, int* nchunks) {
-    const int taps = kh * kw;
-    const int chunks = mode == 0 ? kh : (mode == 1 ? (taps + 1) / 2 : (cin / 32) * taps);
-    *nchunks = chunks;
-    for (int ch = 0; ch < chunks; ++ch)
-        for (int mt = 0; mt < mtiles; ++mt)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int kk = lane >> 4, co = mt * 16 + (lane & 15);
-                    int tap, ci;
-                    if (mode == 0) { tap = kk < kw ? ch * kw + kk : -1; ci = j; }
-                    else if (mode == 1) { tap = 2 * ch + (kk >> 1); ci = (kk & 1) * 8 + j; if (tap >= taps) tap = -1; }
-                    else { const int G = ch / taps; tap = ch % taps; ci = 32 * G + kk * 8 + j; }
-                    dst.push_back(f2bf(tap < 0 ? 0.f : W(tap, ci, co)));
-                }
-}
-
-int conv_bmode(int cin) { return cin == 8 ? 0 : (cin == 16 ? 1 : (cin % 32 == 0 ? 2 : -1)); }
-
-// bf16 fragments of one packed conv / deconv (called from pack_conv when the model is bf16)
-int pack_conv_bf(asep_aru* m, PackedConv& pc, const HostTensor& w) {
-    const int taps = pc.kh * pc.kw;
-    auto W = [&](int tap, int ci, int co) -> float {
-        if (ci >= pc.cin || co >= pc.cout || tap >= taps) return 0.f;
-        return pc.deconv ? w.data[((size_t)tap * pc.cout + co) * pc.cin + ci] : w.data[((size_t)tap * pc.cin + ci) * pc.cout + co];
-    };
-    std::vector<bf16_t> pk;
-    if (!pc.deconv) {
-        // the 12-channel output of the attention head is stored as a 16-channel plane (4 zero channels): Cin 12 -> mode 1
-        const int cin_eff = pc.cin == 12 ? 16 : pc.cin;
-        pc.bmode = conv_bmode(cin_eff);
-        if (pc.bmode < 0 || (pc.bmode == 0 && pc.kh != 3)) return ASEP_OK;      // not served by convb (refused at run time if it is needed)
-        pack_frags_conv(pc.bmode, pc.kh, pc.kw, cin_eff, pc.mtiles, W, pk, &pc.bchunks);
-    } else {
-        pc.bmode = pc.cin == 16 ? 1 : (pc.cin % 32 == 0 ? 2 : -1);
-        if (pc.bmode < 0 || pc.kh != 3 || pc.kw != 3) { pc.bmode = -1; return ASEP_OK; }
-        if (pc.bmode == 2) {
-            const int G = pc.cin / 32;
-            pc.bchunks = G * 9;
-            for (int g = 0; g < G; ++g)
-                for (int tap = 0; tap < 9; ++tap)
-                    for (int mt = 0; mt < pc.mtiles; ++mt)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int j = 0; j < 8; ++j)
-                                pk.push_back(f2bf(W(tap, 32 * g + (lane >> 4) * 8 + j, mt * 16 + (lane & 15))));
-        } else {
-            // fragment f: dy = f >= 4; class (py, px) = dy ? (0, f & 1) : (f >> 1, f & 1); k = 16 dx + ci
-            pc.bchunks = 6;
-            for (int f = 0; f < 6; ++f)
-                for (int mt = 0; mt < pc.mtiles; ++mt)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const int kk = lane >> 4, dx = kk >> 1, ci = (kk & 1) * 8 + j, co = mt * 16 + (lane & 15);
-                            const int dy = f >= 4, py = dy ? 0 : (f >> 1), px = f & 1;
-                            const int ky = py ? 1 : (dy ? 2 : 0);
-                            const int kx = px ? (dx ? -1 : 1) : (dx ? 2 : 0);
-                            pk.push_back(f2bf(kx < 0 ? 0.f : W(ky * 3 + kx, ci, co)));
-                        }
-        }
-    }
-    int rc = upload_bf(pk, &pc.d_wb);
-    if (rc) return rc;
-    m->owned.push_back(pc.d_wb);
-    if (pc.deconv && pc.bmode == 1 && pc.cout == 8) {
-        // deconvb8_kernel: fragment q = (dy = 0, py = 0), (dy = 0, py = 1), (dy = 1, py = 0); row m = 8 px + co; k = 16 dx + ci
-        std::vector<bf16_t> p8;
-        for (int q = 0; q < 3; ++q)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int kk = lane >> 4, dx = kk >> 1, ci = (kk & 1) * 8 + j, mrow = lane & 15, px = mrow >> 3, co = mrow & 7;
-                    const int dy = q == 2, py = q == 1;
-                    const int ky = py ? 1 : (dy ? 2 : 0);
-                    const int kx = px ? (dx ? -1 : 1) : (dx ? 2 : 0);
-                    p8.push_back(f2bf(kx < 0 ? 0.f : W(ky * 3 + kx, ci, co)));
-                }
-        rc = upload_bf(p8, &pc.d_wb8);
-        if (rc) return rc;
-        m->owned.push_back(pc.d_wb8);
-    }
-    return ASEP_OK;
-}
-
-// fp32 filter -> its three bfloat16 parts (round to nearest at every cut: w = h + m + l exactly), in convs_kernel's fragment order
-int pack_conv_split(asep_aru* m, PackedConv& pc, const HostTensor& w) {
-    const int taps = pc.kh * pc.kw;
-    if (!((pc.kh == 3 && pc.kw == 3) || (pc.kh == 4 && pc.kw == 4)) || pc.cout % 16 != 0) return ASEP_OK;
-    pc.smode = (pc.cin == 16 || pc.cin == 12) ? 1 : (pc.cin % 32 == 0 ? 2 : -1);
-    if (pc.smode == 2 && pc.kh != 3) pc.smode = -1;          // 4x4 filters are instantiated for the 12- / 16-channel form only: such a layer keeps the fp32 MFMA kernel
-    if (pc.smode < 0) return ASEP_OK;
-    auto W = [&](int tap, int ci, int co) -> float {
-        if (ci >= pc.cin || co >= pc.cout || tap >= taps) return 0.f;
-        return w.data[((size_t)tap * pc.cin + ci) * pc.cout + co];
-    };
-    auto bfval = [](bf16_t b) { uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; };
-    const int chunks = pc.smode == 1 ? (taps + 1) / 2 : (pc.cin / 32) * taps;
-    std::vector<bf16_t> pk((size_t)chunks * 3 * pc.mtiles * 64 * 8);
-    for (int ch = 0; ch < chunks; ++ch)
-        for (int mt = 0; mt < pc.mtiles; ++mt)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int kk = lane >> 4, co = mt * 16 + (lane & 15);
-                    int tap, ci;
-                    if (pc.smode == 1) { tap = 2 * ch + (kk >> 1); ci = (kk & 1) * 8 + j; if (tap >= taps) tap = -1; }
-                    else { const int G = ch / taps; tap = ch % taps; ci = 32 * G + kk * 8 + j; }
-                    const float v = tap < 0 ? 0.f : W(tap, ci, co);
-                    const bf16_t h = f2bf(v);
-                    const float r = v - bfval(h);
-                    const bf16_t mm = f2bf(r);
-                    const bf16_t l = f2bf(r - bfval(mm));
-                    const bf16_t part[3] = {h, mm, l};
-                    for (int s = 0; s < 3; ++s) pk[((((size_t)ch * 3 + s) * pc.mtiles + mt) * 64 + lane) * 8 + j] = part[s];
-                }
-    int rc = upload_bf(pk, &pc.d_ws);
-    if (rc) return rc;
-    m->owned.push_back(pc.d_ws);
-    if (pc.kh == 3 && pc.kw == 3 && pc.cin % 16 == 0 && pc.cin >= 32) {
-        const int stages = pc.cin / 16;
-        std::vector<bf16_t> pk16((size_t)stages * 5 * 3 * pc.mtiles * 64 * 8);
-        for (int g = 0; g < stages; ++g)
-            for (int t = 0; t < 5; ++t)
-                for (int mt = 0; mt < pc.mtiles; ++mt)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const int kk = lane >> 4, co = mt * 16 + (lane & 15);
-                            const int tap = 2 * t + (kk >> 1), ci = 16 * g + (kk & 1) * 8 + j;
-                            const float v = tap < taps ? W(tap, ci, co) : 0.f;
-                            const bf16_t h = f2bf(v);
-                            const float r = v - bfval(h);
-                            const bf16_t mm = f2bf(r);
-                            const bf16_t part[3] = {h, mm, f2bf(r - bfval(mm))};
-                            for (int s = 0; s < 3; ++s)
-                                pk16[(((((size_t)g * 5 + t) * 3 + s) * pc.mtiles + mt) * 64 + lane) * 8 + j] = part[s];
-                        }
-        rc = upload_bf(pk16, &pc.d_ws16);
-        if (rc) return rc;
-        m->owned.push_back(pc.d_ws16);
-    }
-    return ASEP_OK;
-}
-
-// a 3x3 deconvolution filter with Cin % 32 == 0 as three bfloat16 parts for deconvs_kernel: [stage of 32 channels][tap][part h, m, l][m-tile][lane][8]
-int pack_deconv_split(asep_aru* m, PackedConv& pc, const HostTensor& w) {
-    if (pc.kh != 3 || pc.kw != 3 || pc.cin % 32 != 0 || pc.cout % 16 != 0) return ASEP_OK;      // (level 0, 16 -> 8: deconv8v_kernel)
-    auto W = [&](int tap, int ci, int co) -> float { return w.data[((size_t)tap * pc.cout + co) * pc.cin + ci]; };
-    auto bfval = [](bf16_t b) { uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; };
-    const int G = pc.cin / 32;
-    std::vector<bf16_t> pk((size_t)G * 9 * 3 * pc.mtiles * 64 * 8);
-    for (int g = 0; g < G; ++g)
-        for (int tap = 0; tap < 9; ++tap)
-            for (int mt = 0; mt < pc.mtiles; ++mt)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const float v = W(tap, 32 * g + (lane >> 4) * 8 + j, mt * 16 + (lane & 15));
-                        const bf16_t h = f2bf(v);
-                        const float r = v - bfval(h);
-                        const bf16_t mm = f2bf(r);
-                        const bf16_t part[3] = {h, mm, f2bf(r - bfval(mm))};
-                        for (int s = 0; s < 3; ++s) pk[(((((size_t)g * 9 + tap) * 3 + s) * pc.mtiles + mt) * 64 + lane) * 8 + j] = part[s];
-                    }
-    int rc = upload_bf(pk, &pc.d_ws);
-    if (rc) return rc;
-    m->owned.push_back(pc.d_ws);
-    pc.smode = 2;
-    return ASEP_OK;
-}
-
-// the three convR filters of a residual block for resb_tail_kernel<C>: [3][CPC][64][8] + biases [3][C]
-int pack_resb(asep_aru* m, const std::map<std::string, HostTensor>& blob, const std::string& scope, int C) {
-    std::vector<bf16_t> pk;
-    std::vector<float> br;
-    for (int r = 0; r < 3; ++r) {
-        auto wi = blob.find(scope + "/convR_" + std::to_string(r) + "/weights");
-        auto bi = blob.find(scope + "/convR_" + std::to_string(r) + "/biases");
-        if (wi == blob.end() || bi == blob.end()) { set_error("weights: missing %s/convR_%d", scope.c_str(), r); return ASEP_ERR_WEIGHTS; }
-        const HostTensor& w = wi->second;
-        if (w.dims.size() != 4 || w.dims[0] != 3 || w.dims[1] != 3 || w.dims[2] != C || w.dims[3] != C) return ASEP_OK;   // not this shape: layer-by-layer
-        auto W = [&](int tap, int ci, int co) -> float { return (ci < C && co < C) ? w.data[((size_t)tap * C + ci) * C + co] : 0.f; };
-        int nch = 0;
-        if (C == 32) pack_frags_conv(2, 3, 3, 32, 2, W, pk, &nch);          // [9 taps][2 m-tiles][64 lanes] (res32_tail_kernel)
-        else pack_frags_conv(C == 8 ? 0 : 1, 3, 3, C, 1, W, pk, &nch);
-        br.insert(br.end(), bi->second.data.begin(), bi->second.data.end());
-    }
-    asep_aru::ResB rb;
-    rb.C = C;
-    int rc = upload_bf(pk, &rb.d_w);
-    if (!rc) rc = upload(br, &rb.d_b);
-    if (rc) return rc;
-    m->owned.push_back(rb.d_w);
-    m->owned.push_back(rb.d_b);
-    m->resb[scope] = rb;
-    return ASEP_OK;
-}
-
-// pixel-pair A fragments of a 3x3 conv with 8 output channels for res8b_kernel: row m = (pixel parity e, cout), one fragment
-// per filter row (and per half of the 4-pixel window when there are 16 input channels): k = 8 kk + j.
-//   cin 8:  window pixel p = kk, ci = j;   cin 16: window pixel p = 2 half + (kk >> 1), ci = 8 (kk & 1) + j;   kx = p - e
-void pack_pair_frags(const HostTensor& w, int cin, std::vector<bf16_t>& dst) {
-    const int halves = cin == 16 ? 2 : 1;
-    for (int ky = 0; ky < 3; ++ky)
-        for (int hf = 0; hf < halves; ++hf)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int m = lane & 15, kk = lane >> 4, e = m >> 3, co = m & 7;
-                    const int p = cin == 16 ? 2 * hf + (kk >> 1) : kk;
-                    const int ci = cin == 16 ? (kk & 1) * 8 + j : j;
-                    const int kx = p - e;
-                    dst.push_back(f2bf((kx >= 0 && kx <= 2) ? w.data[(((size_t)ky * 3 + kx) * cin + ci) * 8 + co] : 0.f));
-                }
-}
-
-// three-part pair fragments of the 8 input channels ci0 .. ci0 + 7 of a 3 x 3 filter W[3][3][cin][8], one filter row: [part 3][64 lanes][8]
-// (res8ws_kernels.h; the pair-window mapping of pack_pair_frags, the cut of pack_conv_split)
-void pack_pair_split(const HostTensor& w, int cin, int ci0, int ky, std::vector<bf16_t>& dst) {
-    auto bfval = [](bf16_t b) { uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; };
-    std::vector<bf16_t> part[3];
-    for (int lane = 0; lane < 64; ++lane)
-        for (int i = 0; i < 8; ++i) {
-            const int mr = lane & 15, kk = lane >> 4, e = mr >> 3, co = mr & 7, kx = kk - e;
-            const float v = (kx >= 0 && kx <= 2) ? w.data[(((size_t)ky * 3 + kx) * cin + ci0 + i) * 8 + co] : 0.f;
-            const bf16_t h = f2bf(v);
-            const float r = v - bfval(h);
-            const bf16_t mm = f2bf(r);
-            part[0].push_back(h); part[1].push_back(mm); part[2].push_back(f2bf(r - bfval(mm)));
-        }
-    for (int p = 0; p < 3; ++p) dst.insert(dst.end(), part[p].begin(), part[p].end());
-}
-
-// the split-product walkers' filters (f32s engine): both level-0 tails and the UP block's conv1; left unset (the walkers off) for other shapes
-int pack_res8ws(asep_aru* m, const std::map<std::string, HostTensor>& blob) {
-    auto tail = [&](const std::string& scope, std::vector<bf16_t>& pk) -> bool {
-        for (int r = 0; r < 3; ++r) {
-            auto wi = blob.find(scope + "/convR_" + std::to_string(r) + "/weights");
-            if (wi == blob.end()) return false;
-            const HostTensor& w = wi->second;
-            if (w.dims.size() != 4 || w.dims[0] != 3 || w.dims[1] != 3 || w.dims[2] != 8 || w.dims[3] != 8) return false;
-            for (int ky = 0; ky < 3; ++ky) pack_pair_split(w, 8, 0, ky, pk);
-        }
-        return true;
-    };
-    std::vector<bf16_t> dw, uw, u1;
-    if (!tail("aru_net/featMapG/unet_down_0", dw)) return ASEP_OK;
-    if (m->cfg.scale_space_num > 1) {
-        const std::string u = "aru_net/featMapG/unet_up_0";
-        auto w1 = blob.find(u + "/conv1/weights");
-        if (!tail(u, uw) || w1 == blob.end()) return ASEP_OK;
-        const HostTensor& w = w1->second;
-        if (w.dims.size() != 4 || w.dims[0] != 3 || w.dims[1] != 3 || w.dims[2] != 16 || w.dims[3] != 8) return ASEP_OK;
-        for (int ky = 0; ky < 3; ++ky)
-            for (int src = 0; src < 2; ++src) pack_pair_split(w, 16, 8 * src, ky, u1);
-        int rc = upload_bf(uw, &m->d_r8ws_up_w);
-        if (rc) return rc;
-        m->owned.push_back(m->d_r8ws_up_w);
-        rc = upload_bf(u1, &m->d_r8ws_up_w1);
-        if (rc) return rc;
-        m->owned.push_back(m->d_r8ws_up_w1);
-    }
-    int rc = upload_bf(dw, &m->d_r8ws_down_w);
-    if (rc) return rc;
-    m->owned.push_back(m->d_r8ws_down_w);
-    return ASEP_OK;
-}
-
-int pack_res8b(asep_aru* m, const std::map<std::string, HostTensor>& blob) {
-    auto tail = [&](const std::string& scope, bf16_t** d_w, float** d_b) -> int {
-        std::vector<bf16_t> pk;
-        std::vector<float> br;
-        for (int r = 0; r < 3; ++r) {
-            auto wi = blob.find(scope + "/convR_" + std::to_string(r) + "/weights");
-            auto bi = blob.find(scope + "/convR_" + std::to_string(r) + "/biases");
-            if (wi == blob.end() || bi == blob.end()) { set_error("weights: missing %s/convR_%d", scope.c_str(), r); return ASEP_ERR_WEIGHTS; }
-            const HostTensor& w = wi->second;
-            if (w.dims.size() != 4 || w.dims[0] != 3 || w.dims[1] != 3 || w.dims[2] != 8 || w.dims[3] != 8) return 1;   // other shape: generic kernels
-            pack_pair_frags(w, 8, pk);
-            br.insert(br.end(), bi->second.data.begin(), bi->second.data.end());
-        }
-        int rc = upload_bf(pk, d_w);
-        if (!rc) rc = upload(br, d_b);
-        if (rc) return rc;
-        m->owned.push_back(*d_w);
-        m->owned.push_back(*d_b);
-        return ASEP_OK;
-    };
-    int rc = tail("aru_net/featMapG/unet_down_0", &m->d_r8b_down_w, &m->d_r8b_down_b);
-    if (rc == 1) { m->d_r8b_down_w = nullptr; return ASEP_OK; }
-    if (rc) return rc;
-    {
-        // conv1 (1 -> 8) as one pair fragment: row m = (parity e, cout); k = 8 kk + jj: window row 2 kk + (jj >> 2) (kk < 2), column jj & 3
-        auto w1 = blob.find("aru_net/featMapG/unet_down_0/conv1/weights");
-        if (w1 != blob.end() && w1->second.dims.size() == 4 && w1->second.dims[0] == 3 && w1->second.dims[1] == 3 && w1->second.dims[2] == 1 &&
-            w1->second.dims[3] == 8) {
-            std::vector<bf16_t> pk;
-            for (int lane = 0; lane < 64; ++lane)
-                for (int jj = 0; jj < 8; ++jj) {
-                    const int mrow = lane & 15, kk = lane >> 4, e = mrow >> 3, co = mrow & 7;
-                    const int ky = 2 * kk + (jj >> 2), kx = (jj & 3) - e;
-                    pk.push_back(f2bf((kk < 2 && ky <= 2 && kx >= 0 && kx <= 2) ? w1->second.data[(size_t)(ky * 3 + kx) * 8 + co] : 0.f));
-                }
-            rc = upload_bf(pk, &m->d_r8f_down_w1);
-            if (rc) return rc;
-            m->owned.push_back(m->d_r8f_down_w1);
-            std::vector<float> wr(w1->second.data.size());
-            for (size_t i = 0; i < wr.size(); ++i) {
-                const uint32_t u = (uint32_t)f2bf(w1->second.data[i]) << 16;
-                memcpy(&wr[i], &u, 4);
-            }
-            rc = upload(wr, &m->d_r8b_down_w1r);
-            if (rc) return rc;
-            m->owned.push_back(m->d_r8b_down_w1r);
-        }
-    }
-    if (m->cfg.scale_space_num > 1) {
-        const std::string u = "aru_net/featMapG/unet_up_0";
-        auto w1 = blob.find(u + "/conv1/weights");
-        auto b1 = blob.find(u + "/conv1/biases");
-        if (w1 == blob.end() || b1 == blob.end()) { set_error("weights: missing %s/conv1", u.c_str()); return ASEP_ERR_WEIGHTS; }
-        const HostTensor& w = w1->second;
-        if (w.dims.size() != 4 || w.dims[0] != 3 || w.dims[1] != 3 || w.dims[2] != 16 || w.dims[3] != 8) return ASEP_OK;
-        rc = tail(u, &m->d_r8b_up_w, &m->d_r8b_up_b);
-        if (rc == 1) { m->d_r8b_up_w = nullptr; return ASEP_OK; }
-        if (rc) return rc;
-        std::vector<bf16_t> pk;
-        pack_pair_frags(w, 16, pk);
-        rc = upload_bf(pk, &m->d_r8b_up_w1);
-        if (!rc) rc = upload(b1->second.data, &m->d_r8b_up_b1);
-        if (rc) return rc;
-        m->owned.push_back(m->d_r8b_up_w1);
-        m->owned.push_back(m->d_r8b_up_b1);
-        // res8f_kernel (interior tiles) keeps skip and deconv as two 16-byte planes: fragment (ky, source), k = 8 kk + j <-> window pixel kk, channel 8 source + j
-        std::vector<bf16_t> pf;
-        for (int ky = 0; ky < 3; ++ky)
-            for (int src = 0; src < 2; ++src)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int mrow = lane & 15, kk = lane >> 4, e = mrow >> 3, co = mrow & 7, kx = kk - e;
-                        pf.push_back(f2bf((kx >= 0 && kx <= 2) ? w.data[(((size_t)ky * 3 + kx) * 16 + src * 8 + j) * 8 + co] : 0.f));
-                    }
-        rc = upload_bf(pf, &m->d_r8f_up_w1);
-        if (rc) return rc;
-        m->owned.push_back(m->d_r8f_up_w1);
-    }
-    return ASEP_OK;
-}
-
 Tensor new_tensor_bf(asep_aru* m, int H, int W, int C);
 void run_res8b_tiles(asep_aru* m, bool up, const TL& a0, const TL* a1, const std::vector<const float*>& stats, bool want_pool, const TL& outs, const TL* pool_out);
 
@@ -2465,6 +1859,136 @@ int aru_num_classes(const asep_aru* m) { return m ? m->cfg.n_classes : -1; }
 
 }  // namespace asep
 
+// ---- weights at load time: which packed vector (aru_pack.h) goes into which member, under which cfg and switch -------------------
+namespace {
+
+void load_conv(asep_aru* m, const WeightBlob& blob, const std::string& scope, const char* bias_name = "biases", bool deconv = false) {
+    const Layer L = find_layer(blob, scope, bias_name);
+    const ConvPack c = pack_conv_layer(scope, L, deconv, m->use_c12, m->bf16, m->split);
+    PackedConv pc;
+    static_cast<ConvPlan&>(pc) = c.plan;
+    pc.d_w = m->put(c.w);
+    pc.d_b = m->put(L.b.data);
+    pc.d_wino = m->put_some(c.wino);
+    pc.d_wv = m->put_some(c.wv);
+    pc.d_wb = m->put_some(c.wb);
+    pc.d_wb8 = m->put_some(c.wb8);
+    pc.d_ws = m->put_some(c.ws);
+    pc.d_ws16 = m->put_some(c.ws16);
+    m->convs[scope] = pc;
+}
+
+void load_direct(asep_aru* m, const WeightBlob& blob, const std::string& scope, DirectConv* dc) {
+    const Layer L = find_direct(blob, scope);
+    dc->k = L.w.dims[0];
+    dc->cout = L.w.dims[3];
+    dc->d_w = m->put(L.w.data);
+    dc->d_b = m->put(L.b.data);
+}
+
+// dynamic LDS of a fused block's kernels
+void reserve_lds(std::initializer_list<const void*> kernels, size_t bytes, const char* what) {
+    for (const void* k : kernels)
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+            set_error("cannot reserve %zu bytes of LDS for the fused %s block", bytes, what);
+            throw HipError();
+        }
+}
+
+void load_weights(asep_aru* m, const WeightBlob& blob, bool variant) {
+    const asep_aru_cfg* cfg = &m->cfg;
+    const int n = cfg->scale_space_num;
+    const bool up = n > 1;
+    if (cfg->use_attention) {
+        load_direct(m, blob, "aru_net/attMapG/attPart/conv1", &m->att_first);
+        if (m->att_first.k == 4 && m->att_first.cout == 12) {
+            const FilterView W(blob.find("aru_net/attMapG/attPart/conv1/weights")->second);   // [4][4][1][12]
+            m->d_att_head = m->put(pack_att_head(W));
+            if (m->bf16) m->d_att_headb = m->put(pack_att_headb(W));
+        }
+        for (int i = 2; i <= 4; ++i) load_conv(m, blob, "aru_net/attMapG/attPart/conv" + std::to_string(i));
+    }
+    load_direct(m, blob, "aru_net/featMapG/unet_down_0/conv1", &m->det_first);
+    for (int l = 0; l < n; ++l) {
+        const std::string s = "aru_net/featMapG/unet_down_" + std::to_string(l);
+        if (l > 0) load_conv(m, blob, s + "/conv1");
+        if (cfg->plain_u) { load_conv(m, blob, s + "/conv2"); continue; }
+        for (int r = 0; r < cfg->res_depth; ++r) load_conv(m, blob, convR(s, r));
+    }
+    for (int l = n - 2; l >= 0; --l) {
+        const std::string s = "aru_net/featMapG/unet_up_" + std::to_string(l);
+        load_conv(m, blob, s + "/deconv", "bias", true);
+        load_conv(m, blob, s + "/conv1");
+        if (cfg->plain_u) { load_conv(m, blob, s + "/conv2"); continue; }
+        for (int r = 0; r < cfg->res_depth; ++r) load_conv(m, blob, convR(s, r));
+    }
+    // fused level-0 residual blocks of the fp32 engines (res8_kernels.h, res8v_kernels.h)
+    if ((!variant || m->fused8_var) && !m->bf16 && cfg->feat_root == 8 && cfg->res_depth == 3 && m->det_first.k == 3) {
+        const Res8Pack p = pack_res8(blob, up, R8V_WINO);
+        m->d_r8_down_wr = m->put(p.down_wr);
+        m->d_r8_down_br = m->put(p.down_br);
+        m->d_r8v_down_wr = m->put(p.v_down_wr);
+        if (up) {
+            m->d_r8_up_w1 = m->put(p.up_w1);
+            m->d_r8_up_wr = m->put(p.up_wr);
+            m->d_r8_up_br = m->put(p.up_br);
+            m->d_r8_up_b1 = m->put(p.up_b1);
+            m->d_r8v_up_w1 = m->put(p.v_up_w1);
+            m->d_r8v_up_wr = m->put(p.v_up_wr);
+            reserve_lds({(const void*)res8_up_kernel<false>, (const void*)res8v_up_kernel<0>, (const void*)res8v_up_kernel<1>, (const void*)res8v_up_kernel<2>},
+                        R8_UP_LDS, "up");
+        }
+        reserve_lds({(const void*)res8_down_kernel<false>, (const void*)res8v_down_kernel<0>, (const void*)res8v_down_kernel<1>, (const void*)res8v_down_kernel<2>},
+                    R8_DOWN_LDS, "residual");
+    }
+    if (m->split && !variant && m->d_r8_down_wr) {           // f32s, ReLU graph: the split-product strip walkers (left unset for other shapes)
+        const Res8wsPack p = pack_res8ws(blob, up);
+        m->d_r8ws_up_w = m->put_some(p.up_w);
+        m->d_r8ws_up_w1 = m->put_some(p.up_w1);
+        m->d_r8ws_down_w = m->put_some(p.down_w);
+    }
+    // (bf16 path, elu / leaky / 'U' graphs -- round 5: layer by layer on convb_kernel / deconvb_kernel with the activation in their general
+    //  epilogues; the fused blocks below bake the ReLU into packed-bf16 maxima and serve the ReLU residual graphs)
+    // (round 6: the elu / leaky RESIDUAL graphs take the GENERAL fused forms of the 8- and 16-channel levels -- res8b_tile / resb_tail_tile apply the
+    //  activation to fp32 values and take float maxima in their pools, a template parameter serves them; the 32-channel tail the same way; the lean forms and
+    //  the walkers stay the ReLU graphs')
+    m->fused_act = (m->bf16 && variant && !cfg->plain_u && cfg->activation != 0 && m->fused8_wanted && m->fuse_act) ? cfg->activation : 0;
+    const bool fusedb = m->bf16 && (!variant || m->fused_act);
+    if (fusedb && cfg->res_depth == 3 && cfg->feat_root == 8) {
+        const Res8bPack p = pack_res8b(blob, up);
+        m->d_r8b_down_w = m->put_some(p.down_w);
+        m->d_r8b_down_b = m->put_some(p.down_b);
+        m->d_r8f_down_w1 = m->put_some(p.f_down_w1);
+        m->d_r8b_down_w1r = m->put_some(p.down_w1r);
+        m->d_r8b_up_w = m->put_some(p.up_w);
+        m->d_r8b_up_b = m->put_some(p.up_b);
+        m->d_r8b_up_w1 = m->put_some(p.up_w1);
+        m->d_r8b_up_b1 = m->put_some(p.up_b1);
+        m->d_r8f_up_w1 = m->put_some(p.f_up_w1);
+    }
+    if (fusedb && cfg->res_depth == 3)
+        for (int l = 0; l < n; ++l) {
+            const int f = cfg->feat_root << l;
+            if (f != 8 && f != 16 && !(f == 32 && m->use_res32)) continue;
+            for (const char* side : {"down", "up"}) {
+                if (side[0] == 'u' && l == n - 1) continue;
+                const std::string scope = std::string("aru_net/featMapG/unet_") + side + "_" + std::to_string(l);
+                const ResbPack p = pack_resb(blob, scope, f);
+                if (p.ok) m->resb[scope] = {f, m->put(p.w), m->put(p.b)};
+            }
+        }
+    const Layer logit = find_layer(blob, "aru_net/logit/class");
+    if (!has_shape(logit.w, 4, 4, cfg->feat_root, cfg->n_classes)) {
+        set_error("weights: aru_net/logit/class/weights must be [4,4,%d,%d]", cfg->feat_root, cfg->n_classes);
+        throw PackRefusal{ASEP_ERR_WEIGHTS};
+    }
+    m->d_logit_w = m->put(logit.w.data);
+    m->d_logit_b = m->put(logit.b.data);
+    if (cfg->n_classes == 2) m->d_logit_wd = m->put(pack_logit_diff(logit));
+}
+
+}  // namespace
+
 extern "C" {
 
 asep_aru* asep_aru_load(const void* weight_blob, size_t nbytes, const asep_aru_cfg* cfg) {
@@ -2521,104 +2045,21 @@ asep_aru* asep_aru_load(const void* weight_blob, size_t nbytes, const asep_aru_c
         m->lanes.push_back(std::move(L));
     }
     m->cur = m->lanes[0].get();
-    int rc = ASEP_OK;
-    const int n = cfg->scale_space_num;
-    if (cfg->use_attention) {
-        rc = pack_direct(m.get(), blob, "aru_net/attMapG/attPart/conv1", &m->att_first);
-        if (!rc && m->att_first.k == 4 && m->att_first.cout == 12) {
-            const HostTensor& w = blob.find("aru_net/attMapG/attPart/conv1/weights")->second;   // [4][4][1][12]
-            std::vector<float> pk(64 * 4, 0.f);
-            for (int lane = 0; lane < 64; ++lane)
-                for (int r = 0; r < 4; ++r) {
-                    const int co = lane & 15, ky = lane >> 4, kx = r;
-                    if (co < 12) pk[lane * 4 + r] = w.data[(size_t)(ky * 4 + kx) * 12 + co];
-                }
-            rc = upload(pk, &m->d_att_head);
-            if (!rc) m->owned.push_back(m->d_att_head);
-            if (!rc && m->bf16) {                            // att_headb_kernel: k = 8 kk + 4 r + c <-> tap (2 kk + r, c) for kk < 2, zero rows / slots elsewhere
-                std::vector<bf16_t> pb(64 * 8, 0);
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int co = lane & 15, kk = lane >> 4;
-                    for (int i = 0; i < 8 && kk < 2 && co < 12; ++i) pb[lane * 8 + i] = f2bf(w.data[(size_t)((2 * kk + (i >> 2)) * 4 + (i & 3)) * 12 + co]);
-                }
-                rc = upload_bf(pb, &m->d_att_headb);
-                if (!rc) m->owned.push_back(m->d_att_headb);
-            }
-        }
-        for (int i = 2; i <= 4 && !rc; ++i)
-            rc = pack_conv(m.get(), blob, "aru_net/attMapG/attPart/conv" + std::to_string(i), "biases", false);
+    try {
+        load_weights(m.get(), blob, variant);
+    } catch (const PackRefusal&) {                           // (the error text is set)
+        return nullptr;
     }
-    if (!rc) rc = pack_direct(m.get(), blob, "aru_net/featMapG/unet_down_0/conv1", &m->det_first);
-    for (int l = 0; l < n && !rc; ++l) {
-        const std::string s = "aru_net/featMapG/unet_down_" + std::to_string(l);
-        if (l > 0) rc = pack_conv(m.get(), blob, s + "/conv1", "biases", false);
-        if (cfg->plain_u) { if (!rc) rc = pack_conv(m.get(), blob, s + "/conv2", "biases", false); continue; }
-        for (int r = 0; r < cfg->res_depth && !rc; ++r)
-            rc = pack_conv(m.get(), blob, s + "/convR_" + std::to_string(r), "biases", false);
-    }
-    for (int l = n - 2; l >= 0 && !rc; --l) {
-        const std::string s = "aru_net/featMapG/unet_up_" + std::to_string(l);
-        rc = pack_conv(m.get(), blob, s + "/deconv", "bias", true);
-        if (!rc) rc = pack_conv(m.get(), blob, s + "/conv1", "biases", false);
-        if (cfg->plain_u) { if (!rc) rc = pack_conv(m.get(), blob, s + "/conv2", "biases", false); continue; }
-        for (int r = 0; r < cfg->res_depth && !rc; ++r)
-            rc = pack_conv(m.get(), blob, s + "/convR_" + std::to_string(r), "biases", false);
-    }
-    if (!rc && (!variant || m->fused8_var) && !m->bf16 && cfg->feat_root == 8 && cfg->res_depth == 3 && m->det_first.k == 3) rc = pack_res8(m.get(), blob);
-    if (!rc && m->split && !variant && m->d_r8_down_wr) rc = pack_res8ws(m.get(), blob);
-    // (bf16 path, elu / leaky / 'U' graphs -- round 5: layer by layer on convb_kernel / deconvb_kernel with the activation in their general
-    //  epilogues; the fused blocks below bake the ReLU into packed-bf16 maxima and serve the ReLU residual graphs)
-    // (round 6: the elu / leaky RESIDUAL graphs take the GENERAL fused forms of the 8- and 16-channel levels -- res8b_tile / resb_tail_tile apply the
-    //  activation to fp32 values and take float maxima in their pools, a template parameter serves them; the 32-channel tail the same way; the lean forms and
-    //  the walkers stay the ReLU graphs')
-    m->fused_act = (m->bf16 && variant && !cfg->plain_u && cfg->activation != 0 && m->fused8_wanted && m->fuse_act) ? cfg->activation : 0;
-    const bool fusedb = m->bf16 && (!variant || m->fused_act);
-    if (!rc && fusedb && cfg->res_depth == 3 && cfg->feat_root == 8) rc = pack_res8b(m.get(), blob);
-    if (!rc && fusedb && cfg->res_depth == 3)
-        for (int l = 0; l < n && !rc; ++l) {
-            const int f = cfg->feat_root << l;
-            if (f != 8 && f != 16 && !(f == 32 && m->use_res32)) continue;
-            rc = pack_resb(m.get(), blob, "aru_net/featMapG/unet_down_" + std::to_string(l), f);
-            if (!rc && l < n - 1) rc = pack_resb(m.get(), blob, "aru_net/featMapG/unet_up_" + std::to_string(l), f);
-        }
-    if (rc) return nullptr;
     {
         hipDeviceProp_t prop;
         int dev = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
             m->num_cus = prop.multiProcessorCount;
     }
-    auto lw = blob.find("aru_net/logit/class/weights");
-    auto lb = blob.find("aru_net/logit/class/biases");
-    if (lw == blob.end() || lb == blob.end()) { set_error("weights: missing aru_net/logit/class"); return nullptr; }
-    const auto& d = lw->second.dims;
-    if (d.size() != 4 || d[0] != 4 || d[1] != 4 || d[2] != cfg->feat_root || d[3] != cfg->n_classes) {
-        set_error("weights: aru_net/logit/class/weights must be [4,4,%d,%d]", cfg->feat_root, cfg->n_classes);
-        return nullptr;
-    }
-    if (upload(lw->second.data, &m->d_logit_w) || upload(lb->second.data, &m->d_logit_b)) return nullptr;
-    m->owned.push_back(m->d_logit_w);
-    m->owned.push_back(m->d_logit_b);
-    if (cfg->n_classes == 2) {
-        const std::vector<float>& w = lw->second.data;       // [4][4][feat_root][2]
-        std::vector<float> wd((size_t)16 * cfg->feat_root + 1);
-        for (size_t i = 0; i < (size_t)16 * cfg->feat_root; ++i) wd[i] = w[2 * i + 1] - w[2 * i];
-        wd.back() = lb->second.data[1] - lb->second.data[0];
-        if (upload(wd, &m->d_logit_wd)) return nullptr;
-        m->owned.push_back(m->d_logit_wd);
-    }
-    if (hipMalloc((void**)&m->d_stats, 2 * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&m->d_sums, 2 * sizeof(double)) != hipSuccess) {
-        set_error("asep_aru_load: hipMalloc failed");
-        return nullptr;
-    }
-    m->owned.push_back(m->d_stats);
-    m->owned.push_back(m->d_sums);
-    if (hipMalloc((void**)&m->d_zero_trash, 8192) != hipSuccess || hipMemset(m->d_zero_trash, 0, 8192) != hipSuccess) {
-        set_error("asep_aru_load: hipMalloc failed");
-        return nullptr;
-    }
-    m->owned.push_back(m->d_zero_trash);
+    m->d_stats = m->alloc<float>(2);
+    m->d_sums = m->alloc<double>(2);
+    m->d_zero_trash = m->alloc<unsigned char>(8192);
+    ASEP_HIP_CHECK_THROW(hipMemset(m->d_zero_trash, 0, 8192));
     return m.release();
     ASEP_GUARD_END_PTR
 }

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/asep_hip.h"
+#include "host_tensor.h"
 
 namespace asep {
 
@@ -63,16 +64,6 @@ struct ArgError {};
     }
 #define ASEP_GUARD_END ASEP_GUARD_END_WITH(ASEP_ERR_HIP, ASEP_ERR_ARG)
 #define ASEP_GUARD_END_PTR ASEP_GUARD_END_WITH(nullptr, nullptr)
-
-struct HostTensor {
-    std::vector<int> dims;
-    std::vector<float> data;       // copied out of the caller's blob (payloads may be unaligned)
-    size_t count() const {
-        size_t n = 1;
-        for (int d : dims) n *= (size_t)d;
-        return n;
-    }
-};
 
 // Parses the "ASEPW001" container (weights.py).  Returns false (and sets the error) on malformed input.
 bool parse_blob(const void* blob, size_t nbytes, std::map<std::string, HostTensor>& out);
