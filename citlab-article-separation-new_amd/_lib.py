@@ -45,6 +45,15 @@ class ClusterSetting(C.Structure):
     _fields_ = [("min_neighbors", C.c_int32), ("assign_noise", C.c_int32), ("conf_thr", C.c_double), ("agree_thr", C.c_double)]
 
 
+CLUSTER_METHODS = {"dbscan": 0, "dbscan_std": 1, "greedy": 2}       # ASEP_CLUSTER_* of include/asep_hip.h
+
+
+class ClusterMethodSetting(C.Structure):
+    """asep_cluster_method_setting (include/asep_hip.h): one setting of asep_cluster_grid_run_methods"""
+    _fields_ = [("method", C.c_int32), ("count", C.c_int32), ("assign_noise", C.c_int32), ("reserved", C.c_int32),
+                ("conf_thr", C.c_double), ("param", C.c_double)]
+
+
 class GnnPage(C.Structure):
     """asep_gnn_page (include/asep_hip.h): one page of asep_gnn_forward_visual_batch_dev, device addresses"""
     _fields_ = [("N", C.c_int32), ("E", C.c_int32), ("R", C.c_int32), ("d_edges", C.c_void_p), ("d_node_feat", C.c_void_p),
@@ -124,6 +133,7 @@ SIGNATURES = {
     "asep_cluster_grid_run": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "asep_cluster_grid_last_kernel_us": (C.c_double, []),
     "asep_cluster_grid_max_nodes": (C.c_int, []),
+    "asep_cluster_grid_run_methods": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "asep_releval_create": (_P, []),
     "asep_releval_free": (None, [_P]),
     "asep_releval_reset": (C.c_int, [_P, _P]),

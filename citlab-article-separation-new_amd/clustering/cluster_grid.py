@@ -1,10 +1,15 @@
-"""The ``dbscan`` clustering of many pages under many settings in one launch (``asep_cluster_grid_run``), and the split / merge
-counts of ``as_eval`` for every (page, setting) behind it.
+"""The ``dbscan``, ``dbscan_std`` and ``greedy`` clusterings of many pages under many settings in one call
+(``asep_cluster_grid_run`` for ``dbscan`` alone, ``asep_cluster_grid_run_methods`` for the three mixed), and behind them the
+split / merge counts of ``as_eval`` and ``rel_LLH`` for every (page, setting).
 
 ``ClusterGrid`` prepares each page's matrix with the host classes' own code (``TextblockClustering.set_confs`` and
 ``DBScanRelation.initialize_clustering``), so the device sees what ``DBScanRelation.confidences`` holds; the labels it returns
 equal ``TextblockClustering.calc('dbscan')``'s, integer for integer (a page of two nodes follows ``calc``'s special rule: it is
-uploaded as ``_conf_mat``, not made symmetric, and the kernel tests ``conf[0, 1] >= confidence_threshold``).  There is no CPU fallback: without a GPU the constructor raises.
+uploaded as ``_conf_mat``, not made symmetric, and the kernel tests ``conf[0, 1] >= confidence_threshold``).  A setting dict
+may carry ``"clustering_method"`` (``"dbscan"`` when absent; ``"method"`` is linkage's parameter): ``"dbscan_std"`` reads
+``epsilon`` / ``min_samples`` and runs on the page's ``_dist_mat``, ``"greedy"`` reads ``max_iteration`` and runs on
+``_delta_mat``; their labels equal ``calc('dbscan_std')``'s and ``calc('greedy')``'s.  ``"linkage"`` stays with the host class.
+There is no CPU fallback: without a GPU the constructor raises.
 """
 import ctypes as C
 
@@ -45,12 +50,37 @@ def setting_array(settings):
     return arr
 
 
+def _method_of(given):
+    method = given.get("clustering_method", "dbscan")
+    if method == "linkage":
+        raise ValueError("clustering_method 'linkage' does not run on the device: use TextblockClustering.calc('linkage')")
+    if method not in _lib.CLUSTER_METHODS:
+        raise ValueError(f"clustering_method '{method}': the clustering grid runs {', '.join(_lib.CLUSTER_METHODS)}")
+    return method
+
+
+def method_setting_array(settings):
+    """clustering_params dicts with an optional "clustering_method" -> ctypes array of asep_cluster_method_setting"""
+    arr = (_lib.ClusterMethodSetting * max(1, len(settings)))()
+    for i, given in enumerate(settings):
+        method = _method_of(given)
+        p = dict(DEFAULT_PARAMS)
+        p.update(given)
+        count, param = {"dbscan": ("min_neighbors_for_cluster", "cluster_agreement_threshold"),
+                        "dbscan_std": ("min_samples", "epsilon"), "greedy": ("max_iteration", None)}[method]
+        arr[i] = _lib.ClusterMethodSetting(_lib.CLUSTER_METHODS[method], int(p[count]), 1 if p["assign_noise_clusters"] else 0, 0,
+                                           float(p["confidence_threshold"]), float(p[param]) if param else 0.0)
+    return arr
+
+
 class ClusterGrid:
     def __init__(self, device=0):
         from ..textblock import _handle
         self._lib, self._h = _handle(device)            # raises without the library or a GPU
         self.max_nodes = self._lib.asep_cluster_grid_max_nodes()
         self.mats = []
+        self.dists = []                                 # _dist_mat and _delta_mat of the pages, next to mats
+        self.deltas = []
         self.dtype = None
         self.kernel_us = 0.0
 
@@ -73,17 +103,22 @@ class ClusterGrid:
             raise ValueError(f"page {len(self.mats)} has {n} nodes, the device engine clusters at most {self.max_nodes}")
         self.dtype = mat.dtype
         self.mats.append(mat)
+        self.dists.append(np.ascontiguousarray(tb._dist_mat, mat.dtype))
+        self.deltas.append(np.ascontiguousarray(tb._delta_mat, mat.dtype))
         return len(self.mats) - 1
 
     def clear(self):
         self.mats = []
+        self.dists = []
+        self.deltas = []
         self.dtype = None
 
     # -- launches --------------------------------------------------------------------------------------------------
-    def _run(self, settings, tables=None):
+    def _run(self, settings, tables=None, llh=False):
         node_off = _offsets([m.shape[0] for m in self.mats])
-        conf = np.concatenate([m.reshape(-1) for m in self.mats]) if self.mats else np.zeros(0, np.float32)
-        st = setting_array(settings)
+        flat = lambda mats: np.concatenate([m.reshape(-1) for m in mats]) if mats else np.zeros(0, np.float32)   # noqa: E731
+        conf = flat(self.mats)
+        methods = [_method_of(given) for given in settings]
         labels = np.zeros((len(settings), int(node_off[-1])), np.int32)
         counts = None
         args = [None] * 6
@@ -95,29 +130,54 @@ class ClusterGrid:
                     _offsets([len(t["blocks"]) for t in tables]), _offsets([len(b) for b in blocks]),
                     np.asarray([i for b in blocks for i in b], np.int32)]
             counts = np.zeros((len(settings), len(self.mats), 4), np.int32)
-        _lib.check(self._lib.asep_cluster_grid_run(self._h, len(self.mats), _ptr(node_off), _ptr(conf),
-                                                   1 if conf.dtype == np.float64 else 0, len(settings), st,
-                                                   *[_ptr(a) for a in args], _ptr(labels), _ptr(counts)),
-                   "asep_cluster_grid_run")
+        is_f64 = 1 if conf.dtype == np.float64 else 0
+        rel_llh = None
+        if not llh and all(m == "dbscan" for m in methods):
+            _lib.check(self._lib.asep_cluster_grid_run(self._h, len(self.mats), _ptr(node_off), _ptr(conf), is_f64, len(settings),
+                                                       setting_array(settings), *[_ptr(a) for a in args], _ptr(labels),
+                                                       _ptr(counts)),
+                       "asep_cluster_grid_run")
+        else:
+            if "greedy" in methods:
+                for k, d in enumerate(self.deltas):
+                    if np.isnan(d).any() or (d == np.inf).any():
+                        raise ValueError(f"page {k}: its _delta_mat holds NaN or +inf, greedy needs finite entries off the diagonal "
+                                         f"(confidences in [0, 1])")
+            dist = flat(self.dists) if "dbscan_std" in methods else None
+            delta = flat(self.deltas) if llh or "greedy" in methods else None
+            if llh:
+                rel_llh = np.zeros((len(settings), len(self.mats)), np.float64)
+            _lib.check(self._lib.asep_cluster_grid_run_methods(self._h, len(self.mats), _ptr(node_off), is_f64, _ptr(conf),
+                                                               _ptr(dist), _ptr(delta), len(settings),
+                                                               method_setting_array(settings), *[_ptr(a) for a in args],
+                                                               _ptr(labels), _ptr(counts), _ptr(rel_llh)),
+                       "asep_cluster_grid_run_methods")
         self.kernel_us = self._lib.asep_cluster_grid_last_kernel_us()
-        return node_off, labels, counts
+        return node_off, labels, counts, rel_llh
 
     def run_array(self, settings):
         """-> (node_off int32 [pages + 1], labels int32 [settings, nodes of all pages])"""
-        node_off, labels, _ = self._run(list(settings))
+        node_off, labels, _, _ = self._run(list(settings))
         return node_off, labels
 
     def run(self, settings):
-        """-> labels[setting][page]: int32 array of the page's labels, from 1 (-1: noise left unassigned)"""
+        """-> labels[setting][page]: int32 array of the page's labels, as the setting's method numbers them: dbscan from 1 (-1:
+        noise left unassigned), dbscan_std from 0 (-1: noise), greedy from 0"""
         node_off, labels = self.run_array(settings)
         return [_per_page(row, node_off) for row in labels]
+
+    def run_llh(self, settings):
+        """-> (labels[setting][page], rel_LLH float64 [settings, pages]): ``TextblockClustering.rel_LLH`` of the labels, each
+        term formed in the matrix dtype and the sum taken in float64 (the host class adds in the matrix dtype)"""
+        node_off, labels, _, rel_llh = self._run(list(settings), llh=True)
+        return [_per_page(row, node_off) for row in labels], rel_llh
 
     def run_compare_array(self, settings, tables):
         """``tables``: one ``as_eval.comparison_tables`` dict per page.  -> (node_off, labels, counts int32 [settings, pages, 4]
         = hypNIs, n_inf, corrects, 0)"""
         if len(tables) != len(self.mats):
             raise ValueError(f"{len(tables)} comparison tables for {len(self.mats)} pages")
-        return self._run(list(settings), list(tables))
+        return self._run(list(settings), list(tables))[:3]
 
     def run_compare(self, settings, pages, on_inconsistent="raise"):
         """``pages``: per page (hypothesis PAGE-XML whose text regions are the page's nodes, ground truth PAGE-XML), paths or

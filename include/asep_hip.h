@@ -473,8 +473,48 @@ int asep_cluster_grid_run(asep_post* p, int n_pages, const int32_t* node_off, co
                           const int32_t* gtblk_lines, int32_t* out_labels, int32_t* out_counts);
 /* Device time in microseconds of the kernels of the calling thread's last asep_cluster_grid_run (0 if nothing ran). */
 double asep_cluster_grid_last_kernel_us(void);
-/* Largest N_k asep_cluster_grid_run accepts. */
+/* Largest N_k asep_cluster_grid_run and asep_cluster_grid_run_methods accept. */
 int asep_cluster_grid_max_nodes(void);
+
+/* The same call over settings of three clustering methods of TextblockClustering, mixed freely; row s of every output belongs to
+ * settings[s].  The pages' matrices come in up to three sets of the layout of `conf` above, all float (mats_are_f64 0) or all
+ * double (1), each as the host class holds it after set_confs:
+ *   conf   DBScanRelation.confidences, and _conf_mat for a page of two nodes (as above): needed by a dbscan setting, and by any
+ *          setting when a page has two nodes (calc's rule for two nodes does not depend on the method; it reads conf_thr)
+ *   dist   _dist_mat (diagonal 0): needed by a dbscan_std setting
+ *   delta  _delta_mat (diagonal -inf, every other entry finite): needed by a greedy setting and by out_llh
+ * A set that is not needed may be NULL; a needed one that is NULL is ASEP_ERR_ARG.
+ * ASEP_CLUSTER_DBSCAN: as asep_cluster_grid_run (count = min_neighbors_for_cluster, param = cluster_agreement_threshold).
+ * ASEP_CLUSTER_DBSCAN_STD: sklearn.cluster.dbscan(dist, metric='precomputed', eps = param, min_samples = count): node i is a core
+ *   point when row i holds at least `count` entries <= (T)eps (the diagonal counts); clusters are numbered from 0 by their seed,
+ *   the lowest core point without a label, and hold whatever is reachable from it along row entries <= (T)eps out of core
+ *   points; other nodes are -1.  Rows, not columns: the matrix may be asymmetric.  assign_noise is not read.
+ * ASEP_CLUSTER_GREEDY: TextblockClustering._greedy with max_iteration = count: while the budget lasts, (i, j) = the first
+ *   maximum of the working matrix in row-major order; stop unless it is > 0; class i absorbs class j, for every other idx
+ *   m[idx][i] = m[idx][i] + m[idx][j] (one addition in T) and m[i][idx] = m[idx][i], row and column j leave.  Labels from 0: the
+ *   rank of the node's class among the classes left.  The working matrices live in the handle's pool (N_k^2 values per greedy
+ *   setting and page).  assign_noise and param are not read.
+ * out_llh (optional) [n_settings][n_pages]: TextblockClustering.rel_LLH of the labels, the sum of (delta[i][k] + delta[k][i]) / 2
+ * over the pairs k < i with equal labels >= 0; each term is formed in T, the sum is taken in double (the host adds in T, so the
+ * two agree to rounding, not bit for bit).  out_labels may be NULL when out_counts or out_llh is asked for.
+ * An unknown method, a missing set, bad tables, more (page, setting) pairs than one launch holds or a page above the limit
+ * return ASEP_ERR_ARG and launch nothing.  asep_cluster_grid_last_kernel_us covers all kernels of this call as well. */
+#define ASEP_CLUSTER_DBSCAN 0
+#define ASEP_CLUSTER_DBSCAN_STD 1
+#define ASEP_CLUSTER_GREEDY 2
+typedef struct asep_cluster_method_setting {
+    int32_t method;        /* ASEP_CLUSTER_* */
+    int32_t count;         /* min_neighbors_for_cluster | min_samples | max_iteration */
+    int32_t assign_noise;  /* assign_noise_clusters (dbscan) */
+    int32_t reserved;      /* 0 */
+    double conf_thr;       /* confidence_threshold: dbscan's neighbourhood, and the rule for a page of two nodes */
+    double param;          /* cluster_agreement_threshold | epsilon */
+} asep_cluster_method_setting;
+int asep_cluster_grid_run_methods(asep_post* p, int n_pages, const int32_t* node_off, int mats_are_f64, const void* conf,
+                                  const void* dist, const void* delta, int n_settings,
+                                  const asep_cluster_method_setting* settings, const int32_t* line_off, const int32_t* line_node,
+                                  const int32_t* line_gt, const int32_t* gtblk_off, const int32_t* gtblk_line_off,
+                                  const int32_t* gtblk_lines, int32_t* out_labels, int32_t* out_counts, double* out_llh);
 
 /* ---- relation net evaluation (article_separation/gnn/trainer/lav_rel.py) ----------------------------------------------
  * An accumulator of (score, label) pairs in HBM and sklearn's _binary_clf_curve over them: what precision_recall_curve,
