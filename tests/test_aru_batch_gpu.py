@@ -133,18 +133,24 @@ def test_bf16_fused_level2_tail_equals_the_layer_by_layer_form(H, W, monkeypatch
     from citlab_article_separation_new_amd.weights import init_aru_weights
     cfg = AruConfig(compute_dtype="bf16")
     w = init_aru_weights(cfg, 99, bias_jitter=0.05, logit_scale=0.05)
+    import kernel_profile as kp
     img = np.random.default_rng(H).random((H, W), dtype=np.float32)
-    res = {}
+    res, prof = {}, {}
     for flag in ("1", "0"):
         monkeypatch.setenv("ASEP_BF_RES32", flag)            # read when the engine is created
         g = helper.AruGraph(w, cfg)
         out = helper.get_net_output(img, g, "0")
         res[flag] = (out, {n: helper.get_endpoint(g, n) for n in ("scale_0_unet_down_2_conv", "scale_1_unet_down_2_conv",
                                                                  "scale_2_unet_up_2_conv", "scale_0_unet_up_2_conv", "scale_0_unet_down_3_conv")})
+        prof[flag] = kp.launched(g, img)                     # (a pass of its own: recording serialises the net)
         g.close()
     for n in res["1"][1]:
         assert np.array_equal(res["1"][1][n], res["0"][1][n]), n
     assert np.array_equal(res["1"][0], res["0"][0])
+    # the two runs really are two kernels: one launch per 32-channel tail against three convb_kernel launches
+    kp.check(prof["1"], ["res32_tail_kernel"], [], "ASEP_BF_RES32=1")
+    kp.check(prof["0"], [], ["res32_tail_kernel"], "ASEP_BF_RES32=0")
+    assert kp.calls(prof["0"], "convb_kernel") == kp.calls(prof["1"], "convb_kernel") + cfg.res_depth * kp.calls(prof["1"], "res32_tail_kernel")
 
 
 def test_bf16_variant_medium_page_within_stated_tolerance():

@@ -176,8 +176,9 @@ def test_fused_activation_of_the_variants_is_the_separate_pass_bit_for_bit(kw, m
     act_kernel pass behind it; same arithmetic on the same values, so ASEP_FUSE_ACT=0 (the round-3 form) must give the same bits --
     on a size with interior AND border tiles (the fused form routes a variant's launches through the general epilogues)."""
     from citlab_article_separation_new_amd import net_post_processing_helper as helper
+    import kernel_profile as kp
     img = _image(300, 270, 3)
-    outs, eps = [], []
+    outs, eps, prof = [], [], []
     # (ASEP_FUSED8=0: the attention head as conv1 + pool in both runs -- its fused vector-ALU form, which an elu / leaky graph takes
     # since round 4 as well, sums the taps in another order; it is held to the oracle by test_graph_variants_elu_leaky_and_plain_u)
     monkeypatch.setenv("ASEP_FUSED8", "0")
@@ -187,8 +188,11 @@ def test_fused_activation_of_the_variants_is_the_separate_pass_bit_for_bit(kw, m
         outs.append(helper.get_net_output(img, graph, "0"))
         eps.append({n: helper.get_endpoint(graph, n) for n in ("scale_0_unet_down_0_conv", "scale_0_unet_down_2_conv", "scale_0_unet_up_0_deconv",
                                                                "scale_0_unet_up_0_conv")})
+        prof.append(kp.launched(graph, img))                     # (a pass of its own: recording serialises the net)
         graph.close()
     assert np.array_equal(outs[0], outs[1])
+    kp.check(prof[0], [], ["act_kernel"], "ASEP_FUSE_ACT=1")     # the two runs really differ: no separate pass in one, one behind every layer in the other
+    kp.check(prof[1], ["act_kernel"], [], "ASEP_FUSE_ACT=0")
     assert all(np.array_equal(eps[0][n], eps[1][n]) for n in eps[0])
     assert (eps[0]["scale_0_unet_up_0_deconv"] < 0).any()        # negative branch exercised
     if kw.get("graph") != "U":
@@ -252,17 +256,21 @@ def test_fp32_level0_mfma_variant_agrees_with_the_vector_alu_kernels(H, W, monke
     each other far inside it (same sums, different order)."""
     from citlab_article_separation_new_amd import net_post_processing_helper as helper
     from oracle import aru_oracle
+    import kernel_profile as kp
     img = _image(H, W, 77)
-    outs = {}
+    outs, prof = {}, {}
     for valu in ("1", "0"):
         monkeypatch.setenv("ASEP_R8_VALU", valu)          # read when the engine is created
         cfg, w, graph = _setup()
         outs[valu] = helper.get_net_output(img, graph, "0")
+        prof[valu] = kp.launched(graph, img)                     # (a pass of its own: recording serialises the net)
         graph.close()
     ref = aru_oracle.forward_torch(img, w, cfg)
     for valu, out in outs.items():
         assert float(np.abs(out - ref).max()) <= PROB_TOL, valu
     assert float(np.abs(outs["1"] - outs["0"]).max()) <= 1e-5
+    kp.check(prof["1"], ["res8v_down_kernel", "res8v_up_kernel"], ["res8_down_kernel", "res8_up_kernel"], "ASEP_R8_VALU=1")
+    kp.check(prof["0"], ["res8_down_kernel", "res8_up_kernel"], ["res8v_down_kernel", "res8v_up_kernel"], "ASEP_R8_VALU=0")
 
 
 @pytest.mark.parametrize("H,W", [(200, 150), (67, 131)])
@@ -271,8 +279,9 @@ def test_fused_pool_and_dense_12_channel_mode_match_their_plain_forms(H, W, monk
     2x2 max in the conv epilogues (same values, so the outputs are bit-identical), ASEP_C12=0 pads the attention conv2's 12
     input channels to 16 instead of the dense K mapping (another summation order: equal to 1e-5)."""
     from citlab_article_separation_new_amd import net_post_processing_helper as helper
+    import kernel_profile as kp
     img = _image(H, W, 91)
-    outs = {}
+    outs, prof = {}, {}
     for name, env in (("default", {}), ("plain_pool", {"ASEP_FUSE_POOL": "0"}), ("padded_c12", {"ASEP_C12": "0"})):
         for k in ("ASEP_FUSE_POOL", "ASEP_C12"):
             monkeypatch.delenv(k, raising=False)
@@ -280,9 +289,26 @@ def test_fused_pool_and_dense_12_channel_mode_match_their_plain_forms(H, W, monk
             monkeypatch.setenv(k, v)                       # read when the engine is created
         cfg, w, graph = _setup()
         outs[name] = helper.get_net_output(img, graph, "0")
+        prof[name] = kp.launched(graph, img)                     # (a pass of its own: recording serialises the net)
         graph.close()
     assert np.array_equal(outs["default"], outs["plain_pool"])
     assert float(np.abs(outs["default"] - outs["padded_c12"]).max()) <= 1e-5
+    kp.check(prof["default"], [], ["maxpool2_kernel"], "default")
+    kp.check(prof["plain_pool"], ["maxpool2_kernel"], [], "ASEP_FUSE_POOL=0")
+    # The default arithmetic (f32s) runs the attention conv2 on convs_kernel whatever ASEP_C12 says: the two runs above launch the same kernels.  The
+    # dense and the padded K mapping are two instantiations of the plain fp32 engine's conv_mfma_kernel: compared there, and shown to be two kernels
+    outs32, prof32 = {}, {}
+    for flag in ("1", "0"):
+        monkeypatch.delenv("ASEP_FUSE_POOL", raising=False)
+        monkeypatch.setenv("ASEP_C12", flag)
+        cfg, w, graph = _setup({"compute_dtype": "f32"})
+        outs32[flag] = helper.get_net_output(img, graph, "0")
+        prof32[flag] = kp.launched(graph, img)
+        graph.close()
+    assert float(np.abs(outs32["1"] - outs32["0"]).max()) <= 1e-5
+    dense, padded = kp.C12_DENSE, kp.C12_PADDED
+    kp.check(prof32["1"], [dense], [padded], "f32 ASEP_C12=1")
+    kp.check(prof32["0"], [padded], [dense], "f32 ASEP_C12=0")
 
 
 def test_integration_md_stub_runs_the_net(tmp_path):
@@ -387,15 +413,20 @@ def test_level0_blocks_as_strip_walkers_against_the_tile_kernels_and_the_oracle(
     from citlab_article_separation_new_amd import net_post_processing_helper as helper
     from oracle import aru_oracle
     down, up = "scale_0_unet_down_0_conv", "scale_0_unet_up_0_conv"
+    import kernel_profile as kp
     img = _image(H, W, 77)
-    res = {}
+    res, prof = {}, {}
     for walk in ("1", "0"):
         monkeypatch.setenv("ASEP_BF_WALK", walk)               # read when the engine is created
         cfg, w, graph = _setup({"compute_dtype": "bf16"}, seed=9)
         res[walk] = (helper.get_net_output(img, graph, "0"),
                      {n: helper.get_endpoint(graph, n) for n in (down, "scale_0_unet_down_1_conv", "scale_0_unet_up_1_conv", up)})
+        prof[walk] = kp.launched(graph, img)                     # (a pass of its own: recording serialises the net)
         graph.close()
     (p1, eng), (p0, eng0) = res["1"], res["0"]
+    # the two runs really are two kernels: both blocks on the walkers in one, on the tile kernels alone in the other
+    kp.check(prof["1"], ["res8w_kernel<false>", "res8w_kernel<true>", "res8wb_kernel<false>", "res8wb_kernel<true>"], [], "ASEP_BF_WALK=1")
+    kp.check(prof["0"], ["res8f_kernel<false>", "res8f_kernel<true>"], ["res8w_kernel", "res8wb_kernel"], "ASEP_BF_WALK=0")
     # the walkers' region, and the tile kernels' interior tiles (whole 24 x 40 window inside the image)
     ys, xs = np.arange(H)[:, None], np.arange(W)[None, :]
     n_strips, y_end = (W - 4 - 32) // 24, 16 + 2 * ((H - 4 - 16) // 2)
@@ -431,15 +462,20 @@ def test_up_block_strip_walker_is_bit_identical_to_the_tile_kernel_on_identical_
     the tile kernel's down block and every tensor in front of unet_up_0; the up block's lean regions must then agree bit for bit"""
     from citlab_article_separation_new_amd import net_post_processing_helper as helper
     name = "scale_0_unet_up_0_conv"
+    import kernel_profile as kp
     img = _image(H, W, 78)
-    res = {}
+    res, prof = {}, {}
     for walk in ("2", "0"):
         monkeypatch.setenv("ASEP_BF_WALK", walk)
         cfg, w, graph = _setup({"compute_dtype": "bf16"}, seed=10)
         helper.get_net_output(img, graph, "0")
         res[walk] = helper.get_endpoint(graph, name)
+        prof[walk] = kp.launched(graph, img)                     # (a pass of its own: recording serialises the net)
         graph.close()
     e1, e0 = res["2"], res["0"]
+    # the up block alone walks in one run, nothing in the other; the down block is the tile kernel's in both
+    kp.check(prof["2"], ["res8w_kernel<true>", "res8f_kernel<false>"], ["res8w_kernel<false>"], "ASEP_BF_WALK=2")
+    kp.check(prof["0"], ["res8f_kernel<true>", "res8f_kernel<false>"], ["res8w_kernel"], "ASEP_BF_WALK=0")
     ys, xs = np.arange(H)[:, None], np.arange(W)[None, :]
     n_strips, y_end = (W - 4 - 32) // 24, 16 + 2 * ((H - 4 - 16) // 2)
     walker = (ys >= 16) & (ys < y_end) & (xs >= 32) & (xs < 32 + 24 * n_strips)
@@ -459,17 +495,23 @@ def test_the_64_channel_layers_with_the_filter_in_registers_are_bit_identical_to
     38 x 3 pixels (ranges of one and two rows, a single partial strip).  The RES form (unet_up_3/convR_2) is in every one of them."""
     from citlab_article_separation_new_amd import net_post_processing_helper as helper
     names = ["scale_0_unet_down_3_conv", "scale_0_unet_up_3_conv", "scale_1_unet_down_3_conv", "scale_2_unet_up_3_conv", "scale_0_unet_up_0_conv"]
+    import kernel_profile as kp
     img = _image(H, W, 91)
-    res = {}
+    res, prof = {}, {}
     for on in ("1", "0"):
         monkeypatch.setenv("ASEP_BF_CONVR", on)
         cfg, w, graph = _setup({"compute_dtype": "bf16"}, seed=12)
         res[on] = (helper.get_net_output(img, graph, "0"), {n: helper.get_endpoint(graph, n) for n in names})
+        prof[on] = kp.launched(graph, img)                       # (a pass of its own: recording serialises the net)
         graph.close()
     (p1, e1), (p0, e0) = res["1"], res["0"]
     for n in names:
         assert e1[n].shape == e0[n].shape and np.array_equal(e1[n], e0[n]), (n, int((e1[n] != e0[n]).sum()))
     assert np.array_equal(p1, p0)
+    # the two runs really are two kernels (tests/test_kernel_selection_gpu.py has the layer-by-layer count)
+    kp.check(prof["1"], ["convr_kernel"], [], "ASEP_BF_CONVR=1")
+    kp.check(prof["0"], [], ["convr_kernel"], "ASEP_BF_CONVR=0")
+    assert kp.calls(prof["0"], "convb_kernel") == kp.calls(prof["1"], "convb_kernel") + kp.calls(prof["1"], "convr_kernel")
 
 
 
@@ -483,15 +525,20 @@ def test_elu_and_leaky_graphs_on_the_fused_general_blocks_of_the_bf16_engine(act
     roundings are test_graph_variants_on_the_bf16_path's and hold for the fused forms: they are what that test runs now.)"""
     from citlab_article_separation_new_amd import net_post_processing_helper as helper
     names = ["scale_0_unet_down_0_conv", "scale_0_unet_down_1_conv", "scale_0_unet_up_1_conv", "scale_0_unet_up_0_conv", "scale_1_unet_up_0_conv"]
+    import kernel_profile as kp
     img = _image(H, W, 57)
-    res = {}
+    res, prof = {}, {}
     for fused in ("1", "0"):
         monkeypatch.setenv("ASEP_FUSED8", fused)
         cfg, w, graph = _setup({"compute_dtype": "bf16", "activation_name": act}, seed=14)
         p = helper.get_net_output(img, graph, "0")
         res[fused] = (p, {n: helper.get_endpoint(graph, n) for n in names})
+        prof[fused] = kp.launched(graph, img)                    # (a pass of its own: recording serialises the net)
         graph.close()
     (p1, e1), (p0, e0) = res["1"], res["0"]
+    act_code = {"elu": 1, "leaky": 2}[act]
+    kp.check(prof["1"], [f"res8b_kernel<false,{act_code}>", f"res8b_kernel<true,{act_code}>", f"resb_tail_kernel<16,{act_code}>"], [], "ASEP_FUSED8=1")
+    kp.check(prof["0"], [], ["res8b_kernel", "resb_tail_kernel"], "ASEP_FUSED8=0")
     assert (e0["scale_0_unet_down_0_conv"] < 0).any()           # the negative branch of the activation is exercised
     d0 = e1["scale_0_unet_down_0_conv"] - e0["scale_0_unet_down_0_conv"]
     sc = max(1.0, float(np.abs(e0["scale_0_unet_down_0_conv"]).max()))

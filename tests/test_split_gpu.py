@@ -117,6 +117,37 @@ def test_split_products_with_other_hyper_parameters_and_graph_variants(kw):
     graph.close()
 
 
+@pytest.mark.parametrize("H,W", [(203, 310), (37, 53)])
+def test_split_product_deconvolutions_agree_with_the_fp32_mfma_form(H, W, monkeypatch):
+    """ASEP_SPLIT_DECONV=0 runs the deconvolutions with >= 32 input channels on deconv_mfma_kernel instead of deconvs_kernel: the same sums from six
+    bf16 partial products per product (dropped terms <= 2^-23 |x w|) in another order -- each deconvolution's end point and the probabilities within
+    1e-5, both forms at the fp32 gates against the oracle; and the launch records show that the two runs are two kernels."""
+    import kernel_profile as kp
+    from citlab_article_separation_new_amd import net_post_processing_helper as helper
+    from oracle import aru_oracle
+    names = [f"scale_{s}_unet_up_{l}_deconv" for s in (0, 2) for l in (3, 2, 1, 0)]
+    img = _image(H, W, 41)
+    res = {}
+    for flag in ("1", "0"):
+        monkeypatch.setenv("ASEP_SPLIT_DECONV", flag)       # read when the engine is created
+        cfg, w, graph = _setup()
+        out = helper.get_net_output(img, graph, "0")
+        res[flag] = (out, {n: helper.get_endpoint(graph, n) for n in names}, kp.launched(graph, img))     # (the launch record: a pass of its own)
+        graph.close()
+    ref, inter = aru_oracle.forward_torch(img, w, cfg, return_intermediates=True)
+    for n in names:
+        a, b = res["1"][1][n], res["0"][1][n]
+        assert a.shape == b.shape == inter[n].shape, n
+        assert float(np.abs(a - b).max()) / max(1.0, float(np.abs(b).max())) <= 1e-5, n
+        for x in (a, b):
+            assert float(np.abs(x - inter[n]).max()) / max(1.0, float(np.abs(inter[n]).max())) <= ENDPOINT_GATE, n
+    assert float(np.abs(res["1"][0] - res["0"][0]).max()) <= 1e-5
+    for flag in ("1", "0"):
+        assert float(np.abs(res[flag][0] - ref).max()) <= PROB_TOL, flag
+    kp.check(res["1"][2], ["deconvs_kernel"], ["deconv_mfma_kernel"], "ASEP_SPLIT_DECONV=1")
+    kp.check(res["0"][2], ["deconv_mfma_kernel"], ["deconvs_kernel"], "ASEP_SPLIT_DECONV=0")
+
+
 def test_batched_pages_equal_single_pages():
     import ctypes as C
     import torch

@@ -34,13 +34,14 @@ def _image(H, W, seed, wide=False):
 
 
 def _run_both(img, monkeypatch, names):
+    import kernel_profile as kp
     from citlab_article_separation_new_amd import net_post_processing_helper as helper
     res = {}
     for flag in ("1", "0"):
         monkeypatch.setenv("ASEP_SPLIT_WALK", flag)        # read when the engine is created
         cfg, w, g = _setup()
         out = helper.get_net_output(img, g, "0")
-        res[flag] = (out, {n: helper.get_endpoint(g, n) for n in names})
+        res[flag] = (out, {n: helper.get_endpoint(g, n) for n in names}, kp.launched(g, img))      # (the launch record: a pass of its own)
         g.close()
     return cfg, w, res
 
@@ -69,6 +70,10 @@ def test_walker_matches_vector_alu_form_and_oracle(H, W, wide, monkeypatch):
         else:
             assert np.array_equal(res["1"][1][n], res["0"][1][n]), (n, h, wd)
     assert _walks(H, W) == ((H, W) != (140, 131))
+    # ... and the launch records say the same: the walker kernel in the one run of a page with room for it, in no other
+    import kernel_profile as kp
+    kp.check(res["1"][2], ["res8ws_kernel<false>", "res8ws_kernel<true>"] if _walks(H, W) else [], [] if _walks(H, W) else ["res8ws_kernel"], "ASEP_SPLIT_WALK=1")
+    kp.check(res["0"][2], ["res8v_down_kernel", "res8v_up_kernel"], ["res8ws_kernel"], "ASEP_SPLIT_WALK=0")
     for n in LEVEL0:
         a, b = res["1"][1][n], res["0"][1][n]
         assert a.shape == b.shape == inter[n].shape, n
