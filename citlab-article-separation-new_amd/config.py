@@ -13,7 +13,7 @@ from typing import List
 @dataclass
 class AruConfig:
     graph: str = "ARU"            # 'U' (plain conv1 + conv2 blocks), 'RU' (residual blocks) or 'ARU' (+ attention), ARU_v1.py:92-97
-    channels: int = 1             # image channels (the attention branch needs 1)
+    channels: int = 1             # image channels: 1 (gray) or, for the graphs without attention (RU / U), 3 (RGB, interleaved [H,W,3])
     n_classes: int = 2
     feat_root: int = 8
     scale_space_num: int = 5
@@ -50,6 +50,14 @@ class AruConfig:
 
     def feat(self, level: int) -> int:
         return self.feat_root * (self.pool_size ** level)
+
+    def check_channels(self):
+        """the image channels the engine serves; raises ``ValueError`` with the reason otherwise (the same rule as ``asep_aru_load``)"""
+        if self.channels not in (1, 3):
+            raise ValueError(f"{self.channels} input channels: 1 (gray) and 3 (RGB) are supported")
+        if self.channels == 3 and self.use_attention:
+            raise ValueError("3-channel input needs a graph without attention (RU or U): the attention graph upsamples its attention "
+                             "map to the input's shape with a one-channel filter (ARU_v1.py:115)")
 
     def to_dict(self):
         return asdict(self)

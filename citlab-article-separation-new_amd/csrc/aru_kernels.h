@@ -1268,6 +1268,85 @@ __global__ __launch_bounds__(256) void conv_c1_kernel(const C1Args a) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// First layer of a colour net (Cin == 3, 3x3 SAME; graphs RU / U): C1Prob::img is the interleaved [H,W,3] page, everything else as in
+// conv_c1_kernel (problem table, optional {mean, 1/std} applied while loading, epilogues, OUTBF roundings).  One thread per output pixel of a
+// 64 x 4 block.  The block first puts its standardised 66 x 6 pixel window into LDS (zero outside the page = SAME padding): the rows are read
+// with consecutive addresses (a pixel's three values lie 12 bytes apart, so a thread reading its own nine values of a row from HBM would issue
+// nine strided loads), and the 27 values of a thread then come from LDS at a stride of three words, which no two lanes of a bank share.
+// The filter [ky][kx][ci][COUT] (aru_pack.h, pack_first_rgb: already rounded to bfloat16 for OUTBF) lies in LDS and is read at one address per
+// wave; the loops over the nine taps are rolled, a tap's 3 * COUT products unrolled (v_pk_fma_f32 on ds_read_b128 filter quads).
+// As compiled for gfx950: COUT 8: 40 VGPRs, 5648 B LDS; COUT 16: 64 VGPRs, 6544 B LDS; no scratch, eight waves per SIMD (DESIGN.md section 4.1
+// has the command, the measured time and the two forms that were tried and dropped).
+// ------------------------------------------------------------------------------------------------
+constexpr int C3_TW = 64, C3_TH = 4;                         // output pixels of a block
+constexpr int C3_ROW = (C3_TW + 2) * 3;                      // floats of a window row
+template <int COUT, bool OUTBF = false>
+__global__ __launch_bounds__(256) void conv_c3_kernel(const C1Args a) {
+    static_assert(C3_TW * C3_TH == 256, "one thread per output pixel");
+    static_assert(COUT % 8 == 0, "whole 16-byte units of bf16 output");
+    __shared__ float sw[27 * COUT + COUT];
+    __shared__ float win[(C3_TH + 2) * C3_ROW];
+    auto rbf = [](float v) { return OUTBF ? __uint_as_float(bf16x2_of(v, 0.f) << 16) : v; };
+    for (int i = threadIdx.x; i < 27 * COUT; i += 256) sw[i] = a.w[i];
+    for (int i = threadIdx.x; i < COUT; i += 256) sw[27 * COUT + i] = a.bias[i];
+    const int pi = prob_of_tile(a, (int)blockIdx.x);
+    const C1Prob& P = a.p[pi];
+    const int tile = blockIdx.x - P.tile_begin;
+    const int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
+    const int x0 = tx * C3_TW, y0 = ty * C3_TH;
+    const int H = P.H, W = P.W;
+    float mean = 0.f, inv = 1.f;
+    if (P.stats) { mean = P.stats[0]; inv = P.stats[1]; }
+    const float* __restrict__ img = P.img;
+    for (int i = threadIdx.x; i < (C3_TH + 2) * C3_ROW; i += 256) {
+        const int r = i / C3_ROW, e = i - r * C3_ROW;        // e = 3 * window column + channel
+        const int gy = y0 - 1 + r, gx3 = (x0 - 1) * 3 + e;   // gx3 = 3 * page column + channel
+        float v = 0.f;
+        if (gy >= 0 && gy < H && gx3 >= 0 && gx3 < 3 * W) v = rbf((img[(size_t)gy * W * 3 + gx3] - mean) * inv);
+        win[i] = v;
+    }
+    __syncthreads();
+    const int lx = threadIdx.x & (C3_TW - 1), ly = threadIdx.x / C3_TW;
+    const int x = x0 + lx, y = y0 + ly;
+    if (x >= W || y >= H) return;
+    float acc[COUT];
+#pragma unroll
+    for (int c = 0; c < COUT; ++c) acc[c] = 0.f;
+#pragma unroll 1
+    for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll 1
+        for (int kx = 0; kx < 3; ++kx) {
+            const float* __restrict__ px = win + (ly + ky) * C3_ROW + (lx + kx) * 3;      // the three channels of a window pixel
+            const float* __restrict__ wt = sw + (ky * 3 + kx) * 3 * COUT;
+#pragma unroll
+            for (int ci = 0; ci < 3; ++ci) {
+                const float v = px[ci];
+#pragma unroll
+                for (int c = 0; c < COUT; ++c) acc[c] = fmaf(v, wt[ci * COUT + c], acc[c]);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < COUT; ++c) {
+        const float s = acc[c] + sw[27 * COUT + c];
+        acc[c] = a.relu ? fmaxf(s, 0.f) : (a.act ? act1(s, a.act) : s);
+    }
+    if constexpr (OUTBF) {
+        unsigned short* o = reinterpret_cast<unsigned short*>(P.out) + ((size_t)y * W + x) * COUT;
+#pragma unroll
+        for (int c = 0; c < COUT; c += 8) {
+            typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+            *reinterpret_cast<u32x4_t*>(o + c) = u32x4_t{bf16x2_of(acc[c], acc[c + 1]), bf16x2_of(acc[c + 2], acc[c + 3]),
+                                                         bf16x2_of(acc[c + 4], acc[c + 5]), bf16x2_of(acc[c + 6], acc[c + 7])};
+        }
+    } else {
+        float* o = P.out + ((size_t)y * W + x) * COUT;
+#pragma unroll
+        for (int c = 0; c < COUT; c += 4) *reinterpret_cast<f32x4*>(o + c) = f32x4{acc[c], acc[c + 1], acc[c + 2], acc[c + 3]};
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Attention CNN head (ARU_v1.py:173-175): 4x4 conv 1->12 + ReLU + 2x2 max pool in one pass.  The 12-channel
 // full-resolution tensor (648 MB per page) is never written: the conv runs on the MFMA with K = the 16 taps
 // (slot 4*kk+r -> tap row kk, tap column r), M = 12 (of 16) output channels, N = 16 pixels of one row, and the

@@ -475,6 +475,25 @@ inline Layer find_direct(const WeightBlob& blob, const std::string& scope) {
     }
     return L;
 }
+// Cin == 3 first layer of a colour net (conv_c3_kernel).  No re-layout: the kernel reads TensorFlow's own [ky][kx][ci][cout] order, which runs
+// in step with the pixel-interleaved page.  This function checks the shape ([3,3,3,cout], cout 8 or 16: the instantiated kernels) and the bias
+// length and, for the bf16 engine, rounds every coefficient to bfloat16 (its first layer multiplies bfloat16 filter and image values in fp32;
+// conv_c1_kernel does that rounding while it fills its LDS filter, here it is done once at load).
+inline std::vector<float> pack_first_rgb(const std::string& scope, const Layer& L, bool bf16) {
+    if (L.w.dims.size() != 4 || L.w.dims[0] != 3 || L.w.dims[1] != 3 || L.w.dims[2] != 3 || (L.w.dims[3] != 8 && L.w.dims[3] != 16)) {
+        set_error("weights: %s must be [3,3,3,8] or [3,3,3,16] for 3-channel input", scope.c_str());
+        throw PackRefusal{ASEP_ERR_UNSUPPORTED};
+    }
+    const FilterView W(L.w);
+    if ((int)L.b.count() != W.cout) {
+        set_error("weights: %s bias has %zu elements, expected %d", scope.c_str(), L.b.count(), W.cout);
+        throw PackRefusal{ASEP_ERR_WEIGHTS};
+    }
+    std::vector<float> pk(L.w.data);
+    if (bf16)
+        for (float& v : pk) v = bfval(f2bf(v));
+    return pk;
+}
 // attPart/conv1 [4][4][1][12] as ONE fp32 A fragment for att_head_kernel: row = cout (12 of 16), kk = ky, r = kx
 inline std::vector<float> pack_att_head(const FilterView& W) {
     std::vector<float> pk(256);

@@ -118,6 +118,8 @@ int aru_endpoint_dev(asep_aru* m, const char* name, const float** d_ptr, int dim
 int aru_endpoint_channels(const asep_aru* m, const char* name);
 // Number of output classes (channels of the logits / probability map) of the model.
 int aru_num_classes(const asep_aru* m);
+// Number of image channels a page of the model has (1 = gray, 3 = interleaved RGB).
+int aru_input_channels(const asep_aru* m);
 // Stream and buffer pool of an asep_post handle (post_engine.hip), for the entry points of other translation units that run
 // on that handle (textblock_engine.hip).
 hipStream_t post_stream(asep_post* p);

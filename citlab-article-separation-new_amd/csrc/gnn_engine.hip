@@ -1167,7 +1167,8 @@ int asep_gnn_forward_visual(asep_gnn* g, int N, int E, const int32_t* edges, con
     const size_t ne = (size_t)E * 2, nug = (size_t)N * ug, nf = edge_feat ? (size_t)E * g->Ed_fed : 0;
     const bool vedges = g->vise_total > 0 && E > 0;
     if (vedges && (!edge_regions || !edge_num_points)) { set_error("asep_gnn_forward_visual: this graph assigns visual features to edges: edge_regions / edge_num_points required"); return ASEP_ERR_ARG; }
-    const size_t nr = relations ? (size_t)R * 2 : 0, no = (size_t)R * g->cfg.num_classes, ni = (size_t)h * w;
+    const size_t nr = relations ? (size_t)R * 2 : 0, no = (size_t)R * g->cfg.num_classes;
+    const size_t ni = (size_t)h * w * std::max(1, aru_input_channels(g->backbone));   // [h,w,C], C the attached backbone's
     const size_t nreg = (size_t)N * 2 * P;
     auto up = [&](const void* src, size_t bytes) -> void* {          // grow-only staging + async copy on the null stream
         void* d = g->host_stage.get(std::max<size_t>(bytes, 4));

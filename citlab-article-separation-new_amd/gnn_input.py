@@ -89,8 +89,46 @@ def resize_bilinear_tf1(image, new_h, new_w):
     return (top * (1 - wy) + bot * wy).astype(np.float32)
 
 
+LOAD_MODE_CHANNELS = {"L": 1, "RGB": 3}                     # input_dataset.py:42-49
+
+
+def load_mode_channels(input_params):
+    """image channels that ``input_params['load_mode']`` feeds (default 'L'); any other mode is a ``ValueError``"""
+    mode = (input_params or {}).get("load_mode", DEFAULT_INPUT_PARAMS["load_mode"])
+    if mode not in LOAD_MODE_CHANNELS:
+        raise ValueError(f"input_params load_mode={mode!r}: 'L' (gray) and 'RGB' are served")
+    return LOAD_MODE_CHANNELS[mode]
+
+
+def check_load_mode(input_params, graph_cfg):
+    """``load_mode`` against the image channels of the graph's visual backbone: a relation net trained on colour pages reads three
+    channels, one trained on gray pages one -- feeding the other kind is refused here, before the model goes to the device."""
+    fed = load_mode_channels(input_params)
+    if not graph_cfg.visual_dims:
+        return
+    want = graph_cfg.backbone_cfg().channels
+    if fed != want:
+        mode = (input_params or {}).get("load_mode", DEFAULT_INPUT_PARAMS["load_mode"])
+        raise ValueError(f"--input_params load_mode={mode} feeds {fed} image channel(s), the graph's backbone reads {want}: "
+                         f"pass load_mode={'RGB' if want == 3 else 'L'}")
+
+
+def load_page_rgb(img_path):
+    """input_dataset.py:279 with ``load_mode=RGB``: the scan as Pillow's ``convert('RGB')`` -> uint8 [H,W,3] in R, G, B order (the order
+    TensorFlow's decoders give too).  A plain 8-bit RGB png comes from image_io's fast decode, which returns OpenCV's B, G, R order and is
+    turned round here; every other file goes through Pillow."""
+    from PIL import Image
+    from . import image_io
+    image = image_io._load_png_plain(img_path) if str(img_path).lower().endswith(".png") else None
+    if image is not None and image.ndim == 3:
+        return np.ascontiguousarray(image[:, :, ::-1])
+    with Image.open(img_path) as im:
+        return np.asarray(im.convert("RGB"))
+
+
 class InputGNN(object):
-    """``InputGNN(flags)`` with ``flags.input_params`` (dict) and ``flags.image_input`` (bool)."""
+    """``InputGNN(flags)`` with ``flags.input_params`` (dict) and ``flags.image_input`` (bool).  ``input_params['load_mode']``: 'L'
+    feeds the page as one gray channel, 'RGB' as three (R, G, B), each resized like the gray one."""
 
     def __init__(self, flags):
         self._flags = flags
@@ -102,6 +140,7 @@ class InputGNN(object):
         self.input_params.update(given)
         if not (self.input_params["resize_max_dim"] > 0 and self.input_params["resize_min_dim"] > 0):
             raise ValueError("Error in resizing parameters for input image.")
+        self.img_channels = load_mode_channels(self.input_params)
 
     def _masked(self, feats, which):
         mask = self.input_params[f"{which}_input_feature_mask"]
@@ -115,7 +154,9 @@ class InputGNN(object):
 
     def feed_from_json(self, json_path, image=None, targets=None):
         """-> feed dict keyed by the exported placeholder names (batch size 1), ready for ``GnnSession.run``.  ``targets`` (a dict)
-        receives the json's ``gt_relations`` [G, 3] and ``gt_num_relations``: what an evaluation scores the output against."""
+        receives the json's ``gt_relations`` [G, 3] and ``gt_num_relations``: what an evaluation scores the output against.
+        ``image``: the decoded page -- [H,W] gray for ``load_mode=L``, [H,W,3] in R, G, B order for ``load_mode=RGB``
+        (:func:`load_page_rgb`)."""
         d = get_input_and_target_from_json(json_path)
         if targets is not None:
             targets["gt_relations"] = d["gt_relations"].reshape(-1, 3)
@@ -132,6 +173,8 @@ class InputGNN(object):
             ef = d["edge_features"].reshape(int(d["num_interacting_nodes"]), -1)
             feed["edge_features:0"] = self._masked(ef, "edge").astype(np.float32)[None]
         if getattr(self._flags, "image_input", False) and image is not None:
+            if self.img_channels == 3 and (np.ndim(image) != 3 or np.shape(image)[2] != 3):
+                raise ValueError(f"load_mode=RGB feeds [H,W,3] pages, got {np.shape(image)}")
             img = np.asarray(image)                                  # uint8 as decoded, or float32 (values 0..255 either way)
             if img.ndim == 2:
                 img = img[:, :, None]

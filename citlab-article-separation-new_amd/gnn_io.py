@@ -227,7 +227,8 @@ def gnn_forward(graph: GnnGraph, num_nodes, edges, node_feat, edge_feat, relatio
 
 def gnn_forward_visual(graph: GnnGraph, num_nodes, edges, node_feat, edge_feat, image, regions, num_points,
                        relations=None, device=0, edge_regions=None, edge_num_points=None):
-    """graph_relation.py:84-139 + GNN: image float32 [h,w(,1)] as fed (0..255), regions [N,2,P] relative
+    """graph_relation.py:84-139 + GNN: image float32 [h,w(,1)] as fed (0..255; [h,w,3] in R, G, B order when the backbone was trained
+    with ``load_mode=RGB``, a mismatch of the channel counts is a ``ValueError``), regions [N,2,P] relative
     coordinates, num_points [N] -> probabilities [R, num_classes].  ``edge_regions`` [E,2,P] / ``edge_num_points`` [E]: the
     interactions' regions of a graph with ``visual_edges`` (graph_relation.py:141-172)."""
     lib = _lib.init_device(device)
@@ -238,11 +239,13 @@ def gnn_forward_visual(graph: GnnGraph, num_nodes, edges, node_feat, edge_feat, 
     u = np.ascontiguousarray(node_feat, dtype=np.float32).reshape(N, cfg.node_feature_dim)
     ef = np.ascontiguousarray(edge_feat, dtype=np.float32).reshape(E, -1) if edge_feat is not None else None
     img = np.asarray(image, dtype=np.float32)
-    if img.ndim == 3:
-        if img.shape[2] != 1:
-            raise ValueError("the ARU_v1 backbone takes one image channel")
+    chans = cfg.backbone_cfg().channels
+    got = img.shape[2] if img.ndim == 3 else 1
+    if img.ndim not in (2, 3) or got != chans:
+        raise ValueError(f"this graph's backbone takes {chans} image channel(s), the image {img.shape} has {got}")
+    if img.ndim == 3 and chans == 1:
         img = img[:, :, 0]
-    img = np.ascontiguousarray(img)
+    img = np.ascontiguousarray(img)                          # [h,w], or the interleaved [h,w,3] of a colour backbone
     reg = np.ascontiguousarray(regions, dtype=np.float32)
     if reg.ndim != 3 or reg.shape[0] != N or reg.shape[1] != 2:
         raise ValueError(f"visual_regions_nodes must be [N, 2, P], got {reg.shape}")

@@ -360,9 +360,9 @@ def _feed_arrays(feed, cfg):
         if "image_shape:0" in feed:
             ish = np.asarray(feed["image_shape:0"]).reshape(-1, 3)[0]
             image = image[:int(ish[0]), :int(ish[1])]
-        if image.ndim == 3:
+        if image.ndim == 3 and cfg.backbone_cfg().channels == 1:
             image = image[:, :, 0]
-        a["image"] = np.ascontiguousarray(image)
+        a["image"] = np.ascontiguousarray(image)             # [h,w], or [h,w,3] for a colour backbone
         a["regions"] = np.ascontiguousarray(np.asarray(feed["visual_regions_nodes:0"], np.float32)[0][:N])
         a["npts"] = np.ascontiguousarray(np.asarray(feed["num_points_visual_regions_nodes:0"], np.int32)[0][:N])
         if cfg.visual_edges:
@@ -401,7 +401,7 @@ class LavGNN(object):
         out = torch.empty((N * N, cfg.num_classes), dtype=torch.float32, device=dev)
         stream = _stream(self.device)
         if cfg.visual_dims:
-            h, w = a["image"].shape
+            h, w = a["image"].shape[:2]
             page = dict(N=N, E=E, R=N * N, d_edges=ptr(t["edges"]), d_node_feat=ptr(t["u"]), d_edge_feat=ptr(t["ef"]),
                         d_image=ptr(t["image"]), d_regions=ptr(t["regions"]), d_num_points=ptr(t["npts"]),
                         d_edge_regions=ptr(t["eregions"]), d_edge_num_points=ptr(t["enpts"]), d_relations=None,
@@ -458,6 +458,8 @@ class LavGNN(object):
         graph = gnn_io.load_graph(self._pb_path, visual_layers=flags.visual_layers or None)
         if graph.cfg.visual_dims and not flags.image_input:
             raise ValueError("this model was exported with image_input: pass --image_input True")
+        from .gnn_input import check_load_mode
+        check_load_mode(flags.input_params, graph.cfg)               # before the model goes to the device
         if graph.cfg.num_classes != flags.num_classes:
             raise ValueError(f"--num_classes {flags.num_classes}, the model has {graph.cfg.num_classes}")
         tm = self.timings = {"net_s": 0.0, "append_s": 0.0, "finish_s": 0.0, "prepare_wait_s": 0.0, "pages": 0}

@@ -54,6 +54,7 @@ class AruGraph:
         if key not in self._handles:
             lib = _lib.init_device(device_id)
             c = self.cfg
+            c.check_channels()
             if c.compute_dtype not in COMPUTE_DTYPES:
                 raise ValueError(f"compute_dtype must be one of {sorted(COMPUTE_DTYPES)}, got {c.compute_dtype!r}")
             cfg = _lib.AruCfg(c.channels, c.n_classes, c.feat_root, c.scale_space_num, c.res_depth,
@@ -175,7 +176,7 @@ def _pinned_pool(dev, lib):
 
 
 def get_net_output(image, pb_graph: AruGraph, gpu_device="0"):
-    """helper:56-72: image [H,W] (or [1,H,W,1]) -> net output [H,W,n_classes] float32."""
+    """helper:56-72: image [H,W] (or [1,H,W,1]; [H,W,3] / [1,H,W,3] for a colour net) -> net output [H,W,n_classes] float32."""
     out, _, _ = get_net_output_fused(image, pb_graph, gpu_device, want_u8=False, threshold=None)
     return out
 
@@ -193,15 +194,16 @@ def get_net_output_fused(image, pb_graph: AruGraph, gpu_device="0", want_u8=True
         if image.shape[2] != pb_graph.cfg.channels:
             raise ValueError(f"expected {pb_graph.cfg.channels} channel(s), got {image.shape[2]}")
         image = image[:, :, 0] if pb_graph.cfg.channels == 1 else image
-    if image.ndim != 2:
-        raise ValueError(f"unsupported image shape {image.shape}")
-    H, W = image.shape
+    chans = pb_graph.cfg.channels
+    if image.ndim != (2 if chans == 1 else 3):
+        raise ValueError(f"unsupported image shape {image.shape} for a net with {chans} input channel(s)")
+    H, W = image.shape[:2]
     ncls = pb_graph.cfg.n_classes
     dev = _device_of(gpu_device)
     lib = _lib.init_device(dev)
     pool = _pinned_pool(dev, lib)
     # the feed casts float64 -> float32: done while copying into a page-locked staging buffer (one pass over the page)
-    img = pool.array((H, W), np.float32)
+    img = pool.array((H, W) if chans == 1 else (H, W, chans), np.float32)   # a colour page: interleaved [H,W,3]
     _parallel_copy(img, image)
     out = pool.array((H, W, ncls), np.float32)
     u8 = pool.array((H, W, ncls), np.uint8) if want_u8 else None

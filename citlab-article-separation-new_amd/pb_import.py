@@ -319,6 +319,7 @@ def aru_from_constants(nodes, num_scales_att=None, apply_softmax=None):
                     feat_root=int(w0.shape[3]), scale_space_num=levels, res_depth=3 if plain_u else res_depth, activation_name=activation_name,
                     num_scales_att=int(num_scales_att), filter_size=int(w0.shape[0]),
                     mvn=any("aru_net/mvn" in n["name"] for n in nodes), apply_softmax=bool(apply_softmax))
+    _check_channels(cfg)
     tensors = OrderedDict()
     for name, shape in aru_tensor_shapes(cfg).items():
         t = _find(consts, name)
@@ -328,6 +329,14 @@ def aru_from_constants(nodes, num_scales_att=None, apply_softmax=None):
             raise IOError(f"{name}: shape {tuple(t.shape)} in the graph, {tuple(shape)} expected")
         tensors[name] = np.ascontiguousarray(t, dtype=np.float32)
     return tensors, cfg
+
+
+def _check_channels(cfg):
+    """the first filter's input channels against what the engine serves (AruConfig.check_channels), as an import error"""
+    try:
+        cfg.check_channels()
+    except ValueError as e:
+        raise IOError(f"the graph's first convolution reads {cfg.channels} image channel(s): {e}")
 
 
 # ----------------------------------------------------------------------------------------------
@@ -706,6 +715,7 @@ def aru_from_topology(nodes, input_name="inImg", output_name="output"):
     cfg = AruConfig(graph="ARU" if att else ("U" if plain_u else "RU"), channels=channels, n_classes=last.cout, feat_root=feat_root,
                     scale_space_num=n_levels, res_depth=3 if plain_u else res_depth, num_scales_att=n_scales, filter_size=k, mvn=mvn,
                     apply_softmax=softmax, activation_name=activation_name)
+    _check_channels(cfg)
     if activation_name != "relu" and not plain_u:
         # ARU_v1.py:214,268: the activation behind conv1 of a residual block is layers.relu in every variant -- one Relu op per
         # block and pyramid scale, and no other

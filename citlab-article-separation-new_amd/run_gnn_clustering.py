@@ -92,12 +92,16 @@ def _prepare_feed(input_fn, flags, json_path, targets=None):
         from . import image_io
         from .path_util import get_img_from_json_path
         img_path = get_img_from_json_path(json_path)
-        # input_dataset.py:279-280: the scan as mode "L".  A plain 8-bit GRAY png is that already (image_io's fast decode);
-        # colour files go through Pillow's own luma conversion, which is not OpenCV's
-        image = image_io._load_png_plain(img_path) if img_path.lower().endswith(".png") else None
-        if image is None or image.ndim != 2:
-            with Image.open(img_path) as im:
-                image = np.asarray(im.convert("L"))                      # uint8; widened after the resize's gathers
+        if input_fn.img_channels == 3:                                   # load_mode=RGB: [H,W,3] in R, G, B order
+            from .gnn_input import load_page_rgb
+            image = load_page_rgb(img_path)
+        else:
+            # input_dataset.py:279-280: the scan as mode "L".  A plain 8-bit GRAY png is that already (image_io's fast decode);
+            # colour files go through Pillow's own luma conversion, which is not OpenCV's
+            image = image_io._load_png_plain(img_path) if img_path.lower().endswith(".png") else None
+            if image is None or image.ndim != 2:
+                with Image.open(img_path) as im:
+                    image = np.asarray(im.convert("L"))                  # uint8; widened after the resize's gathers
     feed = input_fn.feed_from_json(json_path, image, targets)
     n = feed["node_features:0"].shape[1] if "node_features:0" in feed else int(feed["num_nodes:0"][0])
     return feed, n
@@ -127,6 +131,8 @@ def _load_session(flags, device):
     graph = gnn_io.load_graph(resolve_model_path(flags), visual_layers=flags.visual_layers or None)
     if graph.cfg.visual_dims and not flags.image_input:
         raise ValueError("this model was exported with image_input: pass --image_input True")
+    from .gnn_input import check_load_mode
+    check_load_mode(flags.input_params, graph.cfg)           # load_mode against the backbone's channels, before the device sees the model
     return gnn_io.GnnSession(graph, device)
 
 

@@ -65,7 +65,7 @@ int asep_host_unregister(void* p);
 /* ---- ARU-Net (ARU_v1.py:35-43 hyper-parameters) ---------------------------------------------- */
 typedef struct asep_aru_cfg {
     int32_t struct_size;       /* = sizeof(asep_aru_cfg) of the header the caller was compiled / written against */
-    int32_t channels;          /* image channels, 1 */
+    int32_t channels;          /* image channels: 1 (gray), or 3 (R, G, B) for the graphs without attention (use_attention 0: RU, U) */
     int32_t n_classes;
     int32_t feat_root;         /* 8 */
     int32_t scale_space_num;   /* 5 */
@@ -91,7 +91,12 @@ typedef struct asep_aru asep_aru;
 asep_aru* asep_aru_load(const void* weight_blob, size_t nbytes, const asep_aru_cfg* cfg);
 void asep_aru_free(asep_aru* m);
 
-/* Host-buffer call == get_net_output(): img_hw is H*W*channels floats (row major, values as fed to
+/* Page layout of every asep_aru_forward* entry point: H*W*channels floats, row major, the channels of a pixel interleaved ([H,W] for a gray
+ * net, [H,W,3] in R, G, B order for cfg.channels == 3), values as fed to 'inImg:0'.  With cfg.mvn the page is standardised with the mean and
+ * the standard deviation of all H*W*channels values (layers.py:672-711).  asep_aru_load refuses cfg.channels == 3 together with
+ * use_attention (ARU_v1.py:115 upsamples the attention map to the input's shape with a one-channel filter) and every other channel count.
+ *
+ * Host-buffer call == get_net_output(): img_hw is H*W*channels floats (row major, values as fed to
  * 'inImg:0'); out_hwc receives H*W*n_classes floats ('output:0'[0]).  The optional u8 outputs are
  * the two consumers that directly follow the net in the reference:
  *   out_u8   = uint8(prob*255)               (truncation, separator_net_post_processor.py:147)
@@ -113,7 +118,7 @@ int asep_aru_forward_batch_dev(asep_aru* m, int n_pages, const float* const* d_i
                                float* const* d_outs, uint8_t* const* d_out_u8, uint8_t* const* d_out_mask,
                                float threshold, void* stream);
 /* ABI 6: asep_aru_forward_batch_dev for pages of DIFFERENT sizes: H[b] x W[b] is page b's size, d_imgs[b] / d_outs[b] / d_out_u8[b] /
- * d_out_mask[b] its buffers ([H[b], W[b]] fp32 in; [H[b], W[b], n_classes] out).  Replaces the reference's page-by-page loop over scans of
+ * d_out_mask[b] its buffers ([H[b], W[b](, 3)] fp32 in; [H[b], W[b], n_classes] out).  Replaces the reference's page-by-page loop over scans of
  * arbitrary size (run_net_post_processing.py:61-82 -> get_net_output per scan, ARU_v1.py:64 `inImg` [1, None, None, 1]); results are those
  * of the single-page calls bit for bit.  The pages of a call share every layer's launches. */
 int asep_aru_forward_batch_dev2(asep_aru* m, int n_pages, const float* const* d_imgs, const int32_t* H, const int32_t* W,
@@ -221,7 +226,8 @@ double asep_gnn_flops(const asep_gnn* g, int N, int E_corrected, int R);
 int asep_gnn_attach_backbone(asep_gnn* g, asep_aru* backbone, int n_maps, const char* const* endpoint_names);
 
 /* run_gnn_clustering.py:259-269 with the image feeds: node_feat [N, node_feature_dim - visual dims],
- * image float32 [h,w] (0..255 as fed, input_dataset.py:279-280), regions [N,2,P] relative coordinates (row 0 = x,
+ * image float32 [h,w] -- [h,w,3] in R, G, B order when the attached backbone reads three channels (a net trained with load_mode=RGB,
+ * input_dataset.py:42-49) -- (0..255 as fed, input_dataset.py:279-280), regions [N,2,P] relative coordinates (row 0 = x,
  * row 1 = y), num_points [N].  Backbone -> ROI max -> compression -> concat -> GNN -> probabilities [R, classes].
  * edge_regions [E,2,P] / edge_num_points [E] ('visual_regions_edges', 'num_points_visual_regions_edges'): the regions of the
  * interactions of a graph exported with assign_visual_features_to_edges (cfg.visual_edge_dims > 0; NULL otherwise): their
@@ -232,7 +238,7 @@ int asep_gnn_forward_visual(asep_gnn* g, int N, int E, const int32_t* edges, con
                             const int32_t* num_points, const float* edge_regions, const int32_t* edge_num_points,
                             int R, const int32_t* relations, float* probs_out);
 
-/* The same with every array already in HBM (image [h,w] float32 included), launched on `stream` without any host
+/* The same with every array already in HBM (image [h,w] or [h,w,3] float32 included), launched on `stream` without any host
  * synchronisation: backbone, ROI kernels and the graph are queued back to back.  Index arrays are not validated here:
  * an edge that names a node outside 0..N-1 is ignored, a relation that does yields NaN probabilities. */
 int asep_gnn_forward_visual_dev(asep_gnn* g, int N, int E, const int32_t* d_edges, const float* d_node_feat,
@@ -244,14 +250,14 @@ int asep_gnn_forward_visual_dev(asep_gnn* g, int N, int E, const int32_t* d_edge
 /* A batch of pages through the visual net (bench.py's step; a GPU owner that holds several decoded pages): the backbones
  * of all pages run as ONE grouped forward (asep_aru_forward_batch_dev: every layer is one launch over the page list, so the
  * small 683 x 1024 images fill the chip together), then ROI kernels + graph per page, all queued on `stream`, no host
- * synchronisation.  Every image is [h,w] float32 and every region array [N,2,P]; the other sizes are per page.
+ * synchronisation.  Every image is [h,w] (colour backbone: [h,w,3]) float32 and every region array [N,2,P]; the other sizes are per page.
  * asep_gnn_get_node_features afterwards returns page 0's features. */
 typedef struct asep_gnn_page {
     int32_t N, E, R;
     const int32_t* d_edges;        /* [E,2] */
     const float* d_node_feat;      /* [N, node_feature_dim - visual dims] */
     const float* d_edge_feat;      /* [E, edge_feature_dim] */
-    const float* d_image;          /* [h,w] */
+    const float* d_image;          /* [h,w], or [h,w,3] for a 3-channel backbone */
     const float* d_regions;        /* [N,2,P] */
     const int32_t* d_num_points;   /* [N] */
     const float* d_edge_regions;   /* [E,2,P] or NULL (cfg.visual_edge_dims == 0) */

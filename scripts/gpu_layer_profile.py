@@ -11,11 +11,12 @@ from citlab_article_separation_new_amd import net_post_processing_helper as help
 H, W = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (4500, 3000)
 dtype = sys.argv[3] if len(sys.argv) > 3 else 'f32'
 passes = int(sys.argv[4]) if len(sys.argv) > 4 else 5
-kw = json.loads(os.environ.get("ASEP_LAYER_PROFILE_CFG", "{}"))          # e.g. '{"activation_name": "elu"}' for the graph variants
+kw = json.loads(os.environ.get("ASEP_LAYER_PROFILE_CFG", "{}"))          # e.g. '{"activation_name": "elu"}' for the graph variants,
+                                                                         # '{"graph": "RU", "channels": 3}' for a colour net
 cfg = AruConfig(compute_dtype=dtype, **kw)
 g = helper.AruGraph(init_aru_weights(cfg, 1234), cfg)
 lib = _lib.init_device(0); h = g.handle(0)
-img = torch.rand(H, W, device='cuda'); out = torch.empty(H, W, cfg.n_classes, device='cuda')
+img = torch.rand(*((H, W) if cfg.channels == 1 else (H, W, cfg.channels)), device='cuda'); out = torch.empty(H, W, cfg.n_classes, device='cuda')
 s = torch.cuda.current_stream().cuda_stream
 NP = int(os.environ.get("ASEP_LAYER_PROFILE_PAGES", "1"))                # pages per call (the bench step runs 4 pages per launch)
 outs = [torch.empty(H, W, cfg.n_classes, device='cuda') for _ in range(NP)]
