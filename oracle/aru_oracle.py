@@ -3,9 +3,14 @@
 Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg may import
 this module.  The product path (``citlab-article-separation-new_amd``) never does.
 
-PARITY UNPINNED: the reference model path needs TensorFlow 1.12-1.14 and the frozen ``.pb``
-files, neither of which exists here and the reference has no tests or
-golden vectors for it.  This file is a restatement of the reference *graph definition*
+PARITY, what is pinned: the WIRING -- which layer follows which, every variable's scope name and shape, the weight sharing across
+the scales, the concat / split orders, which activation sits where.  tests/test_oracle_wiring.py holds both implementations below, at
+1e-6, to every end point the reference's own ``ARU_v1_CNN.infer`` produced when its graph-definition Python was executed on an eager
+float64 stand-in for TensorFlow (tests/golden/make_model_wiring_golden.py, tests/golden/model_wiring_aru.npz).
+
+PARITY UNPINNED, still: the semantics of the TensorFlow ops (SAME padding, the crop of conv2d_transpose, the avg-pool divisor) --
+restated here from the TF 1.x documentation and, independently, in that stand-in -- and the frozen
+``.pb`` nets themselves: TensorFlow 1.12-1.14 and the files do not exist here.  The graph definition restated is
 
     article_separation/backbones/ARU_v1.py:62-294            (_create_aru_net, _attCNN, _detCNN)
     article_separation/gnn/model/graph_util/layers.py:191-247 (conv2d), :342-367 (deconv2d),
@@ -169,8 +174,8 @@ def _plain_block(x, w, prefix, act):
     return act(conv2d_same(c1, w[prefix + "/conv2/weights"], w[prefix + "/conv2/biases"]))
 
 
-def det_cnn(x, w, cfg, end_points=None, sc=0):
-    """ARU_v1.py:186-294."""
+def det_cnn(x, w, cfg, end_points=None, sc=0, pool_end_points=False):
+    """ARU_v1.py:186-294.  ``pool_end_points``: also record the reference's ``*_maxpool`` end points (ARU_v1.py:239-240)."""
     n = cfg.scale_space_num
     act = activation_fn(getattr(cfg, "activation_name", "relu"))
     residual = getattr(cfg, "use_residual", True)
@@ -183,6 +188,8 @@ def det_cnn(x, w, cfg, end_points=None, sc=0):
         if end_points is not None:
             end_points[f"scale_{sc}_unet_down_{l}_conv"] = d
         u = max_pool2(d) if l < n - 1 else d
+        if pool_end_points and end_points is not None and l < n - 1:
+            end_points[f"scale_{sc}_unet_down_{l}_maxpool"] = u
     for l in range(n - 2, -1, -1):
         p = f"aru_net/featMapG/unet_up_{l}"
         skip = skips[l]
@@ -209,8 +216,9 @@ def att_cnn(x, w, act=relu):
     return y
 
 
-def forward_numpy(image, w, cfg, dtype=np.float32, return_intermediates=False):
+def forward_numpy(image, w, cfg, dtype=np.float32, return_intermediates=False, pool_end_points=False):
     """image [H,W] or [H,W,C] -> probabilities (or logits if not cfg.apply_softmax) [H,W,n_classes].
+    ``pool_end_points``: the intermediates also hold the reference's ``scale_<s>_unet_down_<l>_maxpool`` end points.
 
     ARU_v1.py:62-163."""
     x = np.asarray(image, dtype=dtype)
@@ -232,11 +240,11 @@ def forward_numpy(image, w, cfg, dtype=np.float32, return_intermediates=False):
             inter[f"att_{s}"] = a
             att.append(upsample_simple(a, (H, W), up)[:, :, :1])   # out shape = input shape (1 ch)
             up *= 2
-    feats = [det_cnn(x, w, cfg, inter, 0)]
+    feats = [det_cnn(x, w, cfg, inter, 0, pool_end_points)]
     if cfg.use_attention:
         up = 1
         for s in range(1, cfg.num_scales_att):                     # ARU_v1.py:129-138
-            f = det_cnn(scales[s], w, cfg, inter, s)
+            f = det_cnn(scales[s], w, cfg, inter, s, pool_end_points)
             up *= 2
             feats.append(upsample_simple(f, (H, W), up))
         a = softmax(np.concatenate(att, axis=2), axis=2)           # over the scale axis
@@ -289,8 +297,12 @@ def _t_upsample(x, out_hw, up, torch):
     return s[:, :, iy][:, :, :, ix]                                # [1,1,Ho,Wo]; caller broadcasts
 
 
-def forward_torch(image, w, cfg, num_threads=None, dtype=None, return_intermediates=False, bn=None, storage="f32", teacher=None):
-    """``bn``: optional {layer scope: (gamma, beta, moving_mean, moving_variance, epsilon)} -- inference-mode batch
+def forward_torch(image, w, cfg, num_threads=None, dtype=None, return_intermediates=False, bn=None, storage="f32", teacher=None,
+                  pool_end_points=False):
+    """``pool_end_points``: the intermediates also hold the reference's ``scale_<s>_unet_down_<l>_maxpool`` end points (ARU_v1.py:239-240;
+    recorded only, never teacher-forced).
+
+    ``bn``: optional {layer scope: (gamma, beta, moving_mean, moving_variance, epsilon)} -- inference-mode batch
     normalisation applied UNFOLDED between bias and activation (layers.py:241-242 ``batchNorm`` switch); the importer
     folds it into the weights, this is the independent evaluation it is compared with.
 
@@ -389,6 +401,8 @@ def forward_torch(image, w, cfg, num_threads=None, dtype=None, return_intermedia
                 d = force(f"scale_{sc}_unet_down_{l}_conv", block(u, f"aru_net/featMapG/unet_down_{l}"))
                 skips.append(d)
                 u = F.max_pool2d(d, 2, 2, ceil_mode=True) if l < n - 1 else d
+                if pool_end_points and l < n - 1:
+                    inter[f"scale_{sc}_unet_down_{l}_maxpool"] = u
             for l in range(n - 2, -1, -1):
                 p = f"aru_net/featMapG/unet_up_{l}"
                 skip = skips[l]

@@ -3,8 +3,14 @@
 Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg may import
 this module.
 
-PARITY UNPINNED for the float path: the reference graph needs TensorFlow 1.x and the frozen
-``mixed_gnn_vn7e*.pb`` (absent); the reference has no tests for it.  This is a numpy restatement of
+PARITY of the float path, what is pinned: the WIRING of the GNN -- edge correction, the order of the edge-MLP input blocks, the heads,
+the chunked attention pairing, the aggregation, the LSTM gates, the output types, every variable's scope name and shape.
+tests/test_oracle_wiring.py holds ``forward`` at 1e-6 to the ``gnn_node_features`` the reference's own ``GraphGNN.infer`` produced when its
+graph-definition Python was executed on an eager float64 stand-in for TensorFlow (tests/golden/make_model_wiring_golden.py,
+tests/golden/model_wiring_gnn.npz).  PARITY UNPINNED, still: the semantics of the TensorFlow ops (tf.sparse.softmax / reduce_max over the
+stored entries, tf.sets.difference's order, ...), restated here and, independently, in that stand-in; the pair classifier and the
+visual branch (graph_relation.py, not run by the maker); and the frozen ``mixed_gnn_vn7e*.pb`` (absent, as is TensorFlow 1.x).
+This is a numpy restatement of
 
     article_separation/gnn/model/graph_util/misc.py:7-151     check_and_correct_interacting_nodes
     article_separation/gnn/model/graph/graph_gnn.py:46-167     GraphGNN.infer (batch size 1)
@@ -91,8 +97,10 @@ def _transposed_sparse_softmax_values(a_un, frm, to, N):
 
 
 def forward(num_nodes, edges, node_feat, edge_feat, relations, w, cfg, dtype=np.float32,
-            return_hidden=False):
-    """== sess.run('output_belong_to_same_instance:0') at batch size 1 -> probs [R, num_classes]."""
+            return_hidden=False, return_node_output=False):
+    """== sess.run('output_belong_to_same_instance:0') at batch size 1 -> probs [R, num_classes].
+    ``return_hidden``: also the final hidden states h [N, hidden_dim]; ``return_node_output``: also (behind them) what GraphGNN.infer
+    returns as 'gnn_node_features' and the pair classifier reads -- h, h + x W or [h | x], by ``output_type`` (graph_gnn.py:158-167)."""
     N = int(num_nodes)
     w = {k: v.astype(dtype) for k, v in w.items()}
     u = np.asarray(node_feat, dtype=dtype).reshape(N, -1)
@@ -190,9 +198,8 @@ def forward(num_nodes, edges, node_feat, edge_feat, relations, w, cfg, dtype=np.
                           + w[f"{CLS}/fully_connected_layer_h{i}/bias"], 0)
     logits = feat @ w[f"{CLS}/fully_connected_logit_layer_out/weights"] + w[f"{CLS}/fully_connected_logit_layer_out/bias"]
     probs = _softmax(logits).astype(dtype)
-    if return_hidden:
-        return probs, h
-    return probs
+    out = (probs,) + ((h,) if return_hidden else ()) + ((hc,) if return_node_output else ())
+    return out if len(out) > 1 else probs
 
 
 def visual_node_features(image, regions, num_points, w, cfg, return_maps=False, scope_kind="node"):

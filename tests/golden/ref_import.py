@@ -11,7 +11,7 @@ import sys
 import types
 
 STUBBED = ("tensorflow", "cv2", "lxml", "cssutils", "shapely", "gensim", "kneed", "rasterio", "textdistance", "jpype", "jpype1", "pythonrc",
-           "fiona", "skimage", "imageio", "nltk", "flair", "spacy", "fasttext", "Levenshtein", "editdistance", "tqdm_missing", "absl")
+           "fiona", "skimage", "imageio", "nltk", "flair", "spacy", "fasttext", "Levenshtein", "editdistance", "tqdm_missing", "absl", "tensorboard")
 
 
 class _Placeholder:
