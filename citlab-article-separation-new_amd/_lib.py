@@ -16,7 +16,7 @@ class AsepError(RuntimeError):
 
 
 MLP_MAX_HIDDEN = 4       # GNN_MLP_MAX (csrc/gnn_kernels.h): hidden layers of the interaction / attention / classifier MLPs
-ABI_VERSION = 6          # ASEP_ABI_VERSION of include/asep_hip.h this table was written against
+ABI_VERSION = 7          # ASEP_ABI_VERSION of include/asep_hip.h this table was written against
 
 
 class _SizedCfg(C.Structure):
@@ -45,6 +45,7 @@ class ClusterSetting(C.Structure):
     _fields_ = [("min_neighbors", C.c_int32), ("assign_noise", C.c_int32), ("conf_thr", C.c_double), ("agree_thr", C.c_double)]
 
 
+RESIZE_MODES = {"keep": 0, "luma": 1}                                # ASEP_RESIZE_* of include/asep_hip.h
 CLUSTER_METHODS = {"dbscan": 0, "dbscan_std": 1, "greedy": 2}       # ASEP_CLUSTER_* of include/asep_hip.h
 
 
@@ -105,6 +106,8 @@ SIGNATURES = {
     "asep_prep_scaled_size": (C.c_int, [C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "asep_prep_scale_gray": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P]),
     "asep_prep_scale_gray_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P]),
+    "asep_prep_resize_tf1": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "asep_prep_resize_tf1_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "asep_post_cc_filter": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "asep_post_morph_rect": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "asep_post_separator": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -291,6 +291,45 @@ int prep_dev(asep_post* p, hipStream_t st, const uint8_t* d_img, int H, int W, i
     return ASEP_OK;
 }
 
+// gnn_input.resize_bilinear_tf1 on the device: `fn` names the entry point in the messages
+int resize_tf1_check(const char* fn, const void* p, const void* img, const void* out, int H, int W, int C, int mode, int h, int w) {
+    if (!p || !img || !out) {
+        set_error("%s: null argument (%s)", fn, !p ? "handle" : !img ? "img" : "out");
+        return ASEP_ERR_ARG;
+    }
+    if (C != 1 && C != 3) {
+        set_error("%s: C must be 1 or 3 (got %d)", fn, C);
+        return ASEP_ERR_ARG;
+    }
+    if (mode != ASEP_RESIZE_KEEP && mode != ASEP_RESIZE_LUMA) {
+        set_error("%s: mode must be ASEP_RESIZE_KEEP (0) or ASEP_RESIZE_LUMA (1) (got %d)", fn, mode);
+        return ASEP_ERR_ARG;
+    }
+    if (mode == ASEP_RESIZE_LUMA && C != 3) {
+        set_error("%s: mode luma reads C = 3 (R, G, B) pages (got C = %d)", fn, C);
+        return ASEP_ERR_ARG;
+    }
+    if (H < 1 || W < 1 || (size_t)H * W > 0x7fffffffull) {
+        set_error("%s: unsupported source size H x W = %d x %d", fn, H, W);
+        return ASEP_ERR_ARG;
+    }
+    if (h < 1 || w < 1 || (size_t)h * w > 0x7fffffffull) {
+        set_error("%s: unsupported target size h x w = %d x %d", fn, h, w);
+        return ASEP_ERR_ARG;
+    }
+    return ASEP_OK;
+}
+
+int resize_tf1_dev(hipStream_t st, const uint8_t* d_img, int H, int W, int C, int mode, int h, int w, float* d_out) {
+    const float sy = (float)((double)H / (double)h), sx = (float)((double)W / (double)w);
+    const unsigned nb = blocks_for((size_t)h * w);
+    if (mode == ASEP_RESIZE_LUMA) prep_resize_tf1_kernel<3, true><<<nb, 256, 0, st>>>(d_img, H, W, sy, sx, d_out, h, w);
+    else if (C == 3) prep_resize_tf1_kernel<3, false><<<nb, 256, 0, st>>>(d_img, H, W, sy, sx, d_out, h, w);
+    else prep_resize_tf1_kernel<1, false><<<nb, 256, 0, st>>>(d_img, H, W, sy, sx, d_out, h, w);
+    ASEP_HIP_CHECK(hipGetLastError());
+    return ASEP_OK;
+}
+
 int swt_dev(asep_post* p, hipStream_t st, const uint8_t* d_gray, int H, int W, uint8_t* d_out, int32_t* d_d2,
             int** d_thr_out) {
     const size_t n = (size_t)H * W;
@@ -397,6 +436,29 @@ int asep_prep_scale_gray(asep_post* p, const uint8_t* img, int H, int W, int C, 
     if (out_image) ASEP_HIP_CHECK(hipMemcpyAsync(out_image, dimg.p, nout, hipMemcpyDeviceToHost, p->s));
     if (out_gray)
         ASEP_HIP_CHECK(hipMemcpyAsync(out_gray, dgray.p, (size_t)h * w * sizeof(float), hipMemcpyDeviceToHost, p->s));
+    ASEP_HIP_CHECK(hipStreamSynchronize(p->s));
+    return ASEP_OK;
+    POST_GUARD_END
+}
+
+int asep_prep_resize_tf1_dev(asep_post* p, const uint8_t* d_img, int H, int W, int C, int mode, int h, int w, float* d_out,
+                             void* stream) {
+    if (int rc = resize_tf1_check("asep_prep_resize_tf1_dev", p, d_img, d_out, H, W, C, mode, h, w)) return rc;
+    POST_GUARD_BEGIN
+    return resize_tf1_dev((hipStream_t)stream, d_img, H, W, C, mode, h, w, d_out);
+    POST_GUARD_END
+}
+
+int asep_prep_resize_tf1(asep_post* p, const uint8_t* img, int H, int W, int C, int mode, int h, int w, float* out) {
+    if (int rc = resize_tf1_check("asep_prep_resize_tf1", p, img, out, H, W, C, mode, h, w)) return rc;
+    POST_GUARD_BEGIN
+    Staged din, dout;
+    const size_t nin = (size_t)H * W * C, nout = (size_t)h * w * (mode == ASEP_RESIZE_LUMA ? 1 : C) * sizeof(float);
+    if (int rc = din.alloc(nin)) return rc;
+    if (int rc = dout.alloc(nout)) return rc;
+    ASEP_HIP_CHECK(hipMemcpyAsync(din.p, img, nin, hipMemcpyHostToDevice, p->s));
+    if (int rc = resize_tf1_dev(p->s, (const uint8_t*)din.p, H, W, C, mode, h, w, (float*)dout.p)) return rc;
+    ASEP_HIP_CHECK(hipMemcpyAsync(out, dout.p, nout, hipMemcpyDeviceToHost, p->s));
     ASEP_HIP_CHECK(hipStreamSynchronize(p->s));
     return ASEP_OK;
     POST_GUARD_END

@@ -4,6 +4,7 @@
 //   a9   apply_cc_analysis                    region_net_post_processor_base.py:230-251
 //        post_process (openings, subtract)    separator_net_post_processor.py:26-97
 //   a12  StrokeWidthDistanceTransform         swt_dist_trafo.py:18-29
+//   a13  relation net page resize (TF1)       image_resizer.py:111-223
 //
 // Binary images are kept as bit planes (one uint64 per 64 pixels of a row, LSB = smallest x): a 3000x4500 mask
 // is 1.7 MB, so rectangular morphology is word-parallel AND/OR of shifted words out of L2 instead of byte traffic.
@@ -646,6 +647,45 @@ post_gray_u8_kernel(const uint8_t* __restrict__ bgr, size_t n, uint8_t* __restri
         *(uint32_t*)(out + q * 4) = p0 | (p1 << 8) | (p2 << 16) | (p3 << 24);
     } else {
         for (size_t i = q * 4; i < n && i < q * 4 + 4; ++i) out[i] = (uint8_t)gray(bgr[3 * i], bgr[3 * i + 1], bgr[3 * i + 2]);
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------------
+// a13: the relation net's page image (gnn_input.resize_bilinear_tf1 = tf.image.resize BILINEAR of TF 1.x, image_resizer.py:111-223)
+// from the uint8 scan: src = dst * (in / out) in float32, no half-pixel offset, clamp at the border, float32 out (0..255).
+// One thread per output pixel, its channels together; neighbouring lanes read neighbouring taps of the same two source rows.
+// Every product and sum is rounded on its own in the host function's order (no FMA): the output equals it bit for bit.
+//   C = 1 | 3, LUMA 0   every channel on its own, interleaved order kept
+//   C = 3,     LUMA 1   each tap first becomes Pillow's convert('L') value (R 19595 + G 38470 + B 7471 + 2^15) >> 16
+// sy = float32(H / h), sx = float32(W / w) come from the host (a double division, rounded once).
+// --------------------------------------------------------------------------------------------------------------
+template <int C, bool LUMA>
+__global__ void __launch_bounds__(256)
+prep_resize_tf1_kernel(const uint8_t* __restrict__ img, int H, int W, float sy, float sx, float* __restrict__ out, int h, int w) {
+#pragma clang fp contract(off)
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;                               // (the launcher keeps h * w below 2^31)
+    if (i >= (unsigned)h * (unsigned)w) return;
+    const int y = (int)(i / (unsigned)w), x = (int)(i % (unsigned)w);
+    const float ys = (float)y * sy, xs = (float)x * sx;
+    const int y0 = min((int)floorf(ys), H - 1), x0 = min((int)floorf(xs), W - 1);     // (the min never binds below 2^23 rows: it keeps the taps inside)
+    const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
+    const float wy = ys - (float)y0, wx = xs - (float)x0;                             // exact: the fraction bits of ys / xs
+    const float uy = 1.0f - wy, ux = 1.0f - wx;
+    const uint8_t* r0 = img + (size_t)y0 * W * C;
+    const uint8_t* r1 = img + (size_t)y1 * W * C;
+    const size_t o0 = (size_t)x0 * C, o1 = (size_t)x1 * C;
+    if (LUMA) {
+        auto luma = [](const uint8_t* p) -> float { return (float)((p[0] * 19595u + p[1] * 38470u + p[2] * 7471u + 0x8000u) >> 16); };
+        const float top = luma(r0 + o0) * ux + luma(r0 + o1) * wx;
+        const float bot = luma(r1 + o0) * ux + luma(r1 + o1) * wx;
+        out[i] = top * uy + bot * wy;
+    } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float top = (float)r0[o0 + c] * ux + (float)r0[o1 + c] * wx;
+            const float bot = (float)r1[o0 + c] * ux + (float)r1[o1 + c] * wx;
+            out[(size_t)i * C + c] = top * uy + bot * wy;
+        }
     }
 }
 

@@ -126,6 +126,38 @@ def load_page_rgb(img_path):
         return np.asarray(im.convert("RGB"))
 
 
+def load_page_gray(img_path):
+    """input_dataset.py:279-280 with ``load_mode=L``: the scan as Pillow's mode "L" -> uint8 [H,W].  A plain 8-bit GRAY png is that
+    already (image_io's fast decode); colour files go through Pillow's own luma conversion, which is not OpenCV's."""
+    from PIL import Image
+    from . import image_io
+    image = image_io._load_png_plain(img_path) if str(img_path).lower().endswith(".png") else None
+    if image is None or image.ndim != 2:
+        with Image.open(img_path) as im:
+            image = np.asarray(im.convert("L"))                      # uint8; widened after the resize's gathers
+    return image
+
+
+def load_page_gray_or_rgb(img_path):
+    """``load_mode=L`` for the device resize: a gray scan -> uint8 [H,W]; a plain RGB scan -> uint8 [H,W,3] in R, G, B order, as
+    decoded -- the resize kernel takes Pillow's ``convert('L')`` value of every tap it reads instead of the host converting the
+    whole page.  Every other Pillow mode (palette, alpha, CMYK, 16 bit ...) is converted here like :func:`load_page_gray` does."""
+    from PIL import Image
+    from . import image_io
+    image = image_io._load_png_plain(img_path) if str(img_path).lower().endswith(".png") else None
+    if image is not None:
+        return image if image.ndim == 2 else np.ascontiguousarray(image[:, :, ::-1])
+    with Image.open(img_path) as im:
+        return np.asarray(im if im.mode in ("L", "RGB") else im.convert("L"))
+
+
+def load_page(img_path, load_mode="L", device_resize=False):
+    """the decode of one scan for ``input_params['load_mode']`` (what run_gnn_clustering / lav_rel feed to ``feed_from_json``)"""
+    if LOAD_MODE_CHANNELS[load_mode] == 3:
+        return load_page_rgb(img_path)
+    return load_page_gray_or_rgb(img_path) if device_resize else load_page_gray(img_path)
+
+
 class InputGNN(object):
     """``InputGNN(flags)`` with ``flags.input_params`` (dict) and ``flags.image_input`` (bool).  ``input_params['load_mode']``: 'L'
     feeds the page as one gray channel, 'RGB' as three (R, G, B), each resized like the gray one."""
@@ -152,11 +184,30 @@ class InputGNN(object):
             return mask_features(feats, mask)
         return feats
 
-    def feed_from_json(self, json_path, image=None, targets=None):
+    def image_feeds(self, image, device_resize=False):
+        """the image entries of a feed dict.  Default: 'image:0' = the page resized on the host + 'image_shape:0'.  ``device_resize``:
+        'image_u8:0' = the uint8 page untouched + 'image_shape:0' = [[h, w, channels fed]], the ``compute_new_size`` target the engine
+        resizes it to (a colour page under ``load_mode=L`` is fed as one channel: the kernel takes Pillow's luma)."""
+        if self.img_channels == 3 and (np.ndim(image) != 3 or np.shape(image)[2] != 3):
+            raise ValueError(f"load_mode=RGB feeds [H,W,3] pages, got {np.shape(image)}")
+        img = np.asarray(image)                                      # uint8 as decoded, or float32 (values 0..255 either way)
+        nh, nw = compute_new_size(img.shape[0], img.shape[1], self.input_params["resize_min_dim"],
+                                  self.input_params["resize_max_dim"])
+        if device_resize:
+            if img.dtype != np.uint8:
+                raise ValueError(f"device_resize feeds the scan as decoded (uint8), got {img.dtype}")
+            return {"image_u8:0": img[None], "image_shape:0": np.array([[nh, nw, self.img_channels]], np.int32)}
+        if img.ndim == 2:
+            img = img[:, :, None]
+        return {"image:0": resize_bilinear_tf1(img, nh, nw)[None], "image_shape:0": np.array([[nh, nw, img.shape[2]]], np.int32)}
+
+    def feed_from_json(self, json_path, image=None, targets=None, device_resize=False, image_later=False):
         """-> feed dict keyed by the exported placeholder names (batch size 1), ready for ``GnnSession.run``.  ``targets`` (a dict)
         receives the json's ``gt_relations`` [G, 3] and ``gt_num_relations``: what an evaluation scores the output against.
         ``image``: the decoded page -- [H,W] gray for ``load_mode=L``, [H,W,3] in R, G, B order for ``load_mode=RGB``
-        (:func:`load_page_rgb`)."""
+        (:func:`load_page_rgb`).  ``device_resize``: the page goes in untouched as 'image_u8:0' and the engine resizes it
+        (:meth:`image_feeds`).  ``image_later``: the page arrives from elsewhere (a decode slot) -- the json's visual regions are fed
+        without it and the caller adds ``image_feeds(page, ...)``."""
         d = get_input_and_target_from_json(json_path)
         if targets is not None:
             targets["gt_relations"] = d["gt_relations"].reshape(-1, 3)
@@ -172,16 +223,9 @@ class InputGNN(object):
         if self.input_params["edge_feature_dim"] > 0:
             ef = d["edge_features"].reshape(int(d["num_interacting_nodes"]), -1)
             feed["edge_features:0"] = self._masked(ef, "edge").astype(np.float32)[None]
-        if getattr(self._flags, "image_input", False) and image is not None:
-            if self.img_channels == 3 and (np.ndim(image) != 3 or np.shape(image)[2] != 3):
-                raise ValueError(f"load_mode=RGB feeds [H,W,3] pages, got {np.shape(image)}")
-            img = np.asarray(image)                                  # uint8 as decoded, or float32 (values 0..255 either way)
-            if img.ndim == 2:
-                img = img[:, :, None]
-            nh, nw = compute_new_size(img.shape[0], img.shape[1], self.input_params["resize_min_dim"],
-                                      self.input_params["resize_max_dim"])
-            feed["image:0"] = resize_bilinear_tf1(img, nh, nw)[None]
-            feed["image_shape:0"] = np.array([[nh, nw, img.shape[2]]], np.int32)
+        if getattr(self._flags, "image_input", False) and (image is not None or image_later):
+            if image is not None:
+                feed.update(self.image_feeds(image, device_resize))
             for k in ("visual_regions_nodes", "num_points_visual_regions_nodes"):
                 if k in d:
                     feed[k + ":0"] = d[k][None]

@@ -11,6 +11,7 @@ The TensorFlow runtime underneath is replaced by ``csrc/libasep_hip.so`` (``incl
 """
 import ctypes as C
 import os
+import warnings
 
 import numpy as np
 
@@ -25,6 +26,9 @@ FEED_NAMES = (
     "visual_regions_edges:0", "num_points_visual_regions_edges:0",
     "relations_to_consider_belong_to_same_instance:0",
 )
+# extension: the scan as decoded (uint8 [1,H,W], [1,H,W,1] or [1,H,W,3]) in place of 'image:0'; the engine resizes it on the device to
+# the [h, w] of 'image_shape:0' (gnn_input.resize_bilinear_tf1 bit for bit, include/asep_hip.h asep_prep_resize_tf1_dev)
+IMAGE_U8 = "image_u8:0"
 
 
 class GnnGraph:
@@ -154,8 +158,10 @@ class GnnSession:
             raise KeyError(f"The name '{name}' refers to a Tensor which does not exist (only {OUTPUT_NODE})")
         feed = {_key(k): v for k, v in feed_dict.items()}
         for k in feed:
-            if k not in FEED_NAMES:
+            if k not in FEED_NAMES and k != IMAGE_U8:
                 raise KeyError(f"The name '{k}' refers to a Tensor which does not exist")
+        if IMAGE_U8 in feed and "image:0" in feed:
+            raise KeyError(f"feed_dict holds both image:0 and {IMAGE_U8}: feed the resized image or the scan, not both")
         cfg = self.graph.cfg
         num_nodes = np.asarray(feed["num_nodes:0"]).reshape(-1)
         if num_nodes.shape[0] != 1:
@@ -179,14 +185,20 @@ class GnnSession:
         rel = np.ascontiguousarray(
             np.asarray(feed["relations_to_consider_belong_to_same_instance:0"], dtype=np.int32)[0])
         if cfg.visual_dims:
-            for k in ("image:0", "visual_regions_nodes:0", "num_points_visual_regions_nodes:0"):
+            from_scan = IMAGE_U8 in feed
+            for k in ((IMAGE_U8, "image_shape:0") if from_scan else ("image:0",)) + ("visual_regions_nodes:0",
+                                                                                     "num_points_visual_regions_nodes:0"):
                 if k not in feed:
                     raise KeyError(f"this graph was exported with image_input: feed_dict lacks {k}")
-            image = np.asarray(feed["image:0"], dtype=np.float32)
+            image = np.asarray(feed[IMAGE_U8]) if from_scan else np.asarray(feed["image:0"], dtype=np.float32)
             if image.shape[0] != 1:
                 raise ValueError("batch size must be 1 (input_dataset.py:134)")
             image = image[0]
-            if "image_shape:0" in feed:                     # crop to the true shape (no padding at batch size 1)
+            if from_scan:
+                if image.dtype != np.uint8:
+                    raise ValueError(f"{IMAGE_U8} is the scan as decoded (uint8), got {image.dtype}")
+                ish = np.asarray(feed["image_shape:0"]).reshape(-1, 3)[0]
+            elif "image_shape:0" in feed:                   # crop to the true shape (no padding at batch size 1)
                 ish = np.asarray(feed["image_shape:0"]).reshape(-1, 3)[0]
                 image = image[:int(ish[0]), :int(ish[1])]
             regions = np.asarray(feed["visual_regions_nodes:0"], dtype=np.float32)[0][:N]
@@ -198,8 +210,12 @@ class GnnSession:
                         raise KeyError(f"this graph assigns visual features to edges: feed_dict lacks {k}")
                 eregions = np.asarray(feed["visual_regions_edges:0"], dtype=np.float32)[0][:E]
                 enpts = np.asarray(feed["num_points_visual_regions_edges:0"], dtype=np.int32)[0][:E]
-            probs = gnn_forward_visual(self.graph, N, edges, u, ef, image, regions, npts, rel, self.device,
-                                       edge_regions=eregions, edge_num_points=enpts)
+            if from_scan:
+                probs = gnn_forward_visual_u8(self.graph, N, edges, u, ef, image, int(ish[0]), int(ish[1]), regions, npts, rel,
+                                              self.device, edge_regions=eregions, edge_num_points=enpts)
+            else:
+                probs = gnn_forward_visual(self.graph, N, edges, u, ef, image, regions, npts, rel, self.device,
+                                           edge_regions=eregions, edge_num_points=enpts)
         else:
             probs = gnn_forward(self.graph, N, edges, u, ef, rel, self.device)
         return probs[None]
@@ -273,6 +289,84 @@ def gnn_forward_visual(graph: GnnGraph, num_nodes, edges, node_feat, edge_feat, 
                                      ereg_p, enp_p, R, rel_p, out.ctypes.data)
     _lib.check(rc, "asep_gnn_forward_visual")
     return out
+
+
+def resize_mode(page_shape, backbone_channels):
+    """how a uint8 page [H,W] / [H,W,1] / [H,W,3] reaches a backbone of ``backbone_channels``: 'keep' when the counts agree, 'luma'
+    (Pillow's ``convert('L')``, taken per tap on the device) for a colour page into a gray backbone; a gray page into a colour
+    backbone is the ``ValueError`` of :func:`gnn_forward_visual`"""
+    got = page_shape[2] if len(page_shape) == 3 else 1
+    if len(page_shape) not in (2, 3) or got not in (1, 3) or (got != backbone_channels and not (got == 3 and backbone_channels == 1)):
+        raise ValueError(f"this graph's backbone takes {backbone_channels} image channel(s), the image {tuple(page_shape)} has {got}")
+    return "keep" if got == backbone_channels else "luma"
+
+
+def _check_node_indices(what, idx, N):
+    """the host-pointer entries refuse an index outside the page (csrc/gnn_engine.hip check_indices); the device entries cannot"""
+    bad = np.flatnonzero(((idx < 0) | (idx >= N)).any(axis=1)) if idx.size else ()
+    if len(bad):
+        i = int(bad[0])
+        raise _lib.AsepError(f"{what}[{i}] = ({int(idx[i, 0])}, {int(idx[i, 1])}) names a node outside 0..{N - 1}")
+
+
+def gnn_forward_visual_u8(graph: GnnGraph, num_nodes, edges, node_feat, edge_feat, page_u8, h, w, regions, num_points,
+                          relations=None, device=0, edge_regions=None, edge_num_points=None):
+    """:func:`gnn_forward_visual` from the scan as decoded: ``page_u8`` uint8 [H,W(,1)] or [H,W,3] (R, G, B) is uploaded as it is and
+    resized to [h,w] on the device (``asep_prep_resize_tf1_dev`` = ``gnn_input.resize_bilinear_tf1`` bit for bit; a colour page
+    for a gray backbone becomes Pillow's ``convert('L')`` there), then ``asep_gnn_forward_visual_dev`` runs behind it on torch's
+    current stream.  ``h``, ``w``: ``gnn_input.compute_new_size`` of the page.  The device buffers are torch tensors."""
+    import torch
+    from . import image_ops
+    cfg = graph.cfg
+    N = int(num_nodes)
+    page = np.asarray(page_u8)
+    if page.dtype != np.uint8:
+        raise ValueError(f"the page is the scan as decoded (uint8), got {page.dtype}")
+    mode = resize_mode(page.shape, cfg.backbone_cfg().channels)
+    if int(h) < 1 or int(w) < 1:
+        raise ValueError(f"the target size must be positive, got {h} x {w}")
+    edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+    E = edges.shape[0]
+    _check_node_indices("interacting_nodes", edges, N)
+    u = np.ascontiguousarray(node_feat, dtype=np.float32).reshape(N, cfg.node_feature_dim)
+    ef = np.ascontiguousarray(edge_feat, dtype=np.float32).reshape(E, -1) if edge_feat is not None else None
+    reg = np.ascontiguousarray(regions, dtype=np.float32)
+    if reg.ndim != 3 or reg.shape[0] != N or reg.shape[1] != 2:
+        raise ValueError(f"visual_regions_nodes must be [N, 2, P], got {reg.shape}")
+    npts = np.ascontiguousarray(num_points, dtype=np.int32).reshape(N)
+    ereg = enp = None
+    if cfg.visual_edges:
+        if edge_regions is None or edge_num_points is None:
+            raise ValueError("this graph assigns visual features to edges: edge_regions / edge_num_points required")
+        ereg = np.ascontiguousarray(edge_regions, dtype=np.float32)
+        if ereg.shape != (E, 2, reg.shape[2]):
+            raise ValueError(f"visual_regions_edges must be [E, 2, P] = {(E, 2, reg.shape[2])}, got {ereg.shape}")
+        enp = np.ascontiguousarray(edge_num_points, dtype=np.int32).reshape(E)
+    rel = None
+    R = N * N
+    if relations is not None:
+        rel = np.ascontiguousarray(relations, dtype=np.int32).reshape(-1, 2)
+        R = rel.shape[0]
+        _check_node_indices("relations", rel, N)
+    handle = graph.handle(device)                            # (initialises the device before torch allocates on it)
+    dev = torch.device("cuda", int(device))
+    with torch.cuda.device(dev):
+        up = lambda x: torch.from_numpy(x).to(dev, non_blocking=True) if x is not None and x.size else None      # noqa: E731
+        ptr = lambda t: t.data_ptr() if t is not None else None                                                  # noqa: E731
+        with warnings.catch_warnings():                      # (a page Pillow decoded is read-only: it is only read here)
+            warnings.simplefilter("ignore", UserWarning)
+            d_page = torch.from_numpy(np.ascontiguousarray(page)).to(dev, non_blocking=True)     # a DMA from a page-locked slot
+        d_image = image_ops.resize_tf1_dev(d_page, h, w, mode, device)
+        t = [up(a) for a in (edges, u, ef, reg, npts, ereg, enp, rel)]
+        out = torch.empty((R, cfg.num_classes), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        gnn_forward_visual_dev(graph, N, E, ptr(t[0]), ptr(t[1]), ptr(t[2]) if E else None, d_image.data_ptr(), int(h), int(w),
+                               ptr(t[3]), reg.shape[2], ptr(t[4]), R, ptr(t[7]), out.data_ptr() if R else None,
+                               stream.cuda_stream or None, device, d_edge_regions=ptr(t[5]) if E else None,
+                               d_edge_num_points=ptr(t[6]) if E else None)
+        probs = out.cpu().numpy()                            # (waits for the stream: the uploads above stay alive until here)
+    del handle
+    return probs
 
 
 def gnn_forward_visual_dev(graph: GnnGraph, num_nodes, num_edges, d_edges, d_node_feat, d_edge_feat, d_image, h, w, d_regions,

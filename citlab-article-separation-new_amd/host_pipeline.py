@@ -70,12 +70,42 @@ def single_threaded_children():
                 os.environ[k] = v
 
 
+def load_page_l(path):
+    """the relation net's scan under ``load_mode=L``, Pillow semantics (gnn_input.load_page_gray): uint8 [H,W]"""
+    from .gnn_input import load_page_gray
+    return load_page_gray(path)
+
+
+def load_page_l_or_rgb(path):
+    """``load_mode=L`` for the device resize (gnn_input.load_page_gray_or_rgb): uint8 [H,W], or [H,W,3] R, G, B for a plain colour scan"""
+    from .gnn_input import load_page_gray_or_rgb
+    return load_page_gray_or_rgb(path)
+
+
+def load_page_rgb(path):
+    """the relation net's scan under ``load_mode=RGB``, Pillow semantics (gnn_input.load_page_rgb): uint8 [H,W,3] in R, G, B order"""
+    from .gnn_input import load_page_rgb as load
+    return load(path)
+
+
+PAGE_LOADERS = {"load_page_l": load_page_l, "load_page_l_or_rgb": load_page_l_or_rgb, "load_page_rgb": load_page_rgb}
+
+
+def page_loader_name(load_mode="L", device_resize=False):
+    """the DecodePool loader that decodes what ``gnn_input.load_page(path, load_mode, device_resize)`` decodes"""
+    if load_mode == "RGB":
+        return "load_page_rgb"
+    return "load_page_l_or_rgb" if device_resize else "load_page_l"
+
+
 def _resolve_loader(name):
-    """``name`` of a function in image_io, or ``"package.module:function"``"""
+    """``name`` of a function in image_io or of a page loader above, or ``"package.module:function"``"""
     if ":" in name:
         import importlib
         mod, fn = name.split(":", 1)
         return getattr(importlib.import_module(mod), fn)
+    if name in PAGE_LOADERS:
+        return PAGE_LOADERS[name]
     from . import image_io
     return getattr(image_io, name)
 

@@ -4,6 +4,7 @@ The reference calls OpenCV on the host for these; t
 reference's names / argument meaning where it has a function of its own and name the cv2 call otherwise.
 
     scale_image / scale_and_gray      net_post_processing_helper.py:14-33
+    resize_tf1 / resize_tf1_dev       python_util/image_processing/image_resizer.py:111-223 (the relation net's page image)
     apply_cc_analysis                 region_net_post_processor_base.py:230-251
     morphology_rect                   cv2.erode / dilate / morphologyEx(MORPH_OPEN / MORPH_CLOSE), rect kernels
     separator_post_process            separator_net_post_processor.py:26-97
@@ -61,6 +62,46 @@ def scale_and_gray(image, fixed_height=None, scaling_factor=1.0, device=0, want_
     if out_img is not None and Cn == 1:
         out_img = out_img[:, :, 0]
     return out_img, gray, sc
+
+
+def _resize_tf1_args(shape, mode):
+    """(H, W, C, mode code, channels out) of a uint8 page [H,W] / [H,W,1] / [H,W,3] under ``mode`` 'keep' | 'luma'"""
+    if len(shape) not in (2, 3):
+        raise ValueError(f"a page is [H,W] or [H,W,C], got {tuple(shape)}")
+    Cn = shape[2] if len(shape) == 3 else 1
+    if mode not in _lib.RESIZE_MODES:
+        raise ValueError(f"mode {mode!r}: 'keep' and 'luma' are served")
+    return int(shape[0]), int(shape[1]), int(Cn), _lib.RESIZE_MODES[mode], 1 if mode == "luma" else int(Cn)
+
+
+def resize_tf1(image, new_h, new_w, mode="keep", device=0):
+    """``gnn_input.resize_bilinear_tf1`` of a uint8 page on the device, bit for bit (``asep_prep_resize_tf1``): [H,W] or [H,W,C]
+    uint8 -> float32 [new_h,new_w,C] (0..255).  ``mode='luma'``: an [H,W,3] R, G, B page becomes Pillow's ``convert('L')`` gray
+    first -> [new_h,new_w,1]."""
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    H, W, Cn, code, cout = _resize_tf1_args(image.shape, mode)
+    lib, ws = _workspace(device)
+    out = np.empty((max(int(new_h), 0), max(int(new_w), 0), cout), dtype=np.float32)
+    _lib.check(lib.asep_prep_resize_tf1(ws, image.ctypes.data, H, W, Cn, code, int(new_h), int(new_w), out.ctypes.data),
+               "asep_prep_resize_tf1")
+    return out
+
+
+def resize_tf1_dev(d_image, new_h, new_w, mode="keep", device=0):
+    """the same for a page that is in HBM: ``d_image`` a uint8 torch tensor [H,W] / [H,W,C] on the device -> float32 tensor
+    [new_h,new_w,C] ([new_h,new_w,1] for 'luma'), queued on torch's current stream (``asep_prep_resize_tf1_dev``: no host
+    synchronisation)."""
+    import torch
+    if d_image.dtype != torch.uint8 or not d_image.is_cuda:
+        raise ValueError("resize_tf1_dev takes a uint8 tensor on the device")
+    d_image = d_image.contiguous()
+    H, W, Cn, code, cout = _resize_tf1_args(tuple(d_image.shape), mode)
+    lib, ws = _workspace(device)
+    out = torch.empty((max(int(new_h), 0), max(int(new_w), 0), cout), dtype=torch.float32, device=d_image.device)
+    sp = C.c_void_p(torch.cuda.current_stream(d_image.device).cuda_stream)
+    _lib.check(lib.asep_prep_resize_tf1_dev(ws, d_image.data_ptr(), H, W, Cn, code, int(new_h), int(new_w),
+                                            out.data_ptr() if out.numel() else None, sp), "asep_prep_resize_tf1_dev")
+    return out
 
 
 def scale_image(image, fixed_height=None, scaling_factor=1.0, device=0):

@@ -292,6 +292,7 @@ def build_parser():
     # extensions
     p.add_argument("--visual_layers", type=str, nargs="*", default=None)    # as in run_gnn_clustering
     p.add_argument("--num_workers", type=int, default=1)                    # host workers that prepare pages ahead of the GPU owner
+    p.add_argument("--device_resize", default=False, **b)                   # as in run_gnn_clustering: True = the uint8 scan is resized on the device
     return p
 
 
@@ -315,8 +316,10 @@ def check_flags(flags):
 _eval_state = {}
 
 
-def _prepare_eval_page(argv, json_path):
-    """host worker: json (+ scan) -> (feed dict, N, gt_relations) or None"""
+def _prepare_eval_page(argv, json_path, image_later=False, device_resize=False):
+    """host worker: json (+ scan, unless it comes through a decode slot: ``image_later``) -> (feed dict, N, gt_relations) or None.
+    ``device_resize`` False: the scan resized on the host under 'image:0'; True (what ``evaluate`` asks for under --device_resize):
+    the scan as decoded under 'image_u8:0'"""
     from . import run_gnn_clustering
     from .gnn_input import InputGNN
     key = tuple(argv)
@@ -328,7 +331,7 @@ def _prepare_eval_page(argv, json_path):
         logging.warning(f"No json file {json_path}. Skipping.")
         return None
     targets = {}
-    feed, n = run_gnn_clustering._prepare_feed(input_fn, flags, json_path, targets)
+    feed, n = run_gnn_clustering._prepare_feed(input_fn, flags, json_path, targets, image_later=image_later, device_resize=device_resize)
     return feed, n, targets["gt_relations"]
 
 
@@ -353,16 +356,24 @@ def _feed_arrays(feed, cfg):
             raise ValueError(f"edge_features has dim {ef.shape[1]}, model expects {cfg.edge_feature_dim}")
         a["ef"] = ef
     if cfg.visual_dims:
-        for k in ("image:0", "visual_regions_nodes:0", "num_points_visual_regions_nodes:0"):
+        from .gnn_io import IMAGE_U8, resize_mode
+        from_scan = IMAGE_U8 in feed
+        for k in ((IMAGE_U8, "image_shape:0") if from_scan else ("image:0",)) + ("visual_regions_nodes:0",
+                                                                                 "num_points_visual_regions_nodes:0"):
             if k not in feed:
                 raise KeyError(f"this graph was exported with image_input: feed_dict lacks {k}")
-        image = np.asarray(feed["image:0"], np.float32)[0]
-        if "image_shape:0" in feed:
+        if from_scan:                                        # the scan as decoded: resized on the device behind its upload
             ish = np.asarray(feed["image_shape:0"]).reshape(-1, 3)[0]
-            image = image[:int(ish[0]), :int(ish[1])]
-        if image.ndim == 3 and cfg.backbone_cfg().channels == 1:
-            image = image[:, :, 0]
-        a["image"] = np.ascontiguousarray(image)             # [h,w], or [h,w,3] for a colour backbone
+            a["page_u8"] = np.ascontiguousarray(np.asarray(feed[IMAGE_U8])[0])
+            a["resize"] = (int(ish[0]), int(ish[1]), resize_mode(a["page_u8"].shape, cfg.backbone_cfg().channels))
+        else:
+            image = np.asarray(feed["image:0"], np.float32)[0]
+            if "image_shape:0" in feed:
+                ish = np.asarray(feed["image_shape:0"]).reshape(-1, 3)[0]
+                image = image[:int(ish[0]), :int(ish[1])]
+            if image.ndim == 3 and cfg.backbone_cfg().channels == 1:
+                image = image[:, :, 0]
+            a["image"] = np.ascontiguousarray(image)         # [h,w], or [h,w,3] for a colour backbone
         a["regions"] = np.ascontiguousarray(np.asarray(feed["visual_regions_nodes:0"], np.float32)[0][:N])
         a["npts"] = np.ascontiguousarray(np.asarray(feed["num_points_visual_regions_nodes:0"], np.int32)[0][:N])
         if cfg.visual_edges:
@@ -397,11 +408,19 @@ class LavGNN(object):
         up = lambda x: torch.from_numpy(x).to(dev) if x is not None and x.size else None            # noqa: E731
         ptr = lambda t: t.data_ptr() if t is not None else None                                    # noqa: E731
         N, E, cfg = a["N"], a["E"], graph.cfg
-        t = {k: up(a.get(k)) for k in ("edges", "u", "ef", "image", "regions", "npts", "eregions", "enpts")}
+        # (a blocking copy each: a page that sits in a decode slot is in HBM before the slot goes back to the pool)
+        with warnings.catch_warnings():                      # (a page Pillow decoded is read-only: it is only read here)
+            warnings.simplefilter("ignore", UserWarning)
+            t = {k: up(a.get(k)) for k in ("edges", "u", "ef", "image", "page_u8", "regions", "npts", "eregions", "enpts")}
+        if "resize" in a:
+            from . import image_ops
+            h, w, mode = a["resize"]
+            t["image"] = image_ops.resize_tf1_dev(t["page_u8"], h, w, mode, self.device)
+            t["page_u8"] = None                              # (queued on torch's current stream: its allocator keeps the block until then)
         out = torch.empty((N * N, cfg.num_classes), dtype=torch.float32, device=dev)
         stream = _stream(self.device)
         if cfg.visual_dims:
-            h, w = a["image"].shape[:2]
+            h, w = t["image"].shape[:2]
             page = dict(N=N, E=E, R=N * N, d_edges=ptr(t["edges"]), d_node_feat=ptr(t["u"]), d_edge_feat=ptr(t["ef"]),
                         d_image=ptr(t["image"]), d_regions=ptr(t["regions"]), d_num_points=ptr(t["npts"]),
                         d_edge_regions=ptr(t["eregions"]), d_edge_num_points=ptr(t["enpts"]), d_relations=None,
@@ -420,23 +439,48 @@ class LavGNN(object):
         workers = max(1, int(getattr(flags, "num_workers", 1) or 1))
         if workers <= 1 or not self._argv:
             for p in json_paths:
-                yield _prepare_eval_page(self._argv_key(), p)
+                yield _prepare_eval_page(self._argv_key(), p, False, bool(getattr(flags, "device_resize", False)))
             return
         import multiprocessing as mp
         from concurrent.futures import ProcessPoolExecutor
+        from . import run_gnn_clustering
         from .host_pipeline import single_threaded_children
-        with ProcessPoolExecutor(workers, mp_context=mp.get_context("spawn")) as pool:
+        later = bool(flags.image_input and getattr(flags, "device_resize", False))    # the json half only: the scan comes through a slot
+        scans = None
+        if later:                                                    # the decoders start first
+            _, input_fn = self._eval_objects()
+            scans = run_gnn_clustering._ScanSlots(json_paths, input_fn.input_params["load_mode"], self.device, workers)
+        with ProcessPoolExecutor(max(1, workers - run_gnn_clustering._slot_decoders(workers)) if later else workers,
+                                 mp_context=mp.get_context("spawn")) as pool:
             def submit(p):
                 with single_threaded_children():
-                    return pool.submit(_prepare_eval_page, self._argv_key(), p)
+                    return pool.submit(_prepare_eval_page, self._argv_key(), p, later, False)     # (host resize, or the json half)
             ahead = 2 * workers
             pending = [submit(p) for p in json_paths[:ahead]]
-            for k in range(len(json_paths)):
-                page = pending[k].result()
-                pending[k] = None
-                if k + ahead < len(json_paths):
-                    pending.append(submit(json_paths[k + ahead]))
-                yield page
+            try:
+                for k in range(len(json_paths)):
+                    page = pending[k].result()
+                    pending[k] = None
+                    if k + ahead < len(json_paths):
+                        pending.append(submit(json_paths[k + ahead]))
+                    if page is not None and scans is not None:
+                        _, scan = next(scans)                        # (valid until the next one is asked for)
+                        page[0].update(input_fn.image_feeds(scan, True))
+                        del scan
+                    yield page
+                    page = None
+            finally:
+                page = None
+                if scans is not None:
+                    scans.close()
+
+    def _eval_objects(self):
+        key = self._argv_key()
+        if key not in _eval_state:
+            from .gnn_input import InputGNN
+            flags = parse_flags(list(key))
+            _eval_state[key] = (flags, InputGNN(flags))
+        return _eval_state[key]
 
     def _argv_key(self):
         if not self._argv:                                           # flags were handed in as an object: the same process prepares
@@ -488,6 +532,7 @@ class LavGNN(object):
                 feed, n, gt_relations = page
                 t0 = time.perf_counter()
                 out = self._forward_dev(graph, _feed_arrays(feed, graph.cfg), keep)
+                feed = page = None                                    # (a scan fed from a decode slot: no view outlives its slot)
                 t1 = time.perf_counter()
                 acc.append_page(out, n, gt_relations)
                 tm["net_s"] += t1 - t0

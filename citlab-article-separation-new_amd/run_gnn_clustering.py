@@ -37,6 +37,10 @@ def build_parser():
     # extension: the backbone end points a graph exported with --image_input reads its visual node features from
     # (the reference fixed them at training time with --feature_map_generation_params from_layer=[...])
     p.add_argument("--visual_layers", type=str, nargs="*", default=None)
+    # extension: True = the scan goes to the device as decoded (uint8) and is resized there (asep_prep_resize_tf1_dev: the host resize bit
+    # for bit; a colour file under load_mode=L is decoded as RGB and the kernel takes Pillow's luma).  The default stays the host resize
+    # until the device path is no slower on every leg: with host workers it loses on colour scans
+    p.add_argument("--device_resize", type=cli_flags.str2bool, default=False)
     p.add_argument("--assign_visual_features_to_nodes", type=cli_flags.str2bool, default=True)
     p.add_argument("--assign_visual_features_to_edges", type=cli_flags.str2bool, default=False)
     p.add_argument("--mvn", type=cli_flags.str2bool, default=True)
@@ -72,37 +76,34 @@ def resolve_model_path(flags):
     return pb or get_path_from_exportdir(flags.model_dir, "*best*.pb", "_gpu.pb")
 
 
-def _prepare_page(input_fn, flags, json_path):
+def _prepare_page(input_fn, flags, json_path, image_later=False):
     """:237-262 for one page: json (+ scan for a graph exported with image_input) -> (PAGE-XML path, feed dict, number of nodes), or
-    None if the json does not exist"""
+    None if the json does not exist.  ``image_later``: the json half only, the caller adds the scan (a decode slot)"""
     page_path = get_page_from_json_path(json_path)
     if not os.path.isfile(json_path):
         logging.warning(f"No json file found to given pageXML {page_path}. Skipping.")
         return None
-    feed, n = _prepare_feed(input_fn, flags, json_path)
+    feed, n = _prepare_feed(input_fn, flags, json_path, image_later=image_later)
     return page_path, feed, n
 
 
-def _prepare_feed(input_fn, flags, json_path, targets=None):
+def _device_resize(flags):
+    return bool(getattr(flags, "device_resize", False))
+
+
+def _prepare_feed(input_fn, flags, json_path, targets=None, image_later=False, device_resize=None):
     """the feed dict of one graph json (+ its scan for a graph exported with image_input) and its number of nodes; ``targets``
-    (a dict) receives the json's ground truth relations (lav_rel)"""
+    (a dict) receives the json's ground truth relations (lav_rel); ``device_resize`` None: as ``flags`` say"""
     image = None
-    if flags.image_input:
-        from PIL import Image
-        from . import image_io
+    device_resize = _device_resize(flags) if device_resize is None else bool(device_resize)
+    if flags.image_input and not image_later:
+        from .gnn_input import load_page
         from .path_util import get_img_from_json_path
-        img_path = get_img_from_json_path(json_path)
-        if input_fn.img_channels == 3:                                   # load_mode=RGB: [H,W,3] in R, G, B order
-            from .gnn_input import load_page_rgb
-            image = load_page_rgb(img_path)
-        else:
-            # input_dataset.py:279-280: the scan as mode "L".  A plain 8-bit GRAY png is that already (image_io's fast decode);
-            # colour files go through Pillow's own luma conversion, which is not OpenCV's
-            image = image_io._load_png_plain(img_path) if img_path.lower().endswith(".png") else None
-            if image is None or image.ndim != 2:
-                with Image.open(img_path) as im:
-                    image = np.asarray(im.convert("L"))                  # uint8; widened after the resize's gathers
-    feed = input_fn.feed_from_json(json_path, image, targets)
+        # input_dataset.py:279-280: the scan as mode "L", or [H,W,3] in R, G, B order for load_mode=RGB; with --device_resize a colour
+        # file under load_mode=L stays RGB (the resize kernel takes Pillow's luma)
+        image = load_page(get_img_from_json_path(json_path), input_fn.input_params["load_mode"], device_resize)
+    feed = input_fn.feed_from_json(json_path, image, targets, device_resize=device_resize,
+                                   image_later=image_later and flags.image_input)
     n = feed["node_features:0"].shape[1] if "node_features:0" in feed else int(feed["num_nodes:0"][0])
     return feed, n
 
@@ -176,14 +177,82 @@ def _task_objects(argv):
     return _task_state[key]
 
 
-def _prepare_task(argv, json_path):
+def _prepare_task(argv, json_path, image_later=False):
     flags, input_fn, _ = _task_objects(argv)
-    return _prepare_page(input_fn, flags, json_path)
+    return _prepare_page(input_fn, flags, json_path, image_later)
 
 
 def _finish_task(argv, output, n, page_path):
     flags, _, tb = _task_objects(argv)
     return _finish_page(tb, flags, output, n, page_path)
+
+
+def _slot_decoders(host_workers):
+    """of a GPU owner's host workers, those that decode scans into slots; the rest parse jsons ahead of the owner and cluster / write
+    behind it.  Three of four: decoding a 4500 x 3000 png is the larger part of a page's host work, several times the rest for a colour
+    scan (DESIGN section 4.4 has the measured rates).  DecodePool runs worker processes from two workers on, so a request of two starts
+    two decoders and one executor process."""
+    return max(2, (3 * host_workers) // 4)
+
+
+class _ScanSlots:
+    """--device_resize: the scans of the list's jsons, decoded ahead by DecodePool workers into page-locked shared-memory slots (a
+    13 - 40 MB uint8 page is not pickled; its upload is a DMA from the slot) -> iterator over (path, page) in list order.  The workers
+    are started and the first page is awaited on a thread of its own, so decoding runs while the caller loads the model; the slots are
+    page-locked from that thread once the engine is there."""
+
+    def __init__(self, json_paths, load_mode, device, host_workers):
+        import threading
+        from .host_pipeline import DecodePool, page_loader_name
+        from .path_util import get_img_from_json_path
+        present = [get_img_from_json_path(p) for p in json_paths if os.path.isfile(p)]
+        pin = []
+
+        def register(addr, nbytes):
+            if not pin:
+                from .host_pipeline import pin_callbacks
+                pin.extend(pin_callbacks(int(device)))
+            return pin[0](addr, nbytes)
+
+        def unregister(addr):
+            if pin:
+                pin[1](addr)
+        self._it = iter(DecodePool(present, _slot_decoders(host_workers), loader=page_loader_name(load_mode, True), register=register,
+                                   unregister=unregister))
+        self._first = []
+        self._thread = threading.Thread(target=self._prime, daemon=True)
+        self._thread.start()
+
+    def _prime(self):
+        try:
+            self._first.append(("page", next(self._it)))
+        except StopIteration:
+            self._first.append(("end", None))
+        except BaseException as e:                          # surfaced by the first __next__
+            self._first.append(("error", e))
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._thread is not None:
+            self._thread.join()
+            self._thread = None
+            kind, value = self._first.pop()
+            if kind == "page":
+                return value
+            if kind == "end":
+                raise StopIteration
+            raise value
+        return next(self._it)
+
+    def close(self):
+        """stops the decode workers and releases the slots; the caller holds no view of a slot any more"""
+        if self._thread is not None:
+            self._thread.join()
+            self._thread = None
+        del self._first[:]
+        self._it.close()
 
 
 def gnn_clustering_pipelined(json_paths, argv, device="0", host_workers=2):
@@ -195,28 +264,45 @@ def gnn_clustering_pipelined(json_paths, argv, device="0", host_workers=2):
         json_paths = json_paths[:max(0, flags.batch_limiter)]
     t0 = time.time()
     results = []
-    with ProcessPoolExecutor(max(1, host_workers), mp_context=mp.get_context("spawn")) as pool:
+    later = bool(flags.image_input and _device_resize(flags))               # the json half only: the scan comes through a slot
+    executor_workers = max(1, host_workers - _slot_decoders(host_workers)) if later else host_workers
+    scans = input_fn = None
+    if later:                                                               # the decoders start first: they work through the model load
+        from .gnn_input import InputGNN
+        input_fn = InputGNN(flags)
+        scans = _ScanSlots(json_paths, input_fn.input_params["load_mode"], device or 0, host_workers)
+    with ProcessPoolExecutor(max(1, executor_workers), mp_context=mp.get_context("spawn")) as pool:
         def submit(fn, *args):
             with single_threaded_children():                # (the executor spawns its processes inside submit, on demand)
                 return pool.submit(fn, list(argv), *args)
         ahead = 2 * max(1, host_workers)
-        prepared = [submit(_prepare_task, p) for p in json_paths[:ahead]]   # the workers start on the first pages while the
-        sess = _load_session(flags, device)                                  # owner imports the engine and loads the model
         finishing = []
-        for k in range(len(json_paths)):
-            page = prepared[k].result()
-            prepared[k] = None
-            if k + ahead < len(json_paths):
-                prepared.append(submit(_prepare_task, json_paths[k + ahead]))
-            if page is None:
-                continue
-            page_path, feed, n = page
-            output = sess.run("output_belong_to_same_instance:0", feed_dict=feed)
-            finishing.append(submit(_finish_task, output, n, page_path))
-            while len(finishing) > 4 * max(1, host_workers):                 # bounded backlog: surface errors early
-                out = finishing.pop(0).result()
-                if out is not None:
-                    results.append(out)
+        try:
+            prepared = [submit(_prepare_task, p, later) for p in json_paths[:ahead]]   # the workers start on the first pages while the
+            sess = _load_session(flags, device)                              # owner imports the engine and loads the model
+            for k in range(len(json_paths)):
+                page = prepared[k].result()
+                prepared[k] = None
+                if k + ahead < len(json_paths):
+                    prepared.append(submit(_prepare_task, json_paths[k + ahead], later))
+                if page is None:
+                    continue
+                page_path, feed, n = page
+                if scans is not None:
+                    _, scan = next(scans)                                    # (valid until the next one is asked for: run() returns
+                    feed.update(input_fn.image_feeds(scan, True))            # after the page's results have arrived)
+                    del scan
+                output = sess.run("output_belong_to_same_instance:0", feed_dict=feed)
+                feed = page = None                                           # (no view of a slot outlives it)
+                finishing.append(submit(_finish_task, output, n, page_path))
+                while len(finishing) > 4 * max(1, host_workers):                 # bounded backlog: surface errors early
+                    out = finishing.pop(0).result()
+                    if out is not None:
+                        results.append(out)
+        finally:
+            feed = page = None                                               # (also when run() raised: no view of a slot outlives it)
+            if scans is not None:
+                scans.close()                                                # stops the decode workers, releases the slots
         for f in finishing:
             out = f.result()
             if out is not None:

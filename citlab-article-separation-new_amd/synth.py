@@ -153,10 +153,11 @@ GNN_VISUAL_LAYERS = ["scale_0_unet_up_2_conv", "scale_0_unet_up_1_conv", "scale_
 GNN_FEATURE_MASK = [1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1]          # the 7 of the 15 json features the nets read
 
 
-def write_gnn_cli_inputs(root, n_pages, visual=True, W: int = 3000, H: int = 4500, N: int = 200):
+def write_gnn_cli_inputs(root, n_pages, visual=True, W: int = 3000, H: int = 4500, N: int = 200, load_mode: str = "L"):
     """Inputs of the relation net's command line for benchmarks: a frozen graph (random weights, the visual net BASELINE
     configs[3] names or the geometric one), per page a graph json of ``N`` text blocks / ~20k directed edges (+ the scan for the
     visual net) and a PAGE-XML with ``N`` text regions.  Four distinct pages, the rest links to them.
+    ``load_mode='RGB'``: colour scans (the gray page tinted per channel) and a backbone whose first convolution reads three channels.
     -> argv for ``run_gnn_clustering.main`` (without --num_workers / --out_dir)"""
     import json
     import os
@@ -164,7 +165,9 @@ def write_gnn_cli_inputs(root, n_pages, visual=True, W: int = 3000, H: int = 450
     from . import pb_import
     from .config import GnnConfig
     from .weights import init_gnn_weights
-    cfg = GnnConfig(node_feature_dim=7, visual_dims=[16, 16, 16] if visual else [], visual_layers=GNN_VISUAL_LAYERS if visual else [])
+    colour = visual and load_mode == "RGB"
+    cfg = GnnConfig(node_feature_dim=7, visual_dims=[16, 16, 16] if visual else [], visual_layers=GNN_VISUAL_LAYERS if visual else [],
+                    **({"backbone": {"channels": 3}} if colour else {}))
     w = init_gnn_weights(cfg, 3, bias_jitter=0.05)
     keep = [i for i, m in enumerate(GNN_FEATURE_MASK) if m]
     os.makedirs(os.path.join(root, "model", "export"))
@@ -188,6 +191,8 @@ def write_gnn_cli_inputs(root, n_pages, visual=True, W: int = 3000, H: int = 450
                 _, regions, npts = visual_inputs(page, N, k)
                 d["visual_regions_nodes"] = np.asarray(regions).tolist()
                 d["num_points_visual_regions_nodes"] = np.asarray(npts).tolist()
+                if colour:
+                    page = (page[:, :, None] * np.array([0.35, 0.7, 1.0], np.float32)).astype(np.uint8)
                 Image.fromarray(page).save(os.path.join(data, f"{name}.png"), compress_level=1)
             with open(os.path.join(data, "json15d2bb", f"{name}.json"), "w") as f:
                 json.dump(d, f)
@@ -211,8 +216,8 @@ def write_gnn_cli_inputs(root, n_pages, visual=True, W: int = 3000, H: int = 450
     with open(lst, "w") as f:
         f.write("\n".join(jsons) + "\n")
     argv = ["--model_dir", os.path.join(root, "model"), "--eval_list", lst, "--input_params", "node_feature_dim=15",
-            "edge_feature_dim=2", "node_input_feature_mask=" + str(GNN_FEATURE_MASK).replace(" ", ""), "--clustering_method",
-            "dbscan"]
+            "edge_feature_dim=2", "node_input_feature_mask=" + str(GNN_FEATURE_MASK).replace(" ", ""), *(["load_mode=RGB"] if colour else []),
+            "--clustering_method", "dbscan"]
     if visual:
         argv += ["--image_input", "True", "--visual_layers"] + GNN_VISUAL_LAYERS
     return argv

@@ -45,8 +45,9 @@ const char* asep_version(void);
 /* Version of THIS header's struct layouts and signatures (ASEP_ABI_VERSION of the build).  A binding checks it once after
  * dlopen; independently of it every configuration struct starts with its own size in bytes (`struct_size`), and the load
  * functions refuse a struct whose size is not the one the library was built with -- a caller written against an older or newer
- * header gets ASEP_ERR_ARG + a message instead of fields read from whatever follows its struct on the stack. */
-#define ASEP_ABI_VERSION 6
+ * header gets ASEP_ERR_ARG + a message instead of fields read from whatever follows its struct on the stack.
+ * An added function moves the version too: a binding resolves every name it declares when it loads the library. */
+#define ASEP_ABI_VERSION 7
 int asep_abi_version(void);
 /* ABI 6: the environment switches this build of the library reads when a model is loaded (one name per line).
  * Anything else in the environment is not a switch: a caller that records the switches a measurement ran under (bench.py) filters
@@ -295,6 +296,20 @@ int asep_prep_scale_gray(asep_post* p, const uint8_t* img, int H, int W, int C, 
                          uint8_t* out_image, float* out_gray);
 int asep_prep_scale_gray_dev(asep_post* p, const uint8_t* d_img, int H, int W, int C, double sc,
                              uint8_t* d_out_image, float* d_out_gray, void* stream);
+
+/* ABI 7: gnn_input.resize_bilinear_tf1 (image_resizer.py:111-223: tf.image.resize BILINEAR of TF 1.x, align_corners False) from the uint8
+ * scan, for the relation net's page image (input_dataset.py:279-283): src = dst * (in / out) in float32 with the factors
+ * float32(H / h), float32(W / w), no half-pixel offset, taps clamped at the border, every product and sum rounded on its own --
+ * the host function's result bit for bit.  img: uint8 [H,W,C], C = 1 or 3; h, w: the target size, which the caller computes
+ * (gnn_input.compute_new_size).  mode ASEP_RESIZE_KEEP: every channel on its own -> out float32 [h,w] or [h,w,3], interleaved order
+ * kept.  ASEP_RESIZE_LUMA (C = 3 in R, G, B order only): each tap first becomes Pillow's convert('L') value
+ * (R*19595 + G*38470 + B*7471 + 0x8000) >> 16 -> out float32 [h,w]: a colour scan for a gray backbone.  Values 0..255 as fed to
+ * 'image:0'.  The _dev form takes device pointers and queues one kernel on `stream`, nothing is synchronised. */
+#define ASEP_RESIZE_KEEP 0
+#define ASEP_RESIZE_LUMA 1
+int asep_prep_resize_tf1(asep_post* p, const uint8_t* img, int H, int W, int C, int mode, int h, int w, float* out);
+int asep_prep_resize_tf1_dev(asep_post* p, const uint8_t* d_img, int H, int W, int C, int mode, int h, int w, float* d_out,
+                             void* stream);
 
 /* region_net_post_processor_base.py:230-251 apply_cc_analysis: drop 8-connected components whose pixel count is
  * below min_size (the caller evaluates int(size * threshold) in double like the reference).
