@@ -12,6 +12,7 @@
 #include "res8w_kernels.h"
 #include "res8ws_kernels.h"
 #include "level0_plan.h"
+#include "launch_plan.h"
 #include "convr_kernels.h"
 #include "split_kernels.h"
 #include "asep_common.h"
@@ -236,8 +237,6 @@ std::string targs(std::initializer_list<std::string> l) {
 inline std::string tb(bool b) { return b ? "true" : "false"; }
 inline std::string ti(int i) { return std::to_string(i); }
 
-struct TileDims { int tx, ty, begin; };
-
 // a schedule table on the device, owned by the handle; nullptr when it cannot be put there (the callers' contract)
 const int32_t* put_table(asep_aru* m, const std::vector<int32_t>& t) {
     try {
@@ -248,36 +247,19 @@ const int32_t* put_table(asep_aru* m, const std::vector<int32_t>& t) {
 }
 
 // XCD-aware order of the persistent fused kernels' tiles.  Workgroups are dealt round-robin to the 8 XCDs (block b
-// runs on XCD b % 8, each with its own 4 MB L2).  The tiles of every problem are first put into "super-tile" order
-// (groups of 4 x 8 tiles, groups walked down a column of groups first), the concatenated list is cut into 8 equal
-// chunks, and the k-th unit of work (k = block + i * grid) takes the (k / 8)-th tile of chunk k % 8: the 32 blocks of
-// an XCD work on spatially adjacent tiles at the same time, and on the rows just below right after, so the 8-row /
-// 14-column halo overlap of neighbouring tiles is served by that XCD's L2 instead of being fetched again.
+// runs on XCD b % 8, each with its own 4 MB L2).  In the order of xcd_order (launch_plan.h) the 32 blocks of an XCD work on spatially adjacent
+// tiles at the same time, and on the rows just below right after, so the 8-row / 14-column halo overlap of neighbouring tiles is served by
+// that XCD's L2 instead of being fetched again.
 //
 // work unit -> tile table of the PERSISTENT kernels (res8v_*, res32_tail_kernel: resident blocks walk the units with a grid stride) for the
-// problems' tile grids `probs` (tile numbers begin + ty * tx + x, `total` tiles in all): the tiles of every problem in 4 x 8 super-tile
-// order, cut into eight chunks, unit k = the (k / 8)-th tile of chunk k mod 8 (block b runs on XCD b mod 8).  nullptr on failure: identity.
+// problems' tile grids `probs`, cached on the device.  nullptr on failure: identity.
 const int32_t* xcd_schedule(asep_aru* m, const std::vector<TileDims>& probs, int total) {
     std::string key = "u";
     for (const TileDims& q : probs) key += ":" + std::to_string(q.tx) + "x" + std::to_string(q.ty);
     auto it = m->sched_cache.find(key);
     if (it != m->sched_cache.end()) return it->second;
-    std::vector<int32_t> order;
-    order.reserve(total);
-    for (const TileDims& q : probs)
-        for (int gc = 0; gc * 8 < q.tx; ++gc)
-            for (int gr = 0; gr * 4 < q.ty; ++gr)
-                for (int r = 0; r < 4; ++r)
-                    for (int c = 0; c < 8; ++c) {
-                        const int ty = gr * 4 + r, tx = gc * 8 + c;
-                        if (ty < q.ty && tx < q.tx) order.push_back(q.begin + ty * q.tx + tx);
-                    }
-    if ((int)order.size() != total) return nullptr;
-    std::vector<int32_t> sched(total);
-    int off[9];
-    off[0] = 0;
-    for (int x = 0; x < 8; ++x) off[x + 1] = off[x] + (total - x + 7) / 8;
-    for (int k = 0; k < total; ++k) sched[k] = order[off[k % 8] + k / 8];
+    const std::vector<int32_t> sched = xcd_order(probs, total);      // (launch_plan.h)
+    if (sched.empty()) return nullptr;
     const int32_t* d = put_table(m, sched);
     if (d) m->sched_cache[key] = d;
     return d;
@@ -294,21 +276,18 @@ const int32_t* tile_schedule(asep_aru* m, const Res8Args& a, int nblocks, int un
 // one-shot kernels (one block per tile): XCD bands (XcdMap, aru_kernels.h) from a few waves of blocks per XCD on.  *n_units = blocks to launch
 // along x (the grid is padded to eight equal chunks; surplus blocks leave at once).
 XcdMap oneshot_map(asep_aru* m, int total, int* n_units) {
-    XcdMap xm{0, total};
-    if (n_units) *n_units = total;
-    if (!m->use_xcd_sched || total < 8 * 64) return xm;
-    xm.chunk = (total + 7) / 8;
-    if (n_units) *n_units = 8 * xm.chunk;
-    return xm;
+    const OneshotPlan p = oneshot_plan(total, m->use_xcd_sched);     // (launch_plan.h)
+    if (n_units) *n_units = p.units;
+    return XcdMap{p.chunk, total};
 }
 
 // ---- kernel launchers: every launch covers one layer of a LIST of problems (pages x scales) -----------------
 typedef std::vector<Tensor> TL;
 
-Tensor new_tensor(asep_aru* m, int H, int W, int C) {
+Tensor new_tensor(asep_aru* m, int H, int W, int C, bool bf = false) {     // bf: a bf16 tensor of the native bf16 path
     Tensor t;
-    t.H = H; t.W = W; t.C = C;
-    t.p = (float*)m->cur->pool.get(t.count() * sizeof(float));
+    t.H = H; t.W = W; t.C = C; t.bf = bf;
+    t.p = (float*)m->cur->pool.get(t.count() * (bf ? sizeof(bf16_t) : sizeof(float)));
     return t;
 }
 
@@ -320,6 +299,40 @@ std::string dims_of(const TL& l) {
     if (l.size() > 3) d += "+..(" + std::to_string(l.size()) + ")";
     return d;
 }
+
+// the usual layer text of a profiler record: scope, the pages of the launch, channels in -> out
+std::string layer_text(const std::string& scope, const TL& sub, int cin, int cout) {
+    return scope + " " + dims_of(sub) + " " + std::to_string(cin) + "->" + std::to_string(cout);
+}
+
+// One launch of a launcher: problems [b0, b1) of its list, the numbering of their work units (launch_plan.h) and the record's sums so far.
+struct Chunk {
+    size_t b0, b1;
+    UnitCounter units;
+    double flops = 0, bytes = 0;
+    TL sub(const TL& l) const { return TL(l.begin() + b0, l.begin() + b1); }
+};
+template <class A> auto set_total(A& a, int t, int) -> decltype((void)(a.total_tiles = t)) { a.total_tiles = t; }
+template <class A> auto set_total(A& a, int t, long) -> decltype((void)(a.total = t)) { a.total = t; }
+template <class A> void set_total(A&, int, ...) {}
+// The skeleton of every layer launcher: the n problems of a list in launches of at most MAXP.  Per launch a value-initialised Args; fill(p, i, k)
+// sets slot p = a.p[i - b0] of problem i, takes its unit numbers from k.units and adds its flops and bytes to k (bytes starts at bytes0, the
+// launcher's filter term); then nprob and the total (where Args has one) are set and launch(a, k) picks the kernel and launches.
+template <class Args, class Fill, class Launch>
+void for_chunks(size_t n, double bytes0, Fill fill, Launch launch) {
+    for (size_t c = 0; c < num_chunks(n); ++c) {
+        Args a{};
+        Chunk k{chunk_begin(c), chunk_end(n, c)};
+        k.bytes = bytes0;
+        for (size_t i = k.b0; i < k.b1; ++i) fill(a.p[i - k.b0], i, k);
+        a.nprob = (int)(k.b1 - k.b0);
+        set_total(a, k.units.total, 0);
+        launch(a, k);
+    }
+}
+// problem slot <- its 2-D tile numbering
+template <class P>
+void set_tiles(P& p, const Units& u) { p.tiles_x = u.per_row; p.tile_begin = u.begin; }
 
 // launches conv_mfma_kernel<...> and gives the profiler record that instantiation's exact name
 #define ASEP_CONV_LAUNCH(KH_, KW_, MT_, C8_, TH_, DB_, BF_, C12_, MB_)                                                   \
@@ -333,7 +346,7 @@ void launch_conv_k(asep_aru* m, const PackedConv& pc, const ConvArgs& a, int tot
                    const std::string& scope, const TL& in0, bool big_tile) {
     const int mt = pc.c8 ? 1 : (pc.mtiles % 4 == 0 ? 4 : (pc.mtiles % 2 == 0 ? 2 : 1));
     dim3 grid(total_tiles, pc.mtiles / mt);                  // (total_tiles = the schedule's units: padded to 8 when grid.y > 1)
-    ProfScope ps(m, "conv_mfma_kernel", flops, scope + " " + dims_of(in0) + " " + std::to_string(pc.cin) + "->" + std::to_string(pc.cout));
+    ProfScope ps(m, "conv_mfma_kernel", flops, layer_text(scope, in0, pc.cin, pc.cout));
     ps.bytes = bytes;
     hipStream_t s = m->stream;
     const bool res_op = a.p[0].res != nullptr;
@@ -369,6 +382,22 @@ TL run_pool(asep_aru* m, const TL& in, PoolKind kind);
         hipLaunchKernelGGL((convs_kernel<KH_, KW_, C16_, MT_, TH_, MB_>), grid, dim3(256), 0, m->stream, a);          \
     } while (0)
 
+// the filter term of a conv launch's bytes (esize bytes per value) and the problem slot of the fp32 / f32s conv launchers: operands, tw x th tiles,
+// 2 * MAC flops, every operand tensor once
+double conv_wbytes(const PackedConv& pc, double esize) { return (double)pc.kh * pc.kw * pc.cin * pc.cout * esize; }
+auto conv_fill(const PackedConv& pc, int tw, int th, const TL& in0, const TL* in1, const TL* res, const TL& out, const TL* pool) {
+    return [=, &pc, &in0, &out](ConvProb& p, size_t i, Chunk& k) {
+        p.in0 = in0[i].p; p.in1 = in1 ? (*in1)[i].p : nullptr; p.res = res ? (*res)[i].p : nullptr;
+        p.out = out.empty() ? nullptr : out[i].p;
+        p.pool = pool ? (*pool)[i].p : nullptr;
+        p.H = p.Ho = in0[i].H; p.W = p.Wo = in0[i].W;
+        set_tiles(p, k.units.next_tiles(p.H, p.W, tw, th));
+        k.flops += 2.0 * in0[i].H * in0[i].W * pc.kh * pc.kw * (double)pc.cin * pc.cout;
+        k.bytes += tbytes(in0[i]) + (in1 ? tbytes((*in1)[i]) : 0.0) + (res ? tbytes((*res)[i]) : 0.0) + (out.empty() ? 0.0 : tbytes(out[i])) +
+                   (pool ? tbytes((*pool)[i]) : 0.0);
+    };
+}
+
 // a conv layer on the split-product kernel (split_kernels.h): same operands and results as run_conv's fp32 kernels
 TL run_conv_split(asep_aru* m, const PackedConv& pc, const std::string& scope, const TL& in0, const TL* in1, bool relu_in, bool relu_out,
                   const TL* res, TL* pooled, bool keep_full, int act) {
@@ -388,37 +417,17 @@ TL run_conv_split(asep_aru* m, const PackedConv& pc, const std::string& scope, c
     const bool alds = pc.d_ws16 && pc.mtiles == 1;
     const int mt = (pc.mtiles % 4 == 0 && !c16) ? 4 : (pc.mtiles % 2 == 0 ? 2 : 1);
     const int th = (c16 && pc.kh == 3 && mt == 1) ? 16 : 8;
-    for (size_t b0 = 0; b0 < in0.size(); b0 += MAXP) {
-        const size_t b1 = std::min(in0.size(), b0 + MAXP);
-        ConvArgs a{};
-        int tiles = 0;
-        double flops = 0, bytes = (double)pc.kh * pc.kw * pc.cin * pc.cout * 4.0;
-        for (size_t i = b0; i < b1; ++i) {
-            ConvProb& p = a.p[i - b0];
-            p.in0 = in0[i].p; p.in1 = in1 ? (*in1)[i].p : nullptr; p.res = res ? (*res)[i].p : nullptr;
-            p.out = out.empty() ? nullptr : out[i].p;
-            p.pool = fuse_pool ? (*pooled)[i].p : nullptr;
-            p.H = p.Ho = in0[i].H; p.W = p.Wo = in0[i].W;
-            p.tiles_x = (in0[i].W + 31) / 32;
-            p.tile_begin = tiles;
-            tiles += p.tiles_x * ((in0[i].H + th - 1) / th);
-            flops += 2.0 * in0[i].H * in0[i].W * pc.kh * pc.kw * (double)pc.cin * pc.cout;
-            bytes += tbytes(in0[i]) + (in1 ? tbytes((*in1)[i]) : 0.0) + (res ? tbytes((*res)[i]) : 0.0) + (out.empty() ? 0.0 : tbytes(out[i])) +
-                     (fuse_pool ? tbytes((*pooled)[i]) : 0.0);
-        }
-        a.nprob = (int)(b1 - b0);
-        a.total_tiles = tiles;
+    for_chunks<ConvArgs>(in0.size(), conv_wbytes(pc, 4.0), conv_fill(pc, CONV_TW, th, in0, in1, res, out, fuse_pool ? pooled : nullptr), [&](ConvArgs& a, const Chunk& k) {
         a.c0 = in0[0].C; a.c1 = in1 ? (*in1)[0].C : 0;
         a.wpk = (const f32x4*)(alds ? pc.d_ws16 : pc.d_ws); a.bias = pc.d_b;
         a.cout = pc.cout; a.mtiles = pc.mtiles; a.groups = alds ? pc.cin / 16 : pc.cin / 32;
         a.relu_in = relu_in; a.relu_out = relu_out; a.act = act;
         a.skip_full = fuse_pool && !keep_full;
-        int units = tiles;
-        a.xm = oneshot_map(m, tiles, &units);
+        int units;
+        a.xm = oneshot_map(m, k.units.total, &units);
         dim3 grid(units, pc.mtiles / mt);
-        TL sub(in0.begin() + b0, in0.begin() + b1);
-        ProfScope ps(m, "convs_kernel", flops, scope + " " + dims_of(sub) + " " + std::to_string(pc.cin) + "->" + std::to_string(pc.cout));
-        ps.bytes = bytes;
+        ProfScope ps(m, "convs_kernel", k.flops, layer_text(scope, k.sub(in0), pc.cin, pc.cout));
+        ps.bytes = k.bytes;
         if (alds) {                                          // (one m-tile: mt == 1)
             ps.set_name("convs16_kernel<1,8,3,true>");
             hipLaunchKernelGGL((convs16_kernel<1, 8, 3, true>), grid, dim3(256), 0, m->stream, a);
@@ -434,7 +443,7 @@ TL run_conv_split(asep_aru* m, const PackedConv& pc, const std::string& scope, c
             else if (c16) ASEP_CONVS_LAUNCH(4, 4, true, 1, 8, 2);
             else { set_error("internal: conv %s (4x4, %d input channels) was packed for the split-product kernel", scope.c_str(), pc.cin); throw ArgError(); }
         }
-    }
+    });
     if (pooled && !fuse_pool) *pooled = run_pool(m, out, POOL_MAX);
     return out;
 }
@@ -463,32 +472,22 @@ TL run_conv(asep_aru* m, const std::string& scope, const TL& in0, const TL* in1,
         // single output channel (attention conv4): one pixel per thread on the vector ALU
         TL out1;
         for (const Tensor& t : in0) out1.push_back(new_tensor(m, t.H, t.W, 1));
-        for (size_t b0 = 0; b0 < in0.size(); b0 += MAXP) {
-            const size_t b1 = std::min(in0.size(), b0 + MAXP);
-            ConvArgs a{};
-            int tiles = 0;
-            double flops = 0, bytes = 0;
-            for (size_t i = b0; i < b1; ++i) {
-                ConvProb& p = a.p[i - b0];
-                p.in0 = in0[i].p; p.out = out1[i].p;
-                p.H = p.Ho = in0[i].H; p.W = p.Wo = in0[i].W;
-                p.tiles_x = cdiv(in0[i].W, C1O_T);
-                p.tile_begin = tiles;
-                tiles += p.tiles_x * cdiv(in0[i].H, C1O_T);
-                flops += 2.0 * in0[i].H * in0[i].W * 16.0 * pc.cin;
-                bytes += tbytes(in0[i]) + tbytes(out1[i]);
-            }
-            a.nprob = (int)(b1 - b0);
-            a.total_tiles = tiles;
+        for_chunks<ConvArgs>(in0.size(), 0.0, [&](ConvProb& p, size_t i, Chunk& k) {
+            p.in0 = in0[i].p; p.out = out1[i].p;
+            p.H = p.Ho = in0[i].H; p.W = p.Wo = in0[i].W;
+            set_tiles(p, k.units.next_tiles(p.H, p.W, C1O_T, C1O_T));
+            k.flops += 2.0 * in0[i].H * in0[i].W * 16.0 * pc.cin;
+            k.bytes += tbytes(in0[i]) + tbytes(out1[i]);
+        }, [&](ConvArgs& a, const Chunk& k) {
             a.c0 = pc.cin; a.cout = 1;
             a.wpk = (const f32x4*)pc.d_wv; a.bias = pc.d_b;
             a.relu_in = relu_in; a.relu_out = relu_out; a.act = act;
-            int units = tiles;
-            a.xm = oneshot_map(m, tiles, &units);
-            ProfScope ps(m, "conv_c1out_kernel", flops, scope);
-            ps.bytes = bytes;
+            int units;
+            a.xm = oneshot_map(m, k.units.total, &units);
+            ProfScope ps(m, "conv_c1out_kernel", k.flops, scope);
+            ps.bytes = k.bytes;
             hipLaunchKernelGGL(conv_c1out_kernel, dim3(units), dim3(256), 0, m->stream, a);
-        }
+        });
         return out1;
     }
     if (m->split && pc.d_ws) return run_conv_split(m, pc, scope, in0, in1, relu_in, relu_out, res, pooled, keep_full, act);
@@ -506,62 +505,26 @@ TL run_conv(asep_aru* m, const std::string& scope, const TL& in0, const TL* in1,
     // block against the fixed load latency of these short blocks)
     // (two channel groups only for the residual-free 3x3 variant: four blocks per CU hide the refill of its single LDS buffer)
     const bool big_tile = !wino && (!pc.c8 || (pc.kh == 3 && !res)) && (pc.groups == 1 || (pc.groups == 2 && !res && pc.kh == 3)) && pc.mtiles == 1;
-    const int th = big_tile ? 16 : CONV_TH;
-    for (size_t b0 = 0; b0 < in0.size(); b0 += MAXP) {
-        const size_t b1 = std::min(in0.size(), b0 + MAXP);
-        ConvArgs a{};
-        int tiles = 0;
-        double flops = 0, bytes = (double)pc.kh * pc.kw * pc.cin * pc.cout * 4.0;
-        for (size_t i = b0; i < b1; ++i) {
-            ConvProb& p = a.p[i - b0];
-            p.in0 = in0[i].p; p.in1 = in1 ? (*in1)[i].p : nullptr; p.res = res ? (*res)[i].p : nullptr;
-            p.out = out.empty() ? nullptr : out[i].p;
-            p.pool = fuse_pool ? (*pooled)[i].p : nullptr;
-            p.H = p.Ho = in0[i].H; p.W = p.Wo = in0[i].W;
-            p.tiles_x = cdiv(in0[i].W, CONV_TW);
-            p.tile_begin = tiles;
-            tiles += p.tiles_x * cdiv(in0[i].H, th);
-            flops += 2.0 * in0[i].H * in0[i].W * pc.kh * pc.kw * (double)pc.cin * pc.cout;
-            bytes += tbytes(in0[i]) + (in1 ? tbytes((*in1)[i]) : 0.0) + (res ? tbytes((*res)[i]) : 0.0) + (out.empty() ? 0.0 : tbytes(out[i])) +
-                     (fuse_pool ? tbytes((*pooled)[i]) : 0.0);
-        }
-        a.nprob = (int)(b1 - b0);
-        a.total_tiles = tiles;
+    // Winograd blocks are 4 x 32 output pixels, those of the register-resident variant for one m-tile 8 x 32
+    const int tw = wino ? WINO_TW : CONV_TW, th = wino ? (wino_mt == 1 ? 2 * WINO_TH : WINO_TH) : (big_tile ? 16 : CONV_TH);
+    for_chunks<ConvArgs>(in0.size(), conv_wbytes(pc, 4.0), conv_fill(pc, tw, th, in0, in1, res, out, fuse_pool ? pooled : nullptr), [&](ConvArgs& a, const Chunk& k) {
         a.c0 = in0[0].C; a.c1 = in1 ? (*in1)[0].C : 0;
-        a.wpk = (const f32x4*)pc.d_w; a.bias = pc.d_b;
+        a.wpk = (const f32x4*)(wino ? pc.d_wino : pc.d_w); a.bias = pc.d_b;
         a.cout = pc.cout; a.mtiles = pc.mtiles; a.groups = pc.groups;
         a.relu_in = relu_in; a.relu_out = relu_out; a.act = act;
         a.skip_full = fuse_pool && !keep_full;
-        TL sub(in0.begin() + b0, in0.begin() + b1);
+        const TL sub = k.sub(in0);
+        int units;
+        a.xm = oneshot_map(m, k.units.total, &units);
         if (wino) {
-            a.wpk = (const f32x4*)pc.d_wino;
-            int wt = 0;
-            for (size_t i = b0; i < b1; ++i) {              // Winograd blocks are 4 x 32 output pixels
-                ConvProb& p = a.p[i - b0];
-                p.tiles_x = cdiv(in0[i].W, WINO_TW);
-                p.tile_begin = wt;
-                wt += p.tiles_x * cdiv(in0[i].H, WINO_TH);
-            }
             const int mt = wino_mt;
-            if (mt == 1) {                                   // register-resident variant for one m-tile: 8 x 32 pixel blocks
-                wt = 0;
-                for (size_t i = b0; i < b1; ++i) {
-                    ConvProb& p = a.p[i - b0];
-                    p.tile_begin = wt;
-                    wt += p.tiles_x * cdiv(in0[i].H, 2 * WINO_TH);
-                }
-            }
-            a.total_tiles = wt;
-            const int ny = pc.mtiles / mt;
-            int wunits = wt;
-            a.xm = oneshot_map(m, wt, &wunits);
-            dim3 grid(wunits, ny);
+            dim3 grid(units, pc.mtiles / mt);
             std::string pname;
             if (mt == 1) pname = "conv_winor_kernel<false,1,true>";
             else if (mt == 2) pname = !res ? "conv_winor_kernel<false,2,false>" : "conv_winor_kernel<false,2,true>";
             else pname = "conv_wino_kernel" + targs({ti(mt), tb(false)});
-            ProfScope ps(m, pname, flops, scope + " " + dims_of(sub) + " " + std::to_string(pc.cin) + "->" + std::to_string(pc.cout));
-            ps.bytes = bytes;
+            ProfScope ps(m, pname, k.flops, layer_text(scope, sub, pc.cin, pc.cout));
+            ps.bytes = k.bytes;
             if (mt == 1) {
                 hipLaunchKernelGGL((conv_winor_kernel<false, 1, true>), grid, dim3(256), 0, m->stream, a);
             } else if (mt == 2) {
@@ -569,13 +532,9 @@ TL run_conv(asep_aru* m, const std::string& scope, const TL& in0, const TL* in1,
                 if (!res) hipLaunchKernelGGL((conv_winor_kernel<false, 2, false>), grid, dim3(256), 0, m->stream, a);
                 else hipLaunchKernelGGL((conv_winor_kernel<false, 2, true>), grid, dim3(256), 0, m->stream, a);
             } else hipLaunchKernelGGL((conv_wino_kernel<4>), grid, dim3(256), 0, m->stream, a);
-        } else {
-            int units = tiles;
-            a.xm = oneshot_map(m, tiles, &units);
-            if (pc.kh == 3) launch_conv_k<3, 3>(m, pc, a, units, flops, bytes, scope, sub, big_tile);
-            else launch_conv_k<4, 4>(m, pc, a, units, flops, bytes, scope, sub, big_tile);
-        }
-    }
+        } else if (pc.kh == 3) launch_conv_k<3, 3>(m, pc, a, units, k.flops, k.bytes, scope, sub, big_tile);
+        else launch_conv_k<4, 4>(m, pc, a, units, k.flops, k.bytes, scope, sub, big_tile);
+    });
     if (pooled && !fuse_pool) *pooled = run_pool(m, out, POOL_MAX);
     return out;
 }
@@ -603,35 +562,26 @@ TL run_deconv(asep_aru* m, const std::string& scope, const TL& in, const TL& lik
 #define DS_ROWS 8                  // input rows per block of deconvs_kernel (16: 280 / 310 / 477 us against 260 / 312 / 440)
 #endif
     const bool splitd = m->split && m->use_deconvs && pc.d_ws && pc.smode == 2 && !valu;   // >= 32 input channels: split products (deconvs_kernel)
-    for (size_t b0 = 0; b0 < in.size(); b0 += MAXP) {
-        const size_t b1 = std::min(in.size(), b0 + MAXP);
-        ConvArgs a{};
-        int tiles = 0;
-        double flops = 0, bytes = 9.0 * pc.cin * pc.cout * 4.0;
-        for (size_t i = b0; i < b1; ++i) {
-            ConvProb& p = a.p[i - b0];
-            p.in0 = in[i].p; p.in1 = nullptr; p.res = nullptr; p.out = out[i].p;
-            p.H = in[i].H; p.W = in[i].W; p.Ho = out[i].H; p.Wo = out[i].W;
-            p.pbh = std::max((in[i].H - 1) * 2 + 3 - out[i].H, 0) / 2;
-            p.pbw = std::max((in[i].W - 1) * 2 + 3 - out[i].W, 0) / 2;
-            p.tiles_x = cdiv(in[i].W, valu ? DCV_T : DC_TW);
-            p.tile_begin = tiles;
-            tiles += p.tiles_x * cdiv(in[i].H, valu ? DCV_T : (splitd ? DS_ROWS : DC_TH));
-            flops += 2.0 * in[i].H * in[i].W * 9.0 * pc.cin * pc.cout;
-            bytes += tbytes(in[i]) + tbytes(out[i]);
-        }
-        a.nprob = (int)(b1 - b0);
+    const int tw = valu ? DCV_T : DC_TW, th = valu ? DCV_T : (splitd ? DS_ROWS : DC_TH);
+    for_chunks<ConvArgs>(in.size(), 9.0 * pc.cin * pc.cout * 4.0, [&](ConvProb& p, size_t i, Chunk& k) {
+        p.in0 = in[i].p; p.in1 = nullptr; p.res = nullptr; p.out = out[i].p;
+        p.H = in[i].H; p.W = in[i].W; p.Ho = out[i].H; p.Wo = out[i].W;
+        p.pbh = std::max((in[i].H - 1) * 2 + 3 - out[i].H, 0) / 2;
+        p.pbw = std::max((in[i].W - 1) * 2 + 3 - out[i].W, 0) / 2;
+        set_tiles(p, k.units.next_tiles(p.H, p.W, tw, th));
+        k.flops += 2.0 * in[i].H * in[i].W * 9.0 * pc.cin * pc.cout;
+        k.bytes += tbytes(in[i]) + tbytes(out[i]);
+    }, [&](ConvArgs& a, const Chunk& k) {
         a.c0 = in[0].C; a.c1 = 0;
         a.wpk = (const f32x4*)pc.d_w; a.bias = pc.d_b;
         a.cout = pc.cout; a.mtiles = pc.mtiles; a.groups = pc.groups;
         a.relu_in = 0; a.relu_out = relu_out; a.act = act;
-        int units = tiles;
-        a.xm = oneshot_map(m, tiles, &units);
+        int units;
+        a.xm = oneshot_map(m, k.units.total, &units);
         dim3 grid(units, pc.mtiles / mt);
         const std::string dname = valu ? std::string("deconv8v_kernel") : (splitd ? "deconvs_kernel" + targs({ti(mt), ti(DS_ROWS)}) : "deconv_mfma_kernel" + targs({ti(mt), tb(false)}));
-        TL sub(in.begin() + b0, in.begin() + b1);
-        ProfScope ps(m, dname, flops, scope + " " + dims_of(sub) + " " + std::to_string(pc.cin) + "->" + std::to_string(pc.cout));
-        ps.bytes = bytes;
+        ProfScope ps(m, dname, k.flops, layer_text(scope, k.sub(in), pc.cin, pc.cout));
+        ps.bytes = k.bytes;
         if (valu) {
             a.wpk = (const f32x4*)pc.d_wv;
             hipLaunchKernelGGL(deconv8v_kernel, dim3(units), dim3(256), 0, m->stream, a);
@@ -641,46 +591,61 @@ TL run_deconv(asep_aru* m, const std::string& scope, const TL& in, const TL& lik
             else hipLaunchKernelGGL((deconvs_kernel<1, DS_ROWS>), grid, dim3(256), 0, m->stream, a);
         } else if (mt == 2) hipLaunchKernelGGL((deconv_mfma_kernel<2>), grid, dim3(256), 0, m->stream, a);
         else hipLaunchKernelGGL((deconv_mfma_kernel<1>), grid, dim3(256), 0, m->stream, a);
-    }
+    });
     return out;
 }
 
 // launches conv_c3_kernel<cout, bf> (defined at the end of this file)
 void launch_conv_c3(asep_aru* m, const C1Args& a, int cout, bool bf, int tiles);
 
-// first layer (Cin == 1, or the interleaved 3-channel page of a colour net); stats[i] = per-problem {mean, 1/std} pointer or nullptr
+// first layer (Cin == 1, or the interleaved 3-channel page of a colour net); stats[i] = per-problem {mean, 1/std} pointer or nullptr.
+// bf16 engine: fp32 image -> bf16 [H,W,8] (pre-ReLU t of unet_down_0, or the activated conv1 of graph 'U')
 TL run_direct(asep_aru* m, const DirectConv& dc, const TL& imgs, bool relu, const std::vector<const float*>& stats, int act = 0) {
+    const bool bf = m->bf16, rgb = dc.cin == 3;              // colour net: conv_c3_kernel
+    if (bf && (dc.k != 3 || dc.cout != 8 || (dc.cin != 1 && !rgb))) {    // (the bf16 engine is a feat_root 8 engine: combine_kernel)
+        set_error("bf16 path: first-layer conv k=%d cin=%d cout=%d not instantiated", dc.k, dc.cin, dc.cout);
+        throw ArgError();
+    }
     TL out;
-    for (const Tensor& t : imgs) out.push_back(new_tensor(m, t.H, t.W, dc.cout));
-    for (size_t b0 = 0; b0 < imgs.size(); b0 += MAXP) {
-        const size_t b1 = std::min(imgs.size(), b0 + MAXP);
-        C1Args a{};
-        int tiles = 0;
-        double flops = 0, bytes = 0;
-        for (size_t i = b0; i < b1; ++i) {
-            C1Prob& p = a.p[i - b0];
-            p.img = imgs[i].p; p.out = out[i].p; p.stats = stats.empty() ? nullptr : stats[i];
-            p.H = imgs[i].H; p.W = imgs[i].W;
-            p.tiles_x = cdiv(imgs[i].W, 64);
-            p.tile_begin = tiles;
-            tiles += p.tiles_x * cdiv(imgs[i].H, 4);
-            flops += 2.0 * imgs[i].H * imgs[i].W * dc.k * dc.k * dc.cin * dc.cout;
-            bytes += tbytes(imgs[i]) + tbytes(out[i]);
-        }
-        a.nprob = (int)(b1 - b0);
+    for (const Tensor& t : imgs) out.push_back(new_tensor(m, t.H, t.W, dc.cout, bf));
+    for_chunks<C1Args>(imgs.size(), 0.0, [&](C1Prob& p, size_t i, Chunk& k) {
+        p.img = imgs[i].p; p.out = out[i].p; p.stats = stats.empty() ? nullptr : stats[i];
+        p.H = imgs[i].H; p.W = imgs[i].W;
+        set_tiles(p, k.units.next_tiles(p.H, p.W, 64, 4));
+        k.flops += 2.0 * imgs[i].H * imgs[i].W * dc.k * dc.k * dc.cin * dc.cout;
+        k.bytes += tbytes(imgs[i]) + tbytes(out[i]);
+    }, [&](C1Args& a, const Chunk& k) {
         a.w = dc.d_w; a.bias = dc.d_b; a.relu = relu ? 1 : 0; a.act = act;
-        ProfScope ps(m, dc.cin == 3 ? "conv_c3_kernel<" + std::to_string(dc.cout) + ",false>"
-                                    : "conv_c1_kernel<" + std::to_string(dc.k) + "," + std::to_string(dc.cout) + ">", flops);
-        ps.bytes = bytes;
+        ProfScope ps(m, rgb ? "conv_c3_kernel<" + std::to_string(dc.cout) + "," + tb(bf) + ">"
+                            : "conv_c1_kernel<" + std::to_string(dc.k) + "," + std::to_string(dc.cout) + (bf ? ",true>" : ">"), k.flops);
+        ps.bytes = k.bytes;
+        const int tiles = k.units.total;
         dim3 grid(tiles);
-        if (dc.cin == 3 && dc.k == 3 && (dc.cout == 8 || dc.cout == 16)) launch_conv_c3(m, a, dc.cout, false, tiles);
+        if (rgb && dc.k == 3 && (dc.cout == 8 || (dc.cout == 16 && !bf))) launch_conv_c3(m, a, dc.cout, bf, tiles);
         else if (dc.cin != 1) { set_error("first-layer conv k=%d cin=%d cout=%d not instantiated", dc.k, dc.cin, dc.cout); throw ArgError(); }
+        else if (bf) hipLaunchKernelGGL((conv_c1_kernel<3, 8, true>), grid, dim3(256), 0, m->stream, a);
         else if (dc.k == 3 && dc.cout == 8) hipLaunchKernelGGL((conv_c1_kernel<3, 8>), grid, dim3(256), 0, m->stream, a);
         else if (dc.k == 3 && dc.cout == 16) hipLaunchKernelGGL((conv_c1_kernel<3, 16>), grid, dim3(256), 0, m->stream, a);
         else if (dc.k == 4 && dc.cout == 12) hipLaunchKernelGGL((conv_c1_kernel<4, 12>), grid, dim3(256), 0, m->stream, a);
         else { set_error("first-layer conv k=%d cout=%d not instantiated", dc.k, dc.cout); throw ArgError(); }
-    }
+    });
     return out;
+}
+
+// The streaming passes (pools, channel sums, act_kernel): one launch of 256-thread blocks per chunk, every problem a range of blocks of
+// `per_block` items over the tensors `l`.  fill(p, i, k) sets problem i's pointers and dims, adds its bytes to k and returns its items;
+// launch(a, grid) launches.
+template <class Args, class Fill, class Launch>
+void stream_pass(asep_aru* m, const TL& l, const char* name, size_t per_block, Fill fill, Launch launch) {
+    for_chunks<Args>(l.size(), 0.0, [&](auto& p, size_t i, Chunk& k) {
+        const size_t items = fill(p, i, k);
+        p.blk_begin = k.units.next_blocks(items, per_block).begin;
+    }, [&](Args& a, const Chunk& k) {
+        a.C = l[0].C;
+        ProfScope ps(m, name, 0.0);
+        ps.bytes = k.bytes;
+        launch(a, dim3(k.units.total));
+    });
 }
 
 TL run_pool(asep_aru* m, const TL& in, PoolKind kind) {
@@ -689,27 +654,16 @@ TL run_pool(asep_aru* m, const TL& in, PoolKind kind) {
         if (kind == POOL_CHANSUM) out.push_back(new_tensor(m, t.H, t.W, 1));
         else out.push_back(new_tensor(m, cdiv(t.H, 2), cdiv(t.W, 2), t.C));
     }
-    for (size_t b0 = 0; b0 < in.size(); b0 += MAXP) {
-        const size_t b1 = std::min(in.size(), b0 + MAXP);
-        PoolArgs a{};
-        int blocks = 0;
-        double bytes = 0;
-        for (size_t i = b0; i < b1; ++i) {
-            bytes += tbytes(in[i]) + tbytes(out[i]);
-            PoolProb& p = a.p[i - b0];
+    stream_pass<PoolArgs>(m, in, kind == POOL_MAX ? "maxpool2_kernel" : (kind == POOL_AVG_C1 ? "avgpool2_c1_kernel" : "chansum_kernel"), POOL_ITEMS,
+        [&](PoolProb& p, size_t i, Chunk& k) {
+            k.bytes += tbytes(in[i]) + tbytes(out[i]);
             p.in = in[i].p; p.out = out[i].p; p.H = in[i].H; p.W = in[i].W; p.Ho = out[i].H; p.Wo = out[i].W;
-            p.blk_begin = blocks;
-            const size_t items = kind == POOL_MAX ? out[i].count() / 4 : (size_t)out[i].H * out[i].W;
-            blocks += (int)((items + POOL_ITEMS - 1) / POOL_ITEMS);
-        }
-        a.nprob = (int)(b1 - b0);
-        a.C = in[0].C;
-        ProfScope ps(m, kind == POOL_MAX ? "maxpool2_kernel" : (kind == POOL_AVG_C1 ? "avgpool2_c1_kernel" : "chansum_kernel"), 0.0);
-        ps.bytes = bytes;
-        if (kind == POOL_MAX) hipLaunchKernelGGL(maxpool2_kernel, dim3(blocks), dim3(256), 0, m->stream, a);
-        else if (kind == POOL_AVG_C1) hipLaunchKernelGGL(avgpool2_c1_kernel, dim3(blocks), dim3(256), 0, m->stream, a);
-        else hipLaunchKernelGGL(chansum_kernel, dim3(blocks), dim3(256), 0, m->stream, a);
-    }
+            return kind == POOL_MAX ? out[i].count() / 4 : (size_t)out[i].H * out[i].W;
+        }, [&](const PoolArgs& a, dim3 grid) {
+            if (kind == POOL_MAX) hipLaunchKernelGGL(maxpool2_kernel, grid, dim3(256), 0, m->stream, a);
+            else if (kind == POOL_AVG_C1) hipLaunchKernelGGL(avgpool2_c1_kernel, grid, dim3(256), 0, m->stream, a);
+            else hipLaunchKernelGGL(chansum_kernel, grid, dim3(256), 0, m->stream, a);
+        });
     return out;
 }
 
@@ -806,25 +760,17 @@ void run_res8(asep_aru* m, bool up, const TL& in0, const TL* in1, const std::vec
     }
     const size_t lds = up ? R8_UP_LDS : R8_DOWN_LDS;
     const char* layer = up ? "unet_up_0" : "unet_down_0";
-    for (size_t b0 = 0; b0 < in0.size(); b0 += MAXP) {
-        const size_t b1 = std::min(in0.size(), b0 + MAXP);
-        Res8Args a{};
-        int tiles = 0;
-        double flops = 0, bytes = 0;
-        for (size_t i = b0; i < b1; ++i) {
-            bytes += tbytes(in0[i]) + (up ? tbytes((*in1)[i]) : 0.0) + tbytes((*d_out)[i]) + (want_pool ? tbytes((*pool_out)[i]) : 0.0);
-            Res8Prob& p = a.p[i - b0];
-            p.img = in0[i].p; p.in1 = up ? (*in1)[i].p : nullptr; p.stats = stats.empty() ? nullptr : stats[i];
-            p.out = (*d_out)[i].p; p.pool = want_pool ? (*pool_out)[i].p : nullptr;
-            p.H = in0[i].H; p.W = in0[i].W;
-            p.tiles_x = cdiv(in0[i].W, R8_OW);
-            p.tile_begin = tiles;
-            tiles += p.tiles_x * cdiv(in0[i].H, R8_OH * R8_NP);
-            flops += 2.0 * in0[i].H * in0[i].W * (9.0 * (up ? 16 : 1) * 8 + 3 * 9.0 * 64);
-        }
-        a.nprob = (int)(b1 - b0);
-        a.total_tiles = tiles;
-        TL sub(in0.begin() + b0, in0.begin() + b1);
+    for_chunks<Res8Args>(in0.size(), 0.0, [&](Res8Prob& p, size_t i, Chunk& k) {
+        k.bytes += tbytes(in0[i]) + (up ? tbytes((*in1)[i]) : 0.0) + tbytes((*d_out)[i]) + (want_pool ? tbytes((*pool_out)[i]) : 0.0);
+        p.img = in0[i].p; p.in1 = up ? (*in1)[i].p : nullptr; p.stats = stats.empty() ? nullptr : stats[i];
+        p.out = (*d_out)[i].p; p.pool = want_pool ? (*pool_out)[i].p : nullptr;
+        p.H = in0[i].H; p.W = in0[i].W;
+        set_tiles(p, k.units.next_tiles(p.H, p.W, R8_OW, R8_OH * R8_NP));
+        k.flops += 2.0 * in0[i].H * in0[i].W * (9.0 * (up ? 16 : 1) * 8 + 3 * 9.0 * 64);
+    }, [&](Res8Args& a, const Chunk& c) {
+        const int tiles = c.units.total;
+        const double flops = c.flops, bytes = c.bytes;
+        const TL sub = c.sub(in0);
         const bool valu = m->r8_valu && r8v_fits(sub);       // vector-ALU kernels, with weights in their own order
         if (up) { a.w1 = valu ? m->d_r8v_up_w1 : m->d_r8_up_w1; a.b1 = m->d_r8_up_b1; }
         else { a.w1 = m->det_first.d_w; a.b1 = m->det_first.d_b; }
@@ -851,28 +797,27 @@ void run_res8(asep_aru* m, bool up, const TL& in0, const TL* in1, const std::vec
                     hipLaunchKernelGGL(k.fn, dim3(std::min(nu, m->num_cus)), dim3(R8_THREADS), lds, m->stream, f);
                 }
                 run_res8ws(m, up, a, walk, res8_what(up, sub));
-                continue;
+                return;
             }
         }
         ProfScope ps(m, k.name, flops, res8_what(up, sub));
         ps.bytes = bytes;
         if (actv && !valu) { set_error("level-0 block of an elu / leaky graph: image too large for the vector-ALU kernel"); throw ArgError(); }
         hipLaunchKernelGGL(k.fn, dim3(std::min(tiles, m->num_cus)), dim3(R8_THREADS), lds, m->stream, a);
-    }
+    });
 }
 
 // ================================================================================================
 // Native bf16 data path (cfg.compute_dtype == 1): launchers of bf16_kernels.h
 // ================================================================================================
-Tensor new_tensor_bf(asep_aru* m, int H, int W, int C);
 void run_res8b_tiles(asep_aru* m, bool up, const TL& a0, const TL* a1, const std::vector<const float*>& stats, bool want_pool, const TL& outs, const TL* pool_out);
 
 // whole level-0 blocks of the bf16 path (res8b_kernel)
 // A level-0 block (up: [skip, deconv] in; down: the fp32 image in, pool out) of the pages the strip walker serves (res8w_kernels.h): one launch of
 // walker items (one wave each) + one launch of the border tiles around the walkers' regions.  `outs` / `pools` are the pages' output tensors.
 void run_res8w(asep_aru* m, bool up, const TL& in0, const TL* dec, const std::vector<const float*>& stats, const TL& outs, const TL* pools) {
-    for (size_t b0 = 0; b0 < in0.size(); b0 += MAXP) {
-        const size_t b1 = std::min(in0.size(), b0 + MAXP);
+    for (size_t c = 0; c < num_chunks(in0.size()); ++c) {      // (two argument structs, a band rule over the whole launch: not on for_chunks)
+        const size_t b0 = chunk_begin(c), b1 = chunk_end(in0.size(), c);
         Res8WArgs wa{};
         Res8WBArgs ba{};
         double flops = 0, bytes = 0, wshare = 0;
@@ -955,8 +900,8 @@ void run_res8w(asep_aru* m, bool up, const TL& in0, const TL* dec, const std::ve
 
 void run_res8b(asep_aru* m, bool up, const TL& a0, const TL* a1, const std::vector<const float*>& stats, bool want_pool, TL* d_out, TL* pool_out) {
     for (const Tensor& t : a0) {
-        d_out->push_back(new_tensor_bf(m, t.H, t.W, 8));
-        if (want_pool) pool_out->push_back(new_tensor_bf(m, cdiv(t.H, 2), cdiv(t.W, 2), 8));
+        d_out->push_back(new_tensor(m, t.H, t.W, 8, true));
+        if (want_pool) pool_out->push_back(new_tensor(m, cdiv(t.H, 2), cdiv(t.W, 2), 8, true));
     }
     if (!m->fused_act && m->use_walk && (up || m->walk_mode == 1) && (up ? m->d_r8f_up_w1 != nullptr : m->d_r8f_down_w1 != nullptr)) {
         // pages with room for at least four strips and two tile rows of walker region go to the strip walker, the others stay on the tile kernels
@@ -982,62 +927,36 @@ void run_res8b(asep_aru* m, bool up, const TL& a0, const TL* a1, const std::vect
 
 // the tile kernels (res8f_kernel for interior tiles + res8b_tile for border tiles in one launch) on the given output tensors
 void run_res8b_tiles(asep_aru* m, bool up, const TL& a0, const TL* a1, const std::vector<const float*>& stats, bool want_pool, const TL& outs, const TL* pool_out) {
-    for (size_t b0 = 0; b0 < a0.size(); b0 += MAXP) {
-        const size_t b1 = std::min(a0.size(), b0 + MAXP);
-        Res8BArgs a{};
-        int tiles = 0;
-        double flops = 0, bytes = 0;
-        for (size_t i = b0; i < b1; ++i) {
-            bytes += tbytes(a0[i]) + (up ? tbytes((*a1)[i]) : 0.0) + tbytes(outs[i]) + (want_pool ? tbytes((*pool_out)[i]) : 0.0);
-            Res8BProb& p = a.p[i - b0];
-            if (up) { p.skip = a0[i].bp(); p.dec = (*a1)[i].bp(); }
-            else { p.img = a0[i].p; p.stats = stats.empty() ? nullptr : stats[i]; }
-            p.out = outs[i].bp(); p.pool = want_pool ? (*pool_out)[i].bp() : nullptr;
-            p.H = a0[i].H; p.W = a0[i].W;
-            p.tiles_x = cdiv(a0[i].W, 32);
-            p.tile_begin = tiles;
-            tiles += p.tiles_x * cdiv(a0[i].H, 16);
-            flops += 2.0 * a0[i].H * a0[i].W * (9.0 * (up ? 16 : 1) * 8 + 3 * 9.0 * 64);
-        }
-        a.nprob = (int)(b1 - b0);
+    struct K { void (*fn)(const Res8BArgs); const char* name; };
+    static const K general[2][3] = {{{res8b_kernel<false>, "res8b_kernel<false,0>"}, {res8b_kernel<false, 1>, "res8b_kernel<false,1>"}, {res8b_kernel<false, 2>, "res8b_kernel<false,2>"}},
+                                    {{res8b_kernel<true>, "res8b_kernel<true,0>"}, {res8b_kernel<true, 1>, "res8b_kernel<true,1>"}, {res8b_kernel<true, 2>, "res8b_kernel<true,2>"}}};
+    static const K lean[2] = {{res8f_kernel<false>, "res8f_kernel<false>"}, {res8f_kernel<true>, "res8f_kernel<true>"}};
+    for_chunks<Res8BArgs>(a0.size(), 0.0, [&](Res8BProb& p, size_t i, Chunk& k) {
+        k.bytes += tbytes(a0[i]) + (up ? tbytes((*a1)[i]) : 0.0) + tbytes(outs[i]) + (want_pool ? tbytes((*pool_out)[i]) : 0.0);
+        if (up) { p.skip = a0[i].bp(); p.dec = (*a1)[i].bp(); }
+        else { p.img = a0[i].p; p.stats = stats.empty() ? nullptr : stats[i]; }
+        p.out = outs[i].bp(); p.pool = want_pool ? (*pool_out)[i].bp() : nullptr;
+        p.H = a0[i].H; p.W = a0[i].W;
+        set_tiles(p, k.units.next_tiles(p.H, p.W, 32, 16));
+        k.flops += 2.0 * a0[i].H * a0[i].W * (9.0 * (up ? 16 : 1) * 8 + 3 * 9.0 * 64);
+    }, [&](Res8BArgs& a, const Chunk& k) {
         if (up) { a.w1pk = (const u32x4*)m->d_r8b_up_w1; a.b1 = m->d_r8b_up_b1; a.wpk = (const u32x4*)m->d_r8b_up_w; a.bias = m->d_r8b_up_b; }
         else { a.w1 = m->d_r8b_down_w1r ? m->d_r8b_down_w1r : m->det_first.d_w; a.b1 = m->det_first.d_b; a.wpk = (const u32x4*)m->d_r8b_down_w; a.bias = m->d_r8b_down_b; }
-        TL sub(a0.begin() + b0, a0.begin() + b1);
-        int units = tiles;
-        a.xm = oneshot_map(m, tiles, &units);
-        const std::string what = res8_what(up, sub);
+        const TL sub = k.sub(a0);
+        int units;
+        a.xm = oneshot_map(m, k.units.total, &units);
         bool small = true;                                   // res8f_kernel addresses its tensors with 32-bit byte offsets (16 bytes per pixel)
-        for (size_t i = b0; i < b1; ++i) small = small && (size_t)a0[i].H * a0[i].W < ((size_t)1 << 28);
-        if (m->fused_act) {                                  // elu / leaky: the general form for every tile
-            ProfScope ps(m, std::string("res8b_kernel") + targs({tb(up), ti(m->fused_act)}), flops, what);
-            ps.bytes = bytes;
-            if (up && m->fused_act == 1) hipLaunchKernelGGL((res8b_kernel<true, 1>), dim3(units), dim3(256), 0, m->stream, a);
-            else if (up) hipLaunchKernelGGL((res8b_kernel<true, 2>), dim3(units), dim3(256), 0, m->stream, a);
-            else if (m->fused_act == 1) hipLaunchKernelGGL((res8b_kernel<false, 1>), dim3(units), dim3(256), 0, m->stream, a);
-            else hipLaunchKernelGGL((res8b_kernel<false, 2>), dim3(units), dim3(256), 0, m->stream, a);
-        } else if (small && (up || m->d_r8f_down_w1)) {
-            // lean form for interior tiles (their 24 x 40 input window inside the image), general form for border tiles, one launch
-            Res8BArgs f = a;
-            if (!up) f.w1pk = (const u32x4*)m->d_r8f_down_w1;
-            else f.w1pf = (const u32x4*)m->d_r8f_up_w1;
-            ProfScope ps(m, up ? "res8f_kernel<true>" : "res8f_kernel<false>", flops, what);
-            ps.bytes = bytes;
-            if (up) hipLaunchKernelGGL(res8f_kernel<true>, dim3(units), dim3(256), 0, m->stream, f);
-            else hipLaunchKernelGGL(res8f_kernel<false>, dim3(units), dim3(256), 0, m->stream, f);
-        } else {
-            ProfScope ps(m, up ? "res8b_kernel<true,0>" : "res8b_kernel<false,0>", flops, what);
-            ps.bytes = bytes;
-            if (up) hipLaunchKernelGGL(res8b_kernel<true>, dim3(units), dim3(256), 0, m->stream, a);
-            else hipLaunchKernelGGL(res8b_kernel<false>, dim3(units), dim3(256), 0, m->stream, a);
-        }
-    }
-}
-
-Tensor new_tensor_bf(asep_aru* m, int H, int W, int C) {
-    Tensor t;
-    t.H = H; t.W = W; t.C = C; t.bf = true;
-    t.p = (float*)m->cur->pool.get(t.count() * sizeof(bf16_t));
-    return t;
+        for (const Tensor& t : sub) small = small && (size_t)t.H * t.W < ((size_t)1 << 28);
+        // elu / leaky: the general form for every tile; else the lean form for interior tiles (their 24 x 40 input window inside the image) and
+        // the general form for border tiles in one launch; else the general form
+        const bool f = !m->fused_act && small && (up || m->d_r8f_down_w1);
+        if (f && !up) a.w1pk = (const u32x4*)m->d_r8f_down_w1;
+        if (f && up) a.w1pf = (const u32x4*)m->d_r8f_up_w1;
+        const K& kn = f ? lean[up] : general[up][m->fused_act];
+        ProfScope ps(m, kn.name, k.flops, res8_what(up, sub));
+        ps.bytes = k.bytes;
+        hipLaunchKernelGGL(kn.fn, dim3(units), dim3(256), 0, m->stream, a);
+    });
 }
 
 #define ASEP_CONVB_LAUNCH(KH_, KW_, MODE_, MT_, WM_, TH_, MB_)                                                         \
@@ -1059,61 +978,40 @@ Tensor new_tensor_bf(asep_aru* m, int H, int W, int C) {
 // maxpool2 of a ReLU layer's bf16 output (behind convr_kernel's RES form)
 TL run_maxpool2b(asep_aru* m, const TL& in) {
     TL out;
-    for (const Tensor& t : in) out.push_back(new_tensor_bf(m, cdiv(t.H, 2), cdiv(t.W, 2), t.C));
-    for (size_t b0 = 0; b0 < in.size(); b0 += MAXP) {
-        const size_t b1 = std::min(in.size(), b0 + MAXP);
-        MaxPoolBArgs a{};
-        int blocks = 0;
-        double bytes = 0;
-        for (size_t i = b0; i < b1; ++i) {
-            bytes += tbytes(in[i]) + tbytes(out[i]);
-            MaxPoolBProb& p = a.p[i - b0];
-            p.in = in[i].bp(); p.out = out[i].bp(); p.H = in[i].H; p.W = in[i].W;
-            p.blk_begin = blocks;
-            blocks += (int)((out[i].count() / 8 + 255) / 256);
-        }
-        a.nprob = (int)(b1 - b0); a.C = in[0].C;
-        ProfScope ps(m, "maxpool2b_kernel", 0.0);
-        ps.bytes = bytes;
-        hipLaunchKernelGGL(maxpool2b_kernel, dim3(blocks), dim3(256), 0, m->stream, a);
-    }
+    for (const Tensor& t : in) out.push_back(new_tensor(m, cdiv(t.H, 2), cdiv(t.W, 2), t.C, true));
+    stream_pass<MaxPoolBArgs>(m, in, "maxpool2b_kernel", 256, [&](MaxPoolBProb& p, size_t i, Chunk& k) {
+        k.bytes += tbytes(in[i]) + tbytes(out[i]);
+        p.in = in[i].bp(); p.out = out[i].bp(); p.H = in[i].H; p.W = in[i].W;
+        return out[i].count() / 8;
+    }, [&](const MaxPoolBArgs& a, dim3 grid) { hipLaunchKernelGGL(maxpool2b_kernel, grid, dim3(256), 0, m->stream, a); });
     return out;
 }
 
 // the 64 -> 64 3x3 layers with the filter in registers (convr_kernels.h): one wave per SIMD, a wave = the pipeline of a 32-column strip
 TL run_convr(asep_aru* m, const std::string& scope, const PackedConv& pc, const TL& in0, bool relu_in, bool relu_out, const TL* res) {
     TL out;
-    for (const Tensor& t : in0) out.push_back(new_tensor_bf(m, t.H, t.W, 64));
-    for (size_t b0 = 0; b0 < in0.size(); b0 += MAXP) {
-        const size_t b1 = std::min(in0.size(), b0 + MAXP);
-        ConvRArgs a{};
-        int total = 0;
-        const int cin = in0[0].C;
-        double flops = 0, bytes = 9.0 * cin * 64 * 2.0;
-        for (size_t i = b0; i < b1; ++i) {
-            bytes += tbytes(in0[i]) + tbytes(out[i]) + (res ? tbytes((*res)[i]) : 0.0);
-            ConvRProb& p = a.p[i - b0];
-            p.in = in0[i].bp(); p.res = res ? (*res)[i].bp() : nullptr; p.out = out[i].bp();
-            p.H = in0[i].H; p.W = in0[i].W; p.strips = cdiv(in0[i].W, 32); p.begin = total;
-            total += p.strips * p.H;
-            flops += 2.0 * in0[i].H * in0[i].W * 9.0 * cin * 64.0;
-        }
-        a.nprob = (int)(b1 - b0); a.total = total;
+    for (const Tensor& t : in0) out.push_back(new_tensor(m, t.H, t.W, 64, true));
+    // the instantiations by (relu_in, relu_out) of the 64-channel form without residual
+    struct K { void (*fn)(const ConvRArgs); };
+    static const K plain[2][2] = {{{convr_kernel<false, false>}, {convr_kernel<false, true>}}, {{convr_kernel<true, false>}, {convr_kernel<true, true>}}};
+    const int cin = in0[0].C;
+    for_chunks<ConvRArgs>(in0.size(), 9.0 * cin * 64 * 2.0, [&](ConvRProb& p, size_t i, Chunk& k) {
+        k.bytes += tbytes(in0[i]) + tbytes(out[i]) + (res ? tbytes((*res)[i]) : 0.0);
+        p.in = in0[i].bp(); p.res = res ? (*res)[i].bp() : nullptr; p.out = out[i].bp();
+        p.H = in0[i].H; p.W = in0[i].W;
+        const Units u = k.units.next_strips(p.H, p.W, 32);
+        p.strips = u.per_row; p.begin = u.begin;
+        k.flops += 2.0 * in0[i].H * in0[i].W * 9.0 * cin * 64.0;
+    }, [&](ConvRArgs& a, const Chunk& k) {
         a.wpk = (const u32x4*)pc.d_wb; a.bias = pc.d_b;
         a.zero = m->d_zero_trash;
         // one wave per SIMD; a wave's range = total / waves rows (never fewer than 8: a range starts with three rows of latency)
-        const int blocks = std::max(1, std::min(m->num_cus, total / 32));
-        TL sub(in0.begin() + b0, in0.begin() + b1);
-        ProfScope ps(m, "convr_kernel", flops, scope + " " + dims_of(sub) + " " + std::to_string(cin) + "->64");
-        ps.bytes = bytes;
-        ps.set_name("convr_kernel" + targs({tb(relu_in), tb(relu_out), tb(res != nullptr), ti(cin)}));
-        if (cin == 32) hipLaunchKernelGGL((convr_kernel<false, false, false, 32>), dim3(blocks), dim3(256), 0, m->stream, a);
-        else if (res) hipLaunchKernelGGL((convr_kernel<false, true, true>), dim3(blocks), dim3(256), 0, m->stream, a);
-        else if (relu_in && relu_out) hipLaunchKernelGGL((convr_kernel<true, true>), dim3(blocks), dim3(256), 0, m->stream, a);
-        else if (relu_in) hipLaunchKernelGGL((convr_kernel<true, false>), dim3(blocks), dim3(256), 0, m->stream, a);
-        else if (relu_out) hipLaunchKernelGGL((convr_kernel<false, true>), dim3(blocks), dim3(256), 0, m->stream, a);
-        else hipLaunchKernelGGL((convr_kernel<false, false>), dim3(blocks), dim3(256), 0, m->stream, a);
-    }
+        const int blocks = std::max(1, std::min(m->num_cus, k.units.total / 32));
+        ProfScope ps(m, "convr_kernel" + targs({tb(relu_in), tb(relu_out), tb(res != nullptr), ti(cin)}), k.flops, layer_text(scope, k.sub(in0), cin, 64));
+        ps.bytes = k.bytes;
+        void (*fn)(const ConvRArgs) = cin == 32 ? convr_kernel<false, false, false, 32> : res ? convr_kernel<false, true, true> : plain[relu_in][relu_out].fn;
+        hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), 0, m->stream, a);
+    });
     return out;
 }
 
@@ -1151,45 +1049,34 @@ TL run_convb(asep_aru* m, const std::string& scope, const TL& in0, const TL* in1
     const int th = (mtb == 4 || (mtb == 2 && pc.bmode == 2)) ? 8 : 16;
     TL out;
     if (keep_full || !pooled)
-        for (const Tensor& t : in0) out.push_back(new_tensor_bf(m, t.H, t.W, pc.cout));
+        for (const Tensor& t : in0) out.push_back(new_tensor(m, t.H, t.W, pc.cout, true));
     if (pooled) {
         pooled->clear();
         for (const Tensor& t : in0) {
-            Tensor q = pool_f32 ? new_tensor(m, cdiv(t.H, 2), cdiv(t.W, 2), pc.cout) : new_tensor_bf(m, cdiv(t.H, 2), cdiv(t.W, 2), pc.cout);
-            pooled->push_back(q);
+            pooled->push_back(new_tensor(m, cdiv(t.H, 2), cdiv(t.W, 2), pc.cout, !pool_f32));
         }
     }
-    for (size_t b0 = 0; b0 < in0.size(); b0 += MAXP) {
-        const size_t b1 = std::min(in0.size(), b0 + MAXP);
-        ConvBArgs a{};
-        int tiles = 0;
-        double flops = 0, bytes = (double)pc.kh * pc.kw * pc.cin * pc.cout * 2.0;
-        for (size_t i = b0; i < b1; ++i) {
-            bytes += tbytes(in0[i]) + (in1 ? tbytes((*in1)[i]) : 0.0) + (res ? tbytes((*res)[i]) : 0.0) + (out.empty() ? 0.0 : tbytes(out[i])) +
-                     (pooled ? tbytes((*pooled)[i]) : 0.0);
-            ConvBProb& p = a.p[i - b0];
-            p.in0 = in0[i].bp(); p.in1 = in1 ? (*in1)[i].bp() : nullptr; p.res = res ? (*res)[i].bp() : nullptr;
-            p.out = out.empty() ? nullptr : out[i].bp();
-            p.pool = pooled ? (void*)(*pooled)[i].p : nullptr;
-            p.H = in0[i].H; p.W = in0[i].W;
-            p.tiles_x = cdiv(in0[i].W, 32);
-            p.tile_begin = tiles;
-            tiles += p.tiles_x * cdiv(in0[i].H, th);
-            flops += 2.0 * in0[i].H * in0[i].W * pc.kh * pc.kw * (double)pc.cin * pc.cout;
-        }
-        a.nprob = (int)(b1 - b0);
+    for_chunks<ConvBArgs>(in0.size(), conv_wbytes(pc, 2.0), [&](ConvBProb& p, size_t i, Chunk& k) {
+        k.bytes += tbytes(in0[i]) + (in1 ? tbytes((*in1)[i]) : 0.0) + (res ? tbytes((*res)[i]) : 0.0) + (out.empty() ? 0.0 : tbytes(out[i])) +
+                   (pooled ? tbytes((*pooled)[i]) : 0.0);
+        p.in0 = in0[i].bp(); p.in1 = in1 ? (*in1)[i].bp() : nullptr; p.res = res ? (*res)[i].bp() : nullptr;
+        p.out = out.empty() ? nullptr : out[i].bp();
+        p.pool = pooled ? (void*)(*pooled)[i].p : nullptr;
+        p.H = in0[i].H; p.W = in0[i].W;
+        set_tiles(p, k.units.next_tiles(p.H, p.W, 32, th));
+        k.flops += 2.0 * in0[i].H * in0[i].W * pc.kh * pc.kw * (double)pc.cin * pc.cout;
+    }, [&](ConvBArgs& a, const Chunk& k) {
         a.wpk = (const u32x4*)pc.d_wb; a.bias = pc.d_b;
         a.c0 = in0[0].C; a.c1 = in1 ? (*in1)[0].C : 0;
         a.cout = pc.cout; a.mtiles = pc.mtiles; a.groups = cin / 32;
         a.relu_in = relu_in; a.relu_out = relu_out; a.act = act; a.skip_full = pooled && !keep_full; a.pool_f32 = pool_f32;
-        int units = tiles;
-        a.xm = oneshot_map(m, tiles, &units);
+        int units;
+        a.xm = oneshot_map(m, k.units.total, &units);
         dim3 grid(units, pc.mtiles / mtb);
-        TL sub(in0.begin() + b0, in0.begin() + b1);
-        ProfScope ps(m, "convb_kernel", flops, scope + " " + dims_of(sub) + " " + std::to_string(pc.cin) + "->" + std::to_string(pc.cout));
-        ps.bytes = bytes;
+        ProfScope ps(m, "convb_kernel", k.flops, layer_text(scope, k.sub(in0), pc.cin, pc.cout));
+        ps.bytes = k.bytes;
         bool res32 = res != nullptr;                          // the RESP kernels address the residual operand with 32-bit byte offsets
-        for (size_t i = b0; res && i < b1; ++i) res32 = res32 && tbytes((*res)[i]) < 4294967296.0;
+        for (size_t i = k.b0; res && i < k.b1; ++i) res32 = res32 && tbytes((*res)[i]) < 4294967296.0;
         const int key = pc.kh * 100 + pc.bmode * 10 + mtb + (th == 8 && mtb == 2 ? 1000 : 0) + (res32 && pc.bmode == 2 && pc.kh == 3 && mtb >= 2 ? 2000 : 0);
         switch (key) {
             case 3322: ASEP_CONVB_LAUNCH_RES(3, 3, 2, 2, 1, 8, 3); break;       // residual operand in the initial value (32- and >= 64-channel convR_2)
@@ -1211,7 +1098,7 @@ TL run_convb(asep_aru* m, const std::string& scope, const TL& in0, const TL* in1
             case 424: ASEP_CONVB_LAUNCH(4, 4, 2, 2, 2, 8, 1); break;       // (16 taps x 4 m-tiles of fragments: one block per CU is what its registers allow)
             default: set_error("conv %s: bf16 kernel variant %d not instantiated", scope.c_str(), key); throw ArgError();
         }
-    }
+    });
     return out;
 }
 
@@ -1222,73 +1109,50 @@ TL run_resb_tail(asep_aru* m, const std::string& scope, const TL& t, TL* pooled)
     const asep_aru::ResB& rb = m->resb.at(scope);
     if (t[0].C != rb.C || !t[0].bf) { set_error("internal: residual tail %s expects %d bf16 channels", scope.c_str(), rb.C); throw ArgError(); }
     TL out;
-    for (const Tensor& x : t) out.push_back(new_tensor_bf(m, x.H, x.W, rb.C));
+    for (const Tensor& x : t) out.push_back(new_tensor(m, x.H, x.W, rb.C, true));
     if (pooled) {
         pooled->clear();
-        for (const Tensor& x : t) pooled->push_back(new_tensor_bf(m, cdiv(x.H, 2), cdiv(x.W, 2), rb.C));
+        for (const Tensor& x : t) pooled->push_back(new_tensor(m, cdiv(x.H, 2), cdiv(x.W, 2), rb.C, true));
     }
-    for (size_t b0 = 0; b0 < t.size(); b0 += MAXP) {
-        const size_t b1 = std::min(t.size(), b0 + MAXP);
-        ResBArgs a{};
-        int tiles = 0;
-        double flops = 0, bytes = 3.0 * 9.0 * rb.C * rb.C * 2.0;
-        for (size_t i = b0; i < b1; ++i) {
-            bytes += tbytes(t[i]) + tbytes(out[i]) + (pooled ? tbytes((*pooled)[i]) : 0.0);
-            ResBProb& p = a.p[i - b0];
-            p.t = t[i].bp(); p.out = out[i].bp(); p.pool = pooled ? (*pooled)[i].bp() : nullptr;
-            p.H = t[i].H; p.W = t[i].W;
-            p.tiles_x = cdiv(t[i].W, RB_TW);
-            p.tile_begin = tiles;
-            tiles += p.tiles_x * cdiv(t[i].H, RB_TH);
-            flops += 2.0 * t[i].H * t[i].W * 3 * 9.0 * rb.C * rb.C;
-        }
-        a.nprob = (int)(b1 - b0);
+    struct K { void (*fn)(const ResBArgs); };
+    static const K tail32[3] = {{res32_tail_kernel<0>}, {res32_tail_kernel<1>}, {res32_tail_kernel<2>}};
+    static const K general[2][3] = {{{resb_tail_kernel<8>}, {resb_tail_kernel<8, 1>}, {resb_tail_kernel<8, 2>}}, {{resb_tail_kernel<16>}, {resb_tail_kernel<16, 1>}, {resb_tail_kernel<16, 2>}}};
+    for_chunks<ResBArgs>(t.size(), 3.0 * 9.0 * rb.C * rb.C * 2.0, [&](ResBProb& p, size_t i, Chunk& k) {
+        k.bytes += tbytes(t[i]) + tbytes(out[i]) + (pooled ? tbytes((*pooled)[i]) : 0.0);
+        p.t = t[i].bp(); p.out = out[i].bp(); p.pool = pooled ? (*pooled)[i].bp() : nullptr;
+        p.H = t[i].H; p.W = t[i].W;
+        set_tiles(p, k.units.next_tiles(p.H, p.W, RB_TW, RB_TH));
+        k.flops += 2.0 * t[i].H * t[i].W * 3 * 9.0 * rb.C * rb.C;
+    }, [&](ResBArgs& a, const Chunk& k) {
         a.wpk = (const u32x4*)rb.d_w; a.bias = rb.d_b;
-        int units = tiles;
+        const int tiles = k.units.total, act = m->fused_act;
+        const TL sub = k.sub(t);
+        const std::string what = scope + " (3xconvR+add" + (pooled ? "+pool) " : ") ") + dims_of(sub);
         if (rb.C == 32) {                                    // persistent kernel: table (its units are walked with a grid stride)
             std::vector<TileDims> probs;
             for (int i = 0; i < a.nprob; ++i) probs.push_back({a.p[i].tiles_x, cdiv(a.p[i].H, RB_TH), a.p[i].tile_begin});
             a.sched = (m->use_xcd_sched && tiles >= 8 * 64) ? xcd_schedule(m, probs, tiles) : nullptr;
-        } else {
-            a.xm = oneshot_map(m, tiles, &units);
-        }
-        TL sub(t.begin() + b0, t.begin() + b1);
-        bool small16 = true;                                 // res16f_kernel addresses its tensors with 32-bit byte offsets (32 bytes per pixel)
-        for (const Tensor& x : sub) small16 = small16 && (size_t)x.H * x.W < ((size_t)1 << 27);
-        const std::string what = scope + " (3xconvR+add" + (pooled ? "+pool) " : ") ") + dims_of(sub);
-        if (rb.C == 32) {
             static bool attr[3] = {false, false, false};
-            const int act = m->fused_act;
-            const void* fn = act == 1 ? (const void*)res32_tail_kernel<1> : act == 2 ? (const void*)res32_tail_kernel<2> : (const void*)res32_tail_kernel<0>;
             if (!attr[act]) {
-                ASEP_HIP_CHECK_THROW(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, Res32Layout::BYTES));
+                ASEP_HIP_CHECK_THROW(hipFuncSetAttribute((const void*)tail32[act].fn, hipFuncAttributeMaxDynamicSharedMemorySize, Res32Layout::BYTES));
                 attr[act] = true;
             }
-            ProfScope ps(m, "res32_tail_kernel" + targs({ti(act)}), flops, what);
-            ps.bytes = bytes;
+            ProfScope ps(m, "res32_tail_kernel" + targs({ti(act)}), k.flops, what);
+            ps.bytes = k.bytes;
             a.ntiles = tiles;
-            const dim3 g32(std::min(tiles, m->num_cus));
-            if (act == 1) hipLaunchKernelGGL(res32_tail_kernel<1>, g32, dim3(512), Res32Layout::BYTES, m->stream, a);
-            else if (act == 2) hipLaunchKernelGGL(res32_tail_kernel<2>, g32, dim3(512), Res32Layout::BYTES, m->stream, a);
-            else hipLaunchKernelGGL(res32_tail_kernel<0>, g32, dim3(512), Res32Layout::BYTES, m->stream, a);
-        } else if (m->fused_act) {                     // elu / leaky: the general form
-            ProfScope ps(m, "resb_tail_kernel" + targs({ti(rb.C), ti(m->fused_act)}), flops, what);
-            ps.bytes = bytes;
-            if (rb.C == 8 && m->fused_act == 1) hipLaunchKernelGGL((resb_tail_kernel<8, 1>), dim3(units), dim3(256), 0, m->stream, a);
-            else if (rb.C == 8) hipLaunchKernelGGL((resb_tail_kernel<8, 2>), dim3(units), dim3(256), 0, m->stream, a);
-            else if (m->fused_act == 1) hipLaunchKernelGGL((resb_tail_kernel<16, 1>), dim3(units), dim3(256), 0, m->stream, a);
-            else hipLaunchKernelGGL((resb_tail_kernel<16, 2>), dim3(units), dim3(256), 0, m->stream, a);
-        } else if (rb.C == 16 && small16) {            // lean form for interior tiles, general form for border tiles, one launch
-            ProfScope ps(m, "res16f_kernel", flops, what);
-            ps.bytes = bytes;
-            hipLaunchKernelGGL(res16f_kernel, dim3(units), dim3(256), 0, m->stream, a);
-        } else {
-            ProfScope ps(m, "resb_tail_kernel" + targs({ti(rb.C), ti(0)}), flops, what);
-            ps.bytes = bytes;
-            if (rb.C == 8) hipLaunchKernelGGL(resb_tail_kernel<8>, dim3(units), dim3(256), 0, m->stream, a);
-            else hipLaunchKernelGGL(resb_tail_kernel<16>, dim3(units), dim3(256), 0, m->stream, a);
+            hipLaunchKernelGGL(tail32[act].fn, dim3(std::min(tiles, m->num_cus)), dim3(512), Res32Layout::BYTES, m->stream, a);
+            return;
         }
-    }
+        int units;
+        a.xm = oneshot_map(m, tiles, &units);
+        bool small16 = true;                                 // res16f_kernel addresses its tensors with 32-bit byte offsets (32 bytes per pixel)
+        for (const Tensor& x : sub) small16 = small16 && (size_t)x.H * x.W < ((size_t)1 << 27);
+        // elu / leaky: the general form; 16 channels: the lean form for interior tiles, the general form for border tiles, one launch
+        const bool f16 = !act && rb.C == 16 && small16;
+        ProfScope ps(m, f16 ? std::string("res16f_kernel") : "resb_tail_kernel" + targs({ti(rb.C), ti(act)}), k.flops, what);
+        ps.bytes = k.bytes;
+        hipLaunchKernelGGL(f16 ? res16f_kernel : general[rb.C == 16][act].fn, dim3(units), dim3(256), 0, m->stream, a);
+    });
     return out;
 }
 
@@ -1308,103 +1172,43 @@ TL run_deconvb(asep_aru* m, const std::string& scope, const TL& in, const TL& li
             set_error("deconv %s: output %dx%d incompatible with input %dx%d", scope.c_str(), like[i].H, like[i].W, in[i].H, in[i].W);
             throw ArgError();
         }
-        out.push_back(new_tensor_bf(m, like[i].H, like[i].W, pc.cout));
+        out.push_back(new_tensor(m, like[i].H, like[i].W, pc.cout, true));
     }
     const int mt = pc.mtiles % 2 == 0 ? 2 : 1;
     const bool d8 = pc.d_wb8 && relu_out && !act;           // level 0 (16 -> 8): no LDS, whole pixels straight to HBM
     const int dth = d8 ? D8_RW : 8;                          // input rows per block (16 rows for one m-tile measured slower: 148 -> 187 us at level 0)
     const int dtw = d8 ? D8_TW : DCB_TW;
-    for (size_t b0 = 0; b0 < in.size(); b0 += MAXP) {
-        const size_t b1 = std::min(in.size(), b0 + MAXP);
-        DeconvBArgs a{};
-        int tiles = 0;
-        double flops = 0, bytes = 9.0 * pc.cin * pc.cout * 2.0;
-        for (size_t i = b0; i < b1; ++i) {
-            bytes += tbytes(in[i]) + tbytes(out[i]);
-            DeconvBProb& p = a.p[i - b0];
-            p.in = in[i].bp(); p.out = out[i].bp();
-            p.Hi = in[i].H; p.Wi = in[i].W; p.Ho = out[i].H; p.Wo = out[i].W;
-            p.pbh = std::max((in[i].H - 1) * 2 + 3 - out[i].H, 0) / 2;
-            p.pbw = std::max((in[i].W - 1) * 2 + 3 - out[i].W, 0) / 2;
-            p.tiles_x = cdiv(in[i].W, dtw);
-            p.tile_begin = tiles;
-            tiles += p.tiles_x * cdiv(in[i].H, dth);
-            flops += 2.0 * in[i].H * in[i].W * 9.0 * pc.cin * pc.cout;
-        }
-        a.nprob = (int)(b1 - b0);
+    void (*const fn)(const DeconvBArgs) = d8 ? deconvb8_kernel : pc.bmode == 1 ? (mt == 1 ? deconvb_kernel<1, 1, 8> : deconvb_kernel<1, 2, 8>)
+                                                                               : (mt == 1 ? deconvb_kernel<2, 1, 8> : deconvb_kernel<2, 2, 8>);
+    for_chunks<DeconvBArgs>(in.size(), 9.0 * pc.cin * pc.cout * 2.0, [&](DeconvBProb& p, size_t i, Chunk& k) {
+        k.bytes += tbytes(in[i]) + tbytes(out[i]);
+        p.in = in[i].bp(); p.out = out[i].bp();
+        p.Hi = in[i].H; p.Wi = in[i].W; p.Ho = out[i].H; p.Wo = out[i].W;
+        p.pbh = std::max((in[i].H - 1) * 2 + 3 - out[i].H, 0) / 2;
+        p.pbw = std::max((in[i].W - 1) * 2 + 3 - out[i].W, 0) / 2;
+        set_tiles(p, k.units.next_tiles(p.Hi, p.Wi, dtw, dth));
+        k.flops += 2.0 * in[i].H * in[i].W * 9.0 * pc.cin * pc.cout;
+    }, [&](DeconvBArgs& a, const Chunk& k) {
         a.wpk = (const u32x4*)(d8 ? pc.d_wb8 : pc.d_wb); a.bias = pc.d_b;
         a.cin = pc.cin; a.cout = pc.cout; a.mtiles = pc.mtiles; a.groups = pc.cin / 32; a.relu_out = relu_out; a.act = act;
-        int units = tiles;
-        a.xm = oneshot_map(m, tiles, &units);
-        dim3 grid(units, pc.mtiles / mt);
-        TL sub(in.begin() + b0, in.begin() + b1);
-        ProfScope ps(m, d8 ? std::string("deconvb8_kernel") : "deconvb_kernel" + targs({ti(pc.bmode), ti(mt), ti(dth)}), flops,
-                     scope + " " + dims_of(sub) + " " + std::to_string(pc.cin) + "->" + std::to_string(pc.cout));
-        ps.bytes = bytes;
-        if (d8) hipLaunchKernelGGL(deconvb8_kernel, dim3(units), dim3(256), 0, m->stream, a);
-        else if (pc.bmode == 1 && mt == 1) hipLaunchKernelGGL((deconvb_kernel<1, 1, 8>), grid, dim3(256), 0, m->stream, a);
-        else if (pc.bmode == 1) hipLaunchKernelGGL((deconvb_kernel<1, 2, 8>), grid, dim3(256), 0, m->stream, a);
-        else if (mt == 1) hipLaunchKernelGGL((deconvb_kernel<2, 1, 8>), grid, dim3(256), 0, m->stream, a);
-        else hipLaunchKernelGGL((deconvb_kernel<2, 2, 8>), grid, dim3(256), 0, m->stream, a);
-    }
-    return out;
-}
-
-// first layer of the feature CNN on the bf16 path: fp32 image -> bf16 [H,W,8] (pre-ReLU t of unet_down_0)
-TL run_direct_bf(asep_aru* m, const DirectConv& dc, const TL& imgs, const std::vector<const float*>& stats, bool activated = false) {
-    const bool rgb = dc.cin == 3;                            // colour net: conv_c3_kernel
-    if (dc.k != 3 || dc.cout != 8 || (dc.cin != 1 && !rgb)) {    // (the bf16 engine is a feat_root 8 engine: combine_kernel)
-        set_error("bf16 path: first-layer conv k=%d cin=%d cout=%d not instantiated", dc.k, dc.cin, dc.cout);
-        throw ArgError();
-    }
-    TL out;
-    for (const Tensor& t : imgs) out.push_back(new_tensor_bf(m, t.H, t.W, dc.cout));
-    for (size_t b0 = 0; b0 < imgs.size(); b0 += MAXP) {
-        const size_t b1 = std::min(imgs.size(), b0 + MAXP);
-        C1Args a{};
-        int tiles = 0;
-        double flops = 0, bytes = 0;
-        for (size_t i = b0; i < b1; ++i) {
-            bytes += tbytes(imgs[i]) + tbytes(out[i]);
-            C1Prob& p = a.p[i - b0];
-            p.img = imgs[i].p; p.out = out[i].p; p.stats = stats.empty() ? nullptr : stats[i];
-            p.H = imgs[i].H; p.W = imgs[i].W;
-            p.tiles_x = cdiv(imgs[i].W, 64);
-            p.tile_begin = tiles;
-            tiles += p.tiles_x * cdiv(imgs[i].H, 4);
-            flops += 2.0 * imgs[i].H * imgs[i].W * dc.k * dc.k * dc.cin * dc.cout;
-        }
-        a.nprob = (int)(b1 - b0);
-        a.w = dc.d_w; a.bias = dc.d_b; a.relu = (activated && m->cfg.activation == 0) ? 1 : 0; a.act = activated ? m->cfg.activation : 0;
-        ProfScope ps(m, rgb ? "conv_c3_kernel<8,true>" : "conv_c1_kernel<3,8,true>", flops);
-        ps.bytes = bytes;
-        if (rgb) launch_conv_c3(m, a, 8, true, tiles);
-        else hipLaunchKernelGGL((conv_c1_kernel<3, 8, true>), dim3(tiles), dim3(256), 0, m->stream, a);
-    }
+        int units;
+        a.xm = oneshot_map(m, k.units.total, &units);
+        ProfScope ps(m, d8 ? std::string("deconvb8_kernel") : "deconvb_kernel" + targs({ti(pc.bmode), ti(mt), ti(dth)}), k.flops,
+                     layer_text(scope, k.sub(in), pc.cin, pc.cout));
+        ps.bytes = k.bytes;
+        hipLaunchKernelGGL(fn, d8 ? dim3(units) : dim3(units, pc.mtiles / mt), dim3(256), 0, m->stream, a);
+    });
     return out;
 }
 
 TL run_chansum_bf(asep_aru* m, const TL& in) {
     TL out;
     for (const Tensor& t : in) out.push_back(new_tensor(m, t.H, t.W, 1));
-    for (size_t b0 = 0; b0 < in.size(); b0 += MAXP) {
-        const size_t b1 = std::min(in.size(), b0 + MAXP);
-        PoolBArgs a{};
-        int blocks = 0;
-        double bytes = 0;
-        for (size_t i = b0; i < b1; ++i) {
-            bytes += tbytes(in[i]) + tbytes(out[i]);
-            PoolBProb& p = a.p[i - b0];
-            p.in = in[i].bp(); p.out = out[i].p; p.H = in[i].H; p.W = in[i].W;
-            p.blk_begin = blocks;
-            blocks += (int)(((size_t)in[i].H * in[i].W + POOL_ITEMS - 1) / POOL_ITEMS);
-        }
-        a.nprob = (int)(b1 - b0);
-        a.C = in[0].C;
-        ProfScope ps(m, "chansumb_kernel", 0.0);
-        ps.bytes = bytes;
-        hipLaunchKernelGGL(chansumb_kernel, dim3(blocks), dim3(256), 0, m->stream, a);
-    }
+    stream_pass<PoolBArgs>(m, in, "chansumb_kernel", POOL_ITEMS, [&](PoolBProb& p, size_t i, Chunk& k) {
+        k.bytes += tbytes(in[i]) + tbytes(out[i]);
+        p.in = in[i].bp(); p.out = out[i].p; p.H = in[i].H; p.W = in[i].W;
+        return (size_t)in[i].H * in[i].W;
+    }, [&](const PoolBArgs& a, dim3 grid) { hipLaunchKernelGGL(chansumb_kernel, grid, dim3(256), 0, m->stream, a); });
     return out;
 }
 
@@ -1413,25 +1217,11 @@ TL run_chansum_bf(asep_aru* m, const TL& in) {
 // ---- graph variants (asep_aru_cfg.activation != 0 and / or plain_u; fp32 path only): the layer kernels store pre-activation values,
 //      act_kernel follows (on the pooled tensor too: the activations are increasing, the fused 2x2 max commutes with them) ----
 void apply_act(asep_aru* m, TL& l) {
-    if (l.empty()) return;
-    for (size_t b0 = 0; b0 < l.size(); b0 += MAXP) {
-        const size_t b1 = std::min(l.size(), b0 + MAXP);
-        PoolArgs a{};
-        int blocks = 0;
-        double bytes = 0;
-        for (size_t i = b0; i < b1; ++i) {
-            bytes += 2.0 * tbytes(l[i]);
-            PoolProb& p = a.p[i - b0];
-            p.in = l[i].p; p.out = l[i].p; p.H = p.Ho = l[i].H; p.W = p.Wo = l[i].W;
-            p.blk_begin = blocks;
-            blocks += (int)((l[i].count() + (size_t)POOL_ITEMS * 4 - 1) / ((size_t)POOL_ITEMS * 4));
-        }
-        a.nprob = (int)(b1 - b0);
-        a.C = l[0].C;
-        ProfScope ps(m, "act_kernel", 0.0);
-        ps.bytes = bytes;
-        hipLaunchKernelGGL(act_kernel, dim3(blocks), dim3(256), 0, m->stream, a, m->cfg.activation);
-    }
+    stream_pass<PoolArgs>(m, l, "act_kernel", (size_t)POOL_ITEMS * 4, [&](PoolProb& p, size_t i, Chunk& k) {
+        k.bytes += 2.0 * tbytes(l[i]);
+        p.in = l[i].p; p.out = l[i].p; p.H = p.Ho = l[i].H; p.W = p.Wo = l[i].W;
+        return l[i].count();
+    }, [&](const PoolArgs& a, dim3 grid) { hipLaunchKernelGGL(act_kernel, grid, dim3(256), 0, m->stream, a, m->cfg.activation); });
 }
 // conv / deconv / first conv followed by the graph's activation (act = false: identity layers).  Round 4: elu / leaky are applied in the
 // epilogue of the producing kernel (ConvArgs::act: the same arithmetic as act_kernel, so the results are bit-identical to the separate pass
@@ -1455,7 +1245,7 @@ TL deconv_act(asep_aru* m, const std::string& scope, const TL& in, const TL& lik
 }
 TL direct_act(asep_aru* m, const DirectConv& dc, const TL& imgs, bool act, const std::vector<const float*>& stats) {
     if (m->cfg.activation == 0 || !act) return run_direct(m, dc, imgs, act, stats);
-    if (m->fuse_act) return run_direct(m, dc, imgs, false, stats, m->cfg.activation);
+    if (m->fuse_act || m->bf16) return run_direct(m, dc, imgs, false, stats, m->cfg.activation);
     TL out = run_direct(m, dc, imgs, false, stats);
     apply_act(m, out);
     return out;
@@ -1486,80 +1276,49 @@ TL det_cnn(asep_aru* m, const TL& imgs, const std::vector<std::string>& names, c
     auto publish = [&](const TL& l, const std::string& suffix) {
         for (size_t i = 0; i < l.size(); ++i) m->endpoints[names[i] + suffix] = l[i];
     };
+    // the three layer ops of the schedule on the handle's engine; act: the graph's activation behind the layer (the wrappers carry the rules)
+    auto first = [&](bool act) { return direct_act(m, m->det_first, imgs, act, stats); };
+    auto conv = [&](const std::string& sc, const TL& in0, const TL* in1, bool act, TL* pooled = nullptr) {
+        return m->bf16 ? run_convb(m, sc, in0, in1, false, act, nullptr, pooled) : conv_act(m, sc, in0, in1, false, act, nullptr, pooled);
+    };
+    auto deconv = [&](const std::string& sc, const TL& in, const TL& like) {
+        return m->bf16 ? run_deconvb(m, sc, in, like, true) : deconv_act(m, sc, in, like);
+    };
     for (int l = 0; l < n; ++l) {
         const std::string scope = "aru_net/featMapG/unet_down_" + std::to_string(l);
-        if (m->bf16 && l == 0 && !rgb && m->d_r8b_down_w && m->det_first.k == 3 && m->det_first.cout == 8) {
-            TL d, pooled;                                    // the whole block in one kernel: image -> d0 (+ pool)
-            run_res8b(m, false, imgs, nullptr, stats, n > 1, &d, &pooled);
-            skips.push_back(d);
-            publish(d, "_unet_down_0_conv");
-            u = n > 1 ? pooled : d;
-            continue;
-        }
-        if (m->bf16 && m->cfg.plain_u) {                     // graph 'U' (ARU_v1.py:228-233): conv1 + conv2, both activated, layer by layer
-            TL c1 = (l == 0) ? run_direct_bf(m, m->det_first, imgs, stats, true) : run_convb(m, scope + "/conv1", u, nullptr, false, true, nullptr);
-            TL pooled;
-            TL d = run_convb(m, scope + "/conv2", c1, nullptr, false, true, nullptr, l < n - 1 ? &pooled : nullptr);
-            skips.push_back(d);
-            publish(d, "_unet_down_" + std::to_string(l) + "_conv");
-            u = (l < n - 1) ? pooled : d;
-            continue;
-        }
-        if (m->bf16) {
-            // native bf16 path: conv1 -> t (bf16), then the block tail (one kernel at 8 / 16 channels, three convs above)
-            TL t = (l == 0) ? run_direct_bf(m, m->det_first, imgs, stats) : run_convb(m, scope + "/conv1", u, nullptr, false, false, nullptr);
-            TL pooled;
-            TL d = res_block_tail(m, scope, t, l < n - 1 ? &pooled : nullptr);
-            skips.push_back(d);
-            publish(d, "_unet_down_" + std::to_string(l) + "_conv");
-            u = (l < n - 1) ? pooled : d;
-            continue;
-        }
-        if (l == 0 && !rgb && (m->use_fused8 || (m->fused8_var && r8v_fits(imgs))) && m->d_r8_down_wr) {
-            TL d, pooled;
-            run_res8(m, false, imgs, nullptr, stats, n > 1, &d, &pooled);
-            skips.push_back(d);
-            publish(d, "_unet_down_0_conv");
-            u = n > 1 ? pooled : d;
-            continue;
-        }
-        TL pooled, d;
-        if (m->cfg.plain_u) {                                // graph 'U': conv1 + conv2, both activated (ARU_v1.py:228-233)
-            TL c1 = (l == 0) ? direct_act(m, m->det_first, imgs, true, stats) : conv_act(m, scope + "/conv1", u, nullptr, false, true, nullptr);
-            d = conv_act(m, scope + "/conv2", c1, nullptr, false, true, nullptr, l < n - 1 ? &pooled : nullptr);
-        } else {
-            TL t = (l == 0) ? run_direct(m, m->det_first, imgs, false, stats)
-                            : run_conv(m, scope + "/conv1", u, nullptr, false, false, nullptr);
-            d = res_block_tail(m, scope, t, l < n - 1 ? &pooled : nullptr);    // the block's last conv also emits maxpool2(d)
+        const bool pool = l < n - 1;
+        TL d, pooled;
+        if (l == 0 && !rgb && (m->bf16 ? m->d_r8b_down_w && m->det_first.k == 3 && m->det_first.cout == 8
+                                       : (m->use_fused8 || (m->fused8_var && r8v_fits(imgs))) && m->d_r8_down_wr)) {
+            // the whole block in one kernel: image -> d0 (+ pool)
+            if (m->bf16) run_res8b(m, false, imgs, nullptr, stats, pool, &d, &pooled);
+            else run_res8(m, false, imgs, nullptr, stats, pool, &d, &pooled);
+        } else if (m->cfg.plain_u) {                         // graph 'U': conv1 + conv2, both activated (ARU_v1.py:228-233)
+            TL c1 = (l == 0) ? first(true) : conv(scope + "/conv1", u, nullptr, true);
+            d = conv(scope + "/conv2", c1, nullptr, true, pool ? &pooled : nullptr);
+        } else {                                             // conv1 -> t, then the block tail, whose last conv also emits maxpool2(d)
+            TL t = (l == 0) ? first(false) : conv(scope + "/conv1", u, nullptr, false);
+            d = res_block_tail(m, scope, t, pool ? &pooled : nullptr);
         }
         skips.push_back(d);
         publish(d, "_unet_down_" + std::to_string(l) + "_conv");
-        u = (l < n - 1) ? pooled : d;
+        u = pool ? pooled : d;
     }
     for (int l = n - 2; l >= 0; --l) {
         const std::string scope = "aru_net/featMapG/unet_up_" + std::to_string(l);
         const TL& skip = skips[l];
-        TL v = m->bf16 ? run_deconvb(m, scope + "/deconv", u, skip, true) : deconv_act(m, scope + "/deconv", u, skip);
+        TL v = deconv(scope + "/deconv", u, skip);
         publish(v, "_unet_up_" + std::to_string(l) + "_deconv");
-        if (m->bf16 && l == 0 && m->d_r8b_up_w1) {
+        if (l == 0 && (m->bf16 ? m->d_r8b_up_w1 != nullptr : (m->use_fused8 || (m->fused8_var && r8v_fits(skip))) && m->d_r8_up_w1)) {
             TL d, none;                                      // conv1 over [skip, deconv] + the tail in one kernel
-            run_res8b(m, true, skip, &v, {}, false, &d, &none);
-            u = d;
-        } else if (m->bf16 && m->cfg.plain_u) {              // ARU_v1.py:283-288
-            TL c1 = run_convb(m, scope + "/conv1", skip, &v, false, true, nullptr);
-            u = run_convb(m, scope + "/conv2", c1, nullptr, false, true, nullptr);
-        } else if (m->bf16) {
-            TL t = run_convb(m, scope + "/conv1", skip, &v, false, false, nullptr);   // concat [skip, deconv]
-            u = res_block_tail(m, scope, t);
-        } else if (l == 0 && (m->use_fused8 || (m->fused8_var && r8v_fits(skip))) && m->d_r8_up_w1) {
-            TL d, none;
-            run_res8(m, true, skip, &v, {}, false, &d, &none);
+            if (m->bf16) run_res8b(m, true, skip, &v, {}, false, &d, &none);
+            else run_res8(m, true, skip, &v, {}, false, &d, &none);
             u = d;
         } else if (m->cfg.plain_u) {                         // ARU_v1.py:283-288
-            TL c1 = conv_act(m, scope + "/conv1", skip, &v, false, true, nullptr);
-            u = conv_act(m, scope + "/conv2", c1, nullptr, false, true, nullptr);
+            TL c1 = conv(scope + "/conv1", skip, &v, true);
+            u = conv(scope + "/conv2", c1, nullptr, true);
         } else {
-            TL t = run_conv(m, scope + "/conv1", skip, &v, false, false, nullptr);   // concat [skip, deconv]
+            TL t = conv(scope + "/conv1", skip, &v, false);  // concat [skip, deconv]
             u = res_block_tail(m, scope, t);
         }
         publish(u, "_unet_up_" + std::to_string(l) + "_conv");
@@ -1577,62 +1336,42 @@ TL att_cnn(asep_aru* m, const TL& imgs, const std::vector<const float*>& stats) 
     if (m->d_att_head && (m->use_fused8 || head_variant || m->bf16)) {
         // conv1 + ReLU + pool1 fused (the full-resolution 12-channel tensor is never materialised)
         // (bf16 path: the head writes a 16-channel bf16 plane, channels 12..15 zero)
-        for (const Tensor& t : imgs) y.push_back(m->bf16 ? new_tensor_bf(m, cdiv(t.H, 2), cdiv(t.W, 2), 16) : new_tensor(m, cdiv(t.H, 2), cdiv(t.W, 2), 12));
+        for (const Tensor& t : imgs) y.push_back(new_tensor(m, cdiv(t.H, 2), cdiv(t.W, 2), m->bf16 ? 16 : 12, m->bf16));
         bool headb = m->bf16 && m->d_att_headb && m->cfg.activation == 0;
         // (att_headb_kernel addresses the pooled plane with 32-bit element offsets: images of 2^28 pixels and more take the vector-ALU head below,
         //  which refuses them with an error instead of wrapping)
         for (const Tensor& t : imgs) headb = headb && (size_t)t.H * t.W < ((size_t)1 << 28);
-        for (size_t b0 = 0; headb && b0 < imgs.size(); b0 += MAXP) {
-            // bf16 path, ReLU graph: the head on the bf16 MFMA (image and filter as bfloat16 like the feature CNN's first layer)
-            const size_t b1 = std::min(imgs.size(), b0 + MAXP);
-            AttHeadBArgs a{};
-            int tiles = 0;
-            double flops = 0, bytes = 0;
-            for (size_t i = b0; i < b1; ++i) {
-                bytes += tbytes(imgs[i]) + tbytes(y[i]);
-                C1Prob& q = a.p[i - b0];
+        auto fill = [&](int tw, int th) {                    // both heads: tw x th tiles of the page in, the pooled plane out
+            return [&, tw, th](C1Prob& q, size_t i, Chunk& k) {
+                k.bytes += tbytes(imgs[i]) + tbytes(y[i]);
                 q.img = imgs[i].p; q.out = y[i].p; q.stats = stats.empty() ? nullptr : stats[i];
                 q.H = imgs[i].H; q.W = imgs[i].W;
-                q.tiles_x = cdiv(imgs[i].W, ATTB_TW);
-                q.tile_begin = tiles;
-                tiles += q.tiles_x * cdiv(imgs[i].H, ATTB_TH);
-                flops += 2.0 * imgs[i].H * imgs[i].W * 16.0 * 12;
-            }
-            a.nprob = (int)(b1 - b0);
+                set_tiles(q, k.units.next_tiles(q.H, q.W, tw, th));
+                k.flops += 2.0 * imgs[i].H * imgs[i].W * 16.0 * 12;
+            };
+        };
+        // bf16 path, ReLU graph: the head on the bf16 MFMA (image and filter as bfloat16 like the feature CNN's first layer)
+        if (headb) for_chunks<AttHeadBArgs>(imgs.size(), 0.0, fill(ATTB_TW, ATTB_TH), [&](AttHeadBArgs& a, const Chunk& k) {
             a.wpk = (const u32x4*)m->d_att_headb; a.bias = m->att_first.d_b;
-            int units = tiles;
-            a.xm = oneshot_map(m, tiles, &units);
-            ProfScope ps(m, "att_headb_kernel", flops);
-            ps.bytes = bytes;
+            int units;
+            a.xm = oneshot_map(m, k.units.total, &units);
+            ProfScope ps(m, "att_headb_kernel", k.flops);
+            ps.bytes = k.bytes;
             hipLaunchKernelGGL(att_headb_kernel, dim3(units), dim3(256), 0, m->stream, a);
-        }
-        for (size_t b0 = 0; !headb && b0 < imgs.size(); b0 += MAXP) {
-            const size_t b1 = std::min(imgs.size(), b0 + MAXP);
-            AttHeadArgs a{};
-            int tiles = 0;
-            double flops = 0, bytes = 0;
-            for (size_t i = b0; i < b1; ++i) {
-                bytes += tbytes(imgs[i]) + tbytes(y[i]);
-                C1Prob& q = a.p[i - b0];
-                q.img = imgs[i].p; q.out = y[i].p; q.stats = stats.empty() ? nullptr : stats[i];
-                q.H = imgs[i].H; q.W = imgs[i].W;
-                q.tiles_x = cdiv(imgs[i].W, ATT_TW);
-                q.tile_begin = tiles;
-                tiles += q.tiles_x * cdiv(imgs[i].H, ATT_TH);
-                flops += 2.0 * imgs[i].H * imgs[i].W * 16.0 * 12;
-            }
-            a.nprob = (int)(b1 - b0);
+        });
+        else for_chunks<AttHeadArgs>(imgs.size(), 0.0, fill(ATT_TW, ATT_TH), [&](AttHeadArgs& a, const Chunk& k) {
             a.wpk = (const f32x4*)m->d_att_head; a.bias = m->att_first.d_b; a.w = m->att_first.d_w; a.act = m->cfg.activation;
             bool valu = m->r8_valu || m->bf16;               // vector-ALU form (32-bit output offsets, see r8v_fits)
-            for (size_t i = b0; i < b1; ++i) valu = valu && (size_t)imgs[i].H * imgs[i].W < ((size_t)1 << 28);
+            for (size_t i = k.b0; i < k.b1; ++i) valu = valu && (size_t)imgs[i].H * imgs[i].W < ((size_t)1 << 28);
             if (m->bf16 && !valu) { set_error("bf16 path: image too large for the attention head kernel"); throw ArgError(); }
             if (head_variant && !valu) { set_error("attention head of an elu / leaky graph: image too large for the vector-ALU kernel"); throw ArgError(); }
-            ProfScope ps(m, m->bf16 ? "att_headv_kernel<true>" : (valu ? "att_headv_kernel<false>" : "att_head_kernel"), flops);
-            ps.bytes = bytes;
-            if (m->bf16) hipLaunchKernelGGL(att_headv_kernel<true>, dim3(tiles), dim3(256), 0, m->stream, a);
-            else if (valu) hipLaunchKernelGGL(att_headv_kernel<false>, dim3(tiles), dim3(256), 0, m->stream, a);
-            else hipLaunchKernelGGL(att_head_kernel, dim3(tiles), dim3(256), 0, m->stream, a);
-        }
+            ProfScope ps(m, m->bf16 ? "att_headv_kernel<true>" : (valu ? "att_headv_kernel<false>" : "att_head_kernel"), k.flops);
+            ps.bytes = k.bytes;
+            const dim3 grid(k.units.total);
+            if (m->bf16) hipLaunchKernelGGL(att_headv_kernel<true>, grid, dim3(256), 0, m->stream, a);
+            else if (valu) hipLaunchKernelGGL(att_headv_kernel<false>, grid, dim3(256), 0, m->stream, a);
+            else hipLaunchKernelGGL(att_head_kernel, grid, dim3(256), 0, m->stream, a);
+        });
     } else {
         y = direct_act(m, m->att_first, imgs, true, stats);
         y = run_pool(m, y, POOL_MAX);

@@ -13,6 +13,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "launch_plan.h"      // MAXP
+
 namespace asep {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -91,7 +93,6 @@ __device__ __forceinline__ const T* concat_src(const T* in0, const T* in1, int c
     const long off = c < c0 ? (long)c * (long)sizeof(T) : d10 + (long)(c - c0) * (long)sizeof(T);
     return reinterpret_cast<const T*>(reinterpret_cast<const char*>(in0) + off);
 }
-constexpr int MAXP = 12;
 // Problem of work unit t in a launch whose problems' unit ranges start at a.p[i].tile_begin (increasing with i): the index is a
 // COUNT over all starts, so the scalar loads are requested together and answered in one round trip.  (The search loop this replaces
 // -- while (bid >= a.p[pi + 1].tile_begin) ++pi -- compiled to one s_load + s_waitcnt per step: up to eleven dependent scalar-cache

@@ -1,0 +1,79 @@
+// The arithmetic of the ARU engine's layer launchers, in one place and in plain C++17: no HIP, no device types, nothing of the engine, so that a
+// host program can check it (tests/launch_plan_check.cpp).
+//
+// A launch covers one layer of at most MAXP problems (pages x scales); a longer list is cut into chunks.  The work units of a launch are the
+// problems' unit lists one behind the other: problem i's units start at its `begin` (tile_begin / blk_begin / begin of the kernels' *Prob structs).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace asep {
+
+constexpr int MAXP = 12;                  // problems of one launch: the p[] of every *Args struct
+
+// ---- the cut of n problems into launches: chunk c = problems [chunk_begin(c), chunk_end(n, c)) ----
+inline size_t num_chunks(size_t n) { return (n + MAXP - 1) / MAXP; }
+inline size_t chunk_begin(size_t c) { return c * MAXP; }
+inline size_t chunk_end(size_t n, size_t c) { return std::min(n, (c + 1) * (size_t)MAXP); }
+
+// ---- numbering of a launch's work units: next_*() is called for the problems of a launch in order, total = the units so far ----
+struct Units { int per_row, begin; };     // 2-D: tiles_x and tile_begin; strips: strips and begin; 1-D: per_row is 0
+struct UnitCounter {
+    int total = 0;
+    // tiles of tw x th pixels over an H x W problem, row by row: tile (x, y) is unit begin + y * per_row + x
+    Units next_tiles(int H, int W, int tw, int th) {
+        const Units u{(W + tw - 1) / tw, total};
+        total += u.per_row * ((H + th - 1) / th);
+        return u;
+    }
+    // blocks of `per_block` items over `items` items (the last block is partial when per_block does not divide items)
+    Units next_blocks(size_t items, size_t per_block) {
+        const Units u{0, total};
+        total += (int)((items + per_block - 1) / per_block);
+        return u;
+    }
+    // convr_kernel: strips of `sw` columns, a unit = one row of one strip
+    Units next_strips(int H, int W, int sw) {
+        const Units u{(W + sw - 1) / sw, total};
+        total += u.per_row * H;
+        return u;
+    }
+};
+
+// ---- one-shot kernels (one block per unit): XCD bands from a few waves of blocks per XCD on.  chunk = ceil(total / 8) and the grid is padded to
+//      8 * chunk blocks (block b = unit (b & 7) * chunk + (b >> 3); blocks beyond the last unit leave at once), or chunk = 0: identity order ----
+struct OneshotPlan { int chunk, units; };
+inline OneshotPlan oneshot_plan(int total, bool use_xcd_sched) {
+    if (!use_xcd_sched || total < 8 * 64) return {0, total};
+    const int chunk = (total + 7) / 8;
+    return {chunk, 8 * chunk};
+}
+
+// ---- persistent kernels (resident blocks walk the units with a grid stride): work unit -> tile table for the problems' tile grids (tile numbers
+//      begin + y * tx + x, `total` tiles in all): the tiles of every problem in 4 x 8 super-tile order (groups of 4 rows x 8 columns, the groups
+//      walked down a column of groups first), the list cut into eight chunks, unit k = the (k / 8)-th tile of chunk k mod 8 (block b runs on XCD
+//      b mod 8).  Empty when the grids do not add up to `total`: no schedule ----
+struct TileDims { int tx, ty, begin; };
+inline std::vector<int32_t> xcd_order(const std::vector<TileDims>& probs, int total) {
+    std::vector<int32_t> order;
+    order.reserve(total);
+    for (const TileDims& q : probs)
+        for (int gc = 0; gc * 8 < q.tx; ++gc)
+            for (int gr = 0; gr * 4 < q.ty; ++gr)
+                for (int r = 0; r < 4; ++r)
+                    for (int c = 0; c < 8; ++c) {
+                        const int ty = gr * 4 + r, tx = gc * 8 + c;
+                        if (ty < q.ty && tx < q.tx) order.push_back(q.begin + ty * q.tx + tx);
+                    }
+    if ((int)order.size() != total) return {};
+    std::vector<int32_t> sched(total);
+    int off[9];
+    off[0] = 0;
+    for (int x = 0; x < 8; ++x) off[x + 1] = off[x] + (total - x + 7) / 8;
+    for (int k = 0; k < total; ++k) sched[k] = order[off[k % 8] + k / 8];
+    return sched;
+}
+
+}  // namespace asep
