@@ -16,7 +16,7 @@ class AsepError(RuntimeError):
 
 
 MLP_MAX_HIDDEN = 4       # GNN_MLP_MAX (csrc/gnn_kernels.h): hidden layers of the interaction / attention / classifier MLPs
-ABI_VERSION = 7          # ASEP_ABI_VERSION of include/asep_hip.h this table was written against
+ABI_VERSION = 8          # ASEP_ABI_VERSION of include/asep_hip.h this table was written against
 
 
 class _SizedCfg(C.Structure):
@@ -94,6 +94,8 @@ SIGNATURES = {
     "asep_gnn_get_hidden": (C.c_int, [_P, _P, C.c_size_t]),
     "asep_gnn_flops": (C.c_double, [_P, C.c_int, C.c_int, C.c_int]),
     "asep_gnn_attach_backbone": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_char_p)]),
+    "asep_gnn_attach_backbone_maps": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
+    "asep_gnn_get_feature_map": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_int32)]),
     "asep_gnn_forward_visual": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P,
                                           C.c_int, _P, _P]),
     "asep_gnn_forward_visual_dev": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P,

@@ -97,6 +97,10 @@ class GnnConfig:
     visual_layers: List[str] = field(default_factory=list)
     mvn: bool = False                 # GraphRelation flag: per-image standardisation of the fed image
     backbone: dict = field(default_factory=dict)            # AruConfig fields of the ARU_v1 backbone (graph 'RU')
+    # feature_map_generation_params layer_depth per map (feature_map_generators.py:72-197); empty = all -1.  -1: the end point itself.
+    # d > 0 with a from_layer: that end point through a 1x1 conv to d/2 channels and a 3x3 conv to d channels.  d > 0 with from_layer '':
+    # the same two convs over the previous map, the 3x3 at stride 2 (an SSD-style pyramid below the backbone)
+    visual_layer_depths: List[int] = field(default_factory=list)
 
     def backbone_cfg(self) -> "AruConfig":
         kw = dict(graph="RU", apply_softmax=False)
@@ -104,16 +108,54 @@ class GnnConfig:
         kw["mvn"] = bool(kw.get("mvn", False) or self.mvn)
         return AruConfig(**kw)
 
-    def visual_channels(self) -> List[int]:
-        """Channels of the selected end points: feat_root * 2^level (ARU_v1.py:208-292)."""
+    MAX_LAYER_DEPTH = 256             # widest generated map the engine serves (asep_gnn_attach_backbone_maps)
+
+    def layer_depths(self) -> List[int]:
+        """``visual_layer_depths`` per map (empty = all -1), checked against what the reference can build (``ValueError`` with the reason)"""
+        depths = [int(d) for d in self.visual_layer_depths] or [-1] * len(self.visual_layers)
+        if len(depths) != len(self.visual_layers):
+            raise ValueError(f"visual_layer_depths has {len(depths)} entries for {len(self.visual_layers)} visual_layers "
+                             "(feature_map_generators.py:130: from_layer and layer_depth have the same length)")
+        for i, (name, d) in enumerate(zip(self.visual_layers, depths)):
+            if not name and i == 0:
+                raise ValueError("visual_layers[0] is empty: an empty from_layer shrinks the previous feature map and there is none "
+                                 "(feature_map_generators.py:154)")
+            if not name and d == -1:
+                raise ValueError(f"visual_layers[{i}] is empty and its layer_depth is -1: an empty from_layer builds a new map and needs "
+                                 "its depth (feature_map_generators.py:145-155)")
+            if d == -1:
+                continue
+            if d <= 0 or d % 2:
+                raise ValueError(f"layer_depth {d} of map {i}: a positive even depth is needed, layer_depth / 2 is the width of the 1x1 "
+                                 "convolution (feature_map_generators.py:159-160)")
+            if d > self.MAX_LAYER_DEPTH:
+                raise ValueError(f"layer_depth {d} of map {i}: the engine serves generated maps of up to {self.MAX_LAYER_DEPTH} channels")
+        return depths
+
+    def _endpoint_channels(self, name: str) -> int:
         import re
         bc = self.backbone_cfg()
-        out = []
-        for name in self.visual_layers:
-            m = re.fullmatch(r"scale_\d+_unet_(down|up)_(\d+)_(conv|deconv)", name)
-            if not m or int(m.group(2)) >= bc.scale_space_num:
-                raise ValueError(f"'{name}' is not a feature-map end point of the ARU_v1 backbone")
-            out.append(bc.feat(int(m.group(2))))
+        m = re.fullmatch(r"scale_\d+_unet_(down|up)_(\d+)_(conv|deconv)", name)
+        if not m or int(m.group(2)) >= bc.scale_space_num:
+            raise ValueError(f"'{name}' is not a feature-map end point of the ARU_v1 backbone")
+        return bc.feat(int(m.group(2)))
+
+    def visual_channels(self) -> List[int]:
+        """Channels of the feature maps: feat_root * 2^level for an end point (ARU_v1.py:208-292), layer_depth for a generated map."""
+        return [self._endpoint_channels(name) if d == -1 else d for name, d in zip(self.visual_layers, self.layer_depths())]
+
+    def visual_generators(self) -> List[dict]:
+        """The generated maps in order: index, the channels read (``cin``), ``depth``, ``stride`` and the variable scopes of the two
+        convolutions as the reference spells them -- f'{base}_1_Conv2d_{index}_1x1_{layer_depth / 2}' with Python's true division (a
+        float: '3.0') and f'{base}_2_Conv2d_{index}_3x3_s2_{layer_depth}', base = the last from_layer that had depth -1, '' before any
+        (feature_map_generators.py:133,147,159,164)."""
+        out, base, chans = [], "", self.visual_channels()
+        for i, (name, d) in enumerate(zip(self.visual_layers, self.layer_depths())):
+            if d == -1:
+                base = name
+                continue
+            out.append({"index": i, "cin": self._endpoint_channels(name) if name else chans[i - 1], "depth": d, "stride": 1 if name else 2,
+                        "conv1": f"{base}_1_Conv2d_{i}_1x1_{d / 2}", "conv2": f"{base}_2_Conv2d_{i}_3x3_s2_{d}"})
         return out
 
     @property

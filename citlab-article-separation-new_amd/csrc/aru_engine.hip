@@ -1611,6 +1611,16 @@ int aru_endpoint_channels(const asep_aru* m, const char* name) {
 int aru_num_classes(const asep_aru* m) { return m ? m->cfg.n_classes : -1; }
 int aru_input_channels(const asep_aru* m) { return m ? m->cfg.channels : -1; }
 
+// One record of the handle's launch profile (asep_aru_profile) around launches that ANOTHER engine queues on the stream of the handle's last
+// forward: the relation net's feature-map generator runs between the backbone and the ROI kernels and is timed in the same report.
+void* aru_prof_begin(asep_aru* m, const char* name, const char* detail, double flops, double bytes) {
+    if (!m || !m->profiling) return nullptr;
+    ProfScope* ps = new ProfScope(m, name, flops, detail ? detail : "");
+    ps->bytes = bytes;
+    return ps;
+}
+void aru_prof_end(void* scope) { delete static_cast<ProfScope*>(scope); }
+
 }  // namespace asep
 
 // ---- weights at load time: which packed vector (aru_pack.h) goes into which member, under which cfg and switch -------------------

@@ -120,6 +120,10 @@ int aru_endpoint_channels(const asep_aru* m, const char* name);
 int aru_num_classes(const asep_aru* m);
 // Number of image channels a page of the model has (1 = gray, 3 = interleaved RGB).
 int aru_input_channels(const asep_aru* m);
+// Brackets launches queued on the stream of the model's last forward with one record of its launch profile (asep_aru_profile); begin returns
+// nullptr while nothing is recorded, end takes that too.  `name` as rocprofv3 prints the kernel, `detail` the layer text of mode 2.
+void* aru_prof_begin(asep_aru* m, const char* name, const char* detail, double flops, double bytes);
+void aru_prof_end(void* scope);
 // Stream and buffer pool of an asep_post handle (post_engine.hip), for the entry points of other translation units that run
 // on that handle (textblock_engine.hip).
 hipStream_t post_stream(asep_post* p);

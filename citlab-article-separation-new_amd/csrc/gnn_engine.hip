@@ -13,6 +13,7 @@
 #include <memory>
 
 #include "asep_common.h"
+#include "fmap_kernels.h"
 #include "gnn_kernels.h"
 
 using namespace asep;
@@ -65,6 +66,19 @@ struct asep_gnn {
     std::vector<void*> vis_owned;
     std::vector<int> vis_C, vis_d;
     int vis_total = 0;
+    // generated feature maps (feature_map_generators.py:72-197; fmap_kernels.h): per map its layer_depth (-1 = the end point itself) and,
+    // for a generated one, the two convolutions.  All empty / -1 for the default layout: nothing below is then touched by a forward.
+    struct FmapGen {
+        int depth = -1;                              // layer_depth d: 1x1 to d / 2 channels, 3x3 to d
+        int Cin = 0, stride = 1;                     // channels of the map it reads; 2 = from_layer '' (reads map i - 1)
+        float *W1 = nullptr, *b1 = nullptr, *W2 = nullptr, *b2 = nullptr;   // owned through vis_owned
+    };
+    struct FmapRef { const float* p = nullptr; int fh = 0, fw = 0, C = 0, bf = 0; };
+    std::vector<FmapGen> vis_gen;
+    int n_generated = 0;
+    BufferPool fmap_pool;                            // intermediates and generated maps of the last page (sized at its first forward)
+    std::vector<FmapRef> fmap_last;                  // every map of the last page, generated or not (asep_gnn_get_feature_map)
+    std::string fmap_last_prefix;
     float* Wout = nullptr;                           // output_type 1: GraphLSTM1/dense/weights [Uin, H]
     AttHeadW att_w[GNN_MAX_HEADS] = {};              // attention_heads > 0: per-head interaction + attention MLPs
     AttHeadW* d_att_w = nullptr;                     // the same in device memory (kernel argument of gnn_msg_att_kernel)
@@ -105,6 +119,8 @@ struct asep_gnn {
         vis_owned.clear(); vis_W.clear(); vis_b.clear(); vis_names.clear(); vis_C.clear(); vis_d.clear();
         vise_W.clear(); vise_b.clear(); vise_d.clear();
         vis_total = 0; vise_total = 0;
+        vis_gen.clear(); fmap_last.clear(); n_generated = 0;
+        fmap_pool.release();                         // (hipFree waits for the device: no forward still reads the maps)
         backbone = nullptr;
     }
     ~asep_gnn() {
@@ -597,6 +613,81 @@ int forward_batch_impl(asep_gnn* g, BufferPool& pool, int n, GraphCtx* cx, hipSt
 }
 #endif
 
+// TensorFlow's SAME rule along one axis for a 3-tap filter: output size and the padding in front (the smaller half)
+inline void same_pad3(int n, int stride, int* out, int* before) {
+    *out = (n + stride - 1) / stride;
+    *before = std::max((*out - 1) * stride + 3 - n, 0) / 2;
+}
+
+// feature_map_generators.py:140-194 for the page whose backbone end points are "<prefix><name>" of the forward queued on s: every generated
+// map into the handle's arena (two launches each, fmap_kernels.h), every map's address into g->fmap_last.  A layout without generated
+// maps returns at once: it allocates and launches nothing.
+int generate_maps_dev(asep_gnn* g, const std::string& prefix, hipStream_t s) {
+    if (g->n_generated == 0) return ASEP_OK;
+    const size_t n = g->vis_names.size();
+    g->fmap_last.assign(n, asep_gnn::FmapRef{});
+    g->fmap_last_prefix = prefix;
+    for (size_t i = 0; i < n; ++i) {
+        const asep_gnn::FmapGen& G = g->vis_gen[i];
+        asep_gnn::FmapRef src{};
+        if (G.depth < 0 || G.stride == 1) {                 // a backbone end point: the map itself, or what the two convolutions read
+            int dims[3];
+            int rc = aru_endpoint_dev(g->backbone, (prefix + g->vis_names[i]).c_str(), &src.p, dims, &src.bf);
+            if (rc) return rc;
+            src.fh = dims[0]; src.fw = dims[1]; src.C = dims[2];
+        } else {
+            src = g->fmap_last[i - 1];
+        }
+        if (G.depth < 0) { g->fmap_last[i] = src; continue; }
+        if (src.C != G.Cin) { set_error("feature map %zu reads %d channels, its 1x1 filter was loaded for %d", i, src.C, G.Cin); return ASEP_ERR_ARG; }
+        const int half = G.depth / 2;
+        FmapConvArgs a{};
+        a.in = src.p; a.W = G.W1; a.b = G.b1; a.ih = src.fh; a.iw = src.fw; a.Ci = src.C; a.Co = half; a.oh = src.fh; a.ow = src.fw;
+        a.stride = 1;
+        const size_t n1 = (size_t)src.fh * src.fw * half;
+        float* mid = (float*)g->fmap_pool.get(n1 * sizeof(float));
+        a.out = mid;
+        FmapConvArgs c{};
+        c.in = mid; c.W = G.W2; c.b = G.b2; c.ih = src.fh; c.iw = src.fw; c.Ci = half; c.Co = G.depth; c.stride = G.stride;
+        same_pad3(src.fh, G.stride, &c.oh, &c.pad_t);
+        same_pad3(src.fw, G.stride, &c.ow, &c.pad_l);
+        const size_t n2 = (size_t)c.oh * c.ow * G.depth;
+        c.out = (float*)g->fmap_pool.get(n2 * sizeof(float));
+        if (n1 + 255 > ((size_t)1 << 31) * 256 || n2 + 255 > ((size_t)1 << 31) * 256) { set_error("feature map %zu is too large for one launch", i); return ASEP_ERR_UNSUPPORTED; }
+        const std::string where = "fm_" + std::to_string(i) + " " + std::to_string(src.fh) + "x" + std::to_string(src.fw);
+        const size_t ebytes = src.bf ? 2 : 4;
+        {   // algorithmic bytes: the input once, the filter and bias once, the output once
+            const std::string det = where + " " + std::to_string(src.C) + "->" + std::to_string(half);
+            void* ps = aru_prof_begin(g->backbone, src.bf ? "fmap_conv1x1_kernel<true>" : "fmap_conv1x1_kernel<false>", det.c_str(),
+                                      2.0 * (double)n1 * src.C,
+                                      (double)src.fh * src.fw * src.C * ebytes + 4.0 * ((double)src.C * half + half) + 4.0 * (double)n1);
+            if (src.bf) hipLaunchKernelGGL(fmap_conv1x1_kernel<true>, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL(fmap_conv1x1_kernel<false>, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, a);
+            aru_prof_end(ps);
+        }
+        {
+            const std::string det = where + " " + std::to_string(half) + "->" + std::to_string(G.depth) + " s" + std::to_string(G.stride);
+            void* ps = aru_prof_begin(g->backbone, "fmap_conv3x3_kernel", det.c_str(), 2.0 * (double)n2 * 9 * half,
+                                      4.0 * (double)n1 + 4.0 * (9.0 * half * G.depth + G.depth) + 4.0 * (double)n2);
+            hipLaunchKernelGGL(fmap_conv3x3_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, c);
+            aru_prof_end(ps);
+        }
+        g->fmap_last[i] = asep_gnn::FmapRef{c.out, c.oh, c.ow, G.depth, 0};
+    }
+    ASEP_HIP_CHECK(hipGetLastError());
+    return ASEP_OK;
+}
+
+// map i of the page "<prefix>": the backbone's end point (the default layout: exactly the lookup the ROI launchers always made) or, in a
+// layout with generated maps, what generate_maps_dev left for this page
+int visual_map_dev(asep_gnn* g, const std::string& prefix, size_t i, const float** fm, int dims[3], int* bf) {
+    if (g->n_generated == 0) return aru_endpoint_dev(g->backbone, (prefix + g->vis_names[i]).c_str(), fm, dims, bf);
+    if (i >= g->fmap_last.size() || !g->fmap_last[i].p || g->fmap_last_prefix != prefix) { set_error("feature map %zu of this page was not generated", i); return ASEP_ERR_ARG; }
+    const asep_gnn::FmapRef& r = g->fmap_last[i];
+    *fm = r.p; dims[0] = r.fh; dims[1] = r.fw; dims[2] = r.C; *bf = r.bf;
+    return ASEP_OK;
+}
+
 // graph_relation.py:84-139 in front of the graph: backbone, ROI max + compression per feature map, concatenation.
 // ROI max + compression of one page's nodes from the backbone end points "<prefix><name>" of the forward that is queued
 // on s; d_ug [N, U - visual dims] -> d_u [N, U]
@@ -609,7 +700,7 @@ int visual_rois_dev(asep_gnn* g, int N, const float* d_ug, const std::string& pr
         const float* fm = nullptr;
         int dims[3];
         int bf = 0;                                         // a bf16 backbone (compute_dtype 1) hands over bf16 maps
-        int rc = aru_endpoint_dev(g->backbone, (prefix + g->vis_names[i]).c_str(), &fm, dims, &bf);
+        int rc = visual_map_dev(g, prefix, i, &fm, dims, &bf);
         if (rc) return rc;
         if (dims[2] != g->vis_C[i]) { set_error("end point %s has %d channels, expected %d", g->vis_names[i].c_str(), dims[2], g->vis_C[i]); return ASEP_ERR_ARG; }
         RoiArgs a{};
@@ -636,7 +727,7 @@ int visual_edge_rois_dev(asep_gnn* g, int E, const float* d_ef_fed, const std::s
         const float* fm = nullptr;
         int dims[3];
         int bf = 0;
-        int rc = aru_endpoint_dev(g->backbone, (prefix + g->vis_names[i]).c_str(), &fm, dims, &bf);
+        int rc = visual_map_dev(g, prefix, i, &fm, dims, &bf);
         if (rc) return rc;
         RoiArgs a{};
         a.fm = fm; a.fh = dims[0]; a.fw = dims[1]; a.C = dims[2];
@@ -679,6 +770,9 @@ int visual_features_dev(asep_gnn* g, int N, const float* d_ug, const float* d_im
     int rc = reserve_u_cat(g, (size_t)N * g->Uin);
     if (rc) return rc;
     rc = asep_aru_forward_dev(g->backbone, d_img, h, w, d_bo, nullptr, nullptr, 0.f, s);
+    if (rc) return rc;
+    g->fmap_pool.begin();
+    rc = generate_maps_dev(g, std::string(), s);
     if (rc) return rc;
     rc = visual_rois_dev(g, N, d_ug, std::string(), d_reg, P, d_np, g->d_u_cat, s);
     if (rc) return rc;
@@ -801,7 +895,8 @@ asep_gnn* asep_gnn_load(const void* weight_blob, size_t nbytes, const asep_gnn_c
     }
     if (rc) return nullptr;
     for (auto& kv : blob)
-        if (kv.first.rfind("visual_node_feature_compression_fm_", 0) == 0 || kv.first.rfind("visual_edge_feature_compression_fm_", 0) == 0)
+        if (kv.first.rfind("visual_node_feature_compression_fm_", 0) == 0 || kv.first.rfind("visual_edge_feature_compression_fm_", 0) == 0 ||
+            kv.first.find("_Conv2d_") != std::string::npos)       // (the feature-map generator's convolutions, asep_gnn_attach_backbone_maps)
             g->vis_blob[kv.first] = kv.second;
     warn_ignored_switches();
     if (const char* ev = getenv("ASEP_GNN_STEP")) g->use_step = atoi(ev) != 0;
@@ -935,18 +1030,62 @@ int asep_gnn_get_hidden(asep_gnn* g, float* out, size_t max_floats) {
 int asep_gnn_step_mode(const asep_gnn* g) { return g ? step_mode_of(g) : ASEP_ERR_ARG; }
 
 int asep_gnn_attach_backbone(asep_gnn* g, asep_aru* backbone, int n_maps, const char* const* endpoint_names) {
+    return asep_gnn_attach_backbone_maps(g, backbone, n_maps, endpoint_names, nullptr);
+}
+
+int asep_gnn_attach_backbone_maps(asep_gnn* g, asep_aru* backbone, int n_maps, const char* const* endpoint_names, const int32_t* layer_depths) {
     ASEP_GUARD_BEGIN
     if (!g || !backbone || n_maps < 1 || !endpoint_names) { set_error("asep_gnn_attach_backbone: bad argument"); return ASEP_ERR_ARG; }
     g->free_visual();                                   // a second attach replaces (and frees) the first one's uploads
+    std::string base;                                   // feature_map_generators.py:133,147: the last from_layer that had depth -1
     for (int i = 0; i < n_maps; ++i) {
         if (!endpoint_names[i]) { set_error("asep_gnn_attach_backbone: null end-point name"); g->free_visual(); return ASEP_ERR_ARG; }
-        const int C = aru_endpoint_channels(backbone, endpoint_names[i]);
-        if (C < 1 || C > 256) {
+        const int depth = layer_depths ? layer_depths[i] : -1;
+        const bool named = endpoint_names[i][0] != 0;
+        int C = named ? aru_endpoint_channels(backbone, endpoint_names[i]) : 0;
+        if (named && (C < 1 || C > 256)) {
             set_error("asep_gnn_attach_backbone: '%s' is not a feature map of this backbone (only unet conv/deconv "
-                      "end points with layer_depth -1 are supported)", endpoint_names[i]);
+                      "end points are supported)", endpoint_names[i]);
             g->free_visual();
             return ASEP_ERR_UNSUPPORTED;
         }
+        asep_gnn::FmapGen G{};
+        if (depth == -1) {
+            if (!named) {
+                set_error("asep_gnn_attach_backbone_maps: map %d has an empty from_layer and layer_depth -1: an empty from_layer builds a new map "
+                          "and needs its depth (feature_map_generators.py:145-155)", i);
+                g->free_visual();
+                return ASEP_ERR_ARG;
+            }
+            base = endpoint_names[i];
+        } else {
+            if (!named && i == 0) {
+                set_error("asep_gnn_attach_backbone_maps: map 0 has an empty from_layer: there is no previous feature map to shrink "
+                          "(feature_map_generators.py:154)");
+                g->free_visual();
+                return ASEP_ERR_ARG;
+            }
+            if (depth < 2 || depth % 2 != 0 || depth > 256) {
+                set_error("asep_gnn_attach_backbone_maps: map %d has layer_depth %d: an even depth from 2 to 256 is served (layer_depth / 2 is the "
+                          "width of the 1x1 convolution, feature_map_generators.py:159-160)", i, depth);
+                g->free_visual();
+                return depth > 256 ? ASEP_ERR_UNSUPPORTED : ASEP_ERR_ARG;
+            }
+            G.depth = depth;
+            G.stride = named ? 1 : 2;
+            G.Cin = named ? C : g->vis_C[i - 1];
+            // the reference formats layer_depth / 2 as a Python float: "<d/2>.0" (feature_map_generators.py:159,164)
+            const std::string n1 = base + "_1_Conv2d_" + std::to_string(i) + "_1x1_" + std::to_string(depth / 2) + ".0/";
+            const std::string n2 = base + "_2_Conv2d_" + std::to_string(i) + "_3x3_s2_" + std::to_string(depth) + "/";
+            int rc = upload_named(g->vis_owned, g->vis_blob, n1 + "weights", {1, 1, G.Cin, depth / 2}, &G.W1);
+            if (!rc) rc = upload_named(g->vis_owned, g->vis_blob, n1 + "biases", {depth / 2}, &G.b1);
+            if (!rc) rc = upload_named(g->vis_owned, g->vis_blob, n2 + "weights", {3, 3, depth / 2, depth}, &G.W2);
+            if (!rc) rc = upload_named(g->vis_owned, g->vis_blob, n2 + "biases", {depth}, &G.b2);
+            if (rc) { g->free_visual(); return rc; }
+            C = depth;
+            ++g->n_generated;
+        }
+        g->vis_gen.push_back(G);
         const std::string scope = "visual_node_feature_compression_fm_" + std::to_string(i) + "/dense/";
         auto w = g->vis_blob.find(scope + "weights"), b = g->vis_blob.find(scope + "bias");
         if (w == g->vis_blob.end() || b == g->vis_blob.end()) { set_error("weights: missing tensor %sweights|bias", scope.c_str()); g->free_visual(); return ASEP_ERR_WEIGHTS; }
@@ -994,6 +1133,30 @@ int asep_gnn_attach_backbone(asep_gnn* g, asep_aru* backbone, int n_maps, const 
         return ASEP_ERR_ARG;
     }
     g->backbone = backbone;
+    return ASEP_OK;
+    ASEP_GUARD_END
+}
+
+int asep_gnn_get_feature_map(asep_gnn* g, int index, float* out, size_t max_floats, int32_t dims[3]) {
+    ASEP_GUARD_BEGIN
+    if (!g || !g->backbone || !dims || index < 0 || index >= (int)g->vis_names.size()) { set_error("asep_gnn_get_feature_map: bad argument"); return ASEP_ERR_ARG; }
+    const float* p = nullptr;
+    int d[3], bf = 0;
+    // the maps of the page the last forward served last (a batch: its last page)
+    int rc = visual_map_dev(g, g->n_generated ? g->fmap_last_prefix : std::string(), (size_t)index, &p, d, &bf);
+    if (rc) return rc;
+    dims[0] = d[0]; dims[1] = d[1]; dims[2] = d[2];
+    const size_t n = (size_t)d[0] * d[1] * d[2];
+    if (!out) return ASEP_OK;                            // sizes only
+    if (max_floats < n) { set_error("asep_gnn_get_feature_map: buffer too small (%zu floats needed)", n); return ASEP_ERR_ARG; }
+    ASEP_HIP_CHECK(hipStreamSynchronize(g->stream));
+    if (bf) {                                            // a bf16 end point widens exactly
+        std::vector<uint16_t> h(n);
+        ASEP_HIP_CHECK(hipMemcpy(h.data(), p, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) { const uint32_t u = (uint32_t)h[i] << 16; memcpy(out + i, &u, 4); }
+    } else {
+        ASEP_HIP_CHECK(hipMemcpy(out, p, n * sizeof(float), hipMemcpyDeviceToHost));
+    }
     return ASEP_OK;
     ASEP_GUARD_END
 }
@@ -1073,7 +1236,7 @@ int asep_gnn_forward_visual_batch_dev(asep_gnn* g, int n_pages, const asep_gnn_p
     float* d_u = g->d_u_cat;
     float* d_efc = g->d_ef_cat;
 #ifdef ASEP_ABLATION
-    if (L == 1 && g->batch_graph && n_pages > 1 && g->vise_total == 0 && graph_batch_eligible(g)) {
+    if (L == 1 && g->batch_graph && n_pages > 1 && g->vise_total == 0 && g->n_generated == 0 && graph_batch_eligible(g)) {
         // stage by stage over all pages (forward_batch_impl): ROI kernels per feature map, steps, classifier as one launch each
         const int U = g->Uin, ugc = U - g->vis_total;
         g->stream = s;
@@ -1129,6 +1292,11 @@ int asep_gnn_forward_visual_batch_dev(asep_gnn* g, int n_pages, const asep_gnn_p
         hipStream_t ls = L > 1 ? g->page_lanes[b % L]->s : s;
         BufferPool& lp = L > 1 ? g->page_lanes[b % L]->pool : g->pool;
         const std::string prefix = b ? "p" + std::to_string(b) + "/" : std::string();
+        // generated maps page by page, the same two launches as the single-page call: on one stream the pages share the arena's buffers
+        // (page b + 1's generator is ordered behind page b's ROI kernels), on page lanes every page keeps its own
+        if (b == 0 || L == 1) g->fmap_pool.begin();
+        rc = generate_maps_dev(g, prefix, ls);
+        if (rc) return rc;
         rc = visual_rois_dev(g, q.N, q.d_node_feat, prefix, q.d_regions, P, q.d_num_points, d_u, ls);
         if (rc) return rc;
         const float* d_ef = q.d_edge_feat;

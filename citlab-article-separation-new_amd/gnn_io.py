@@ -82,7 +82,16 @@ class GnnGraph:
             if c.visual_dims:
                 bb = self.backbone_graph()
                 names = (C.c_char_p * len(c.visual_layers))(*[n.encode() for n in c.visual_layers])
-                rc = lib.asep_gnn_attach_backbone(h, bb.handle(device_id), len(c.visual_layers), names)
+                try:
+                    depths = c.layer_depths()                # (refuses a layout the reference cannot build, with the reason)
+                except ValueError as e:
+                    lib.asep_gnn_free(h)
+                    raise _lib.AsepError(str(e))
+                if any(d != -1 for d in depths):             # generated maps (feature_map_generators.py:72-197)
+                    rc = lib.asep_gnn_attach_backbone_maps(h, bb.handle(device_id), len(c.visual_layers), names,
+                                                           (C.c_int32 * len(depths))(*depths))
+                else:
+                    rc = lib.asep_gnn_attach_backbone(h, bb.handle(device_id), len(c.visual_layers), names)
                 if rc < 0:
                     lib.asep_gnn_free(h)
                     raise _lib.AsepError("asep_gnn_attach_backbone failed: " + _lib.last_error())
@@ -107,13 +116,15 @@ class GnnGraph:
             pass
 
 
-def load_graph(pb_path, visual_layers=None, num_transition_steps=None) -> GnnGraph:
+def load_graph(pb_path, visual_layers=None, num_transition_steps=None, visual_layer_depths=None) -> GnnGraph:
     """gnn/io.py:12-25.  Accepts a TF1 frozen graph (``*.pb``, decoded without TensorFlow by ``pb_import.py``)
     or the engine's ``*.asepw`` container (+ ``.json`` side-car).  ``visual_layers`` names the backbone end points
     of a graph exported with ``--image_input`` (``--feature_map_generation_params from_layer=[...]``); the names
     are not recoverable from the constants alone, the default is ``scale_0_unet_up_<level>_conv`` per map.
     ``num_transition_steps`` is read from the op graph (one edge-MLP MatMul per step); only a constants-only container
-    without that structure needs it passed in."""
+    without that structure needs it passed in.  ``visual_layer_depths``: the ``layer_depth`` list of a layout with generated maps
+    (``''`` in ``visual_layers`` = from the previous map); a frozen graph says the depths itself (the generator's variable names), what is
+    passed must agree with it."""
     if isinstance(pb_path, GnnGraph):
         return pb_path
     if not os.path.isfile(pb_path):
@@ -121,10 +132,12 @@ def load_graph(pb_path, visual_layers=None, num_transition_steps=None) -> GnnGra
     if str(pb_path).endswith(".pb"):
         from . import pb_import
         tensors, cfg = pb_import.gnn_from_nodes(pb_import.read_graph(pb_path), visual_layers=visual_layers,
-                                                num_transition_steps=num_transition_steps)
+                                                num_transition_steps=num_transition_steps, visual_layer_depths=visual_layer_depths)
     else:
         tensors, meta = load_weights(pb_path)
         cfg = GnnConfig(**(meta or {}).get("gnn_cfg", {}))
+        if visual_layer_depths is not None and [int(d) for d in visual_layer_depths] != cfg.layer_depths():
+            raise IOError(f"visual_layer_depths {list(visual_layer_depths)} given, the container was written for {cfg.layer_depths()}")
     if cfg.visual_dims:                                      # ASEP_COMPUTE_DTYPE: the conv backbone of the visual branch (graph stays fp32)
         from .net_post_processing_helper import compute_dtype_from_env
         cfg.backbone = dict(cfg.backbone, compute_dtype=compute_dtype_from_env(cfg.backbone.get("compute_dtype", cfg.backbone_cfg().compute_dtype)))
@@ -414,6 +427,16 @@ def gnn_node_features(graph: GnnGraph, num_nodes, device=0):
     out = np.empty((int(num_nodes), graph.cfg.u_in_dim), dtype=np.float32)
     _lib.check(lib.asep_gnn_get_node_features(graph.handle(device), out.ctypes.data, out.size),
                "asep_gnn_get_node_features")
+    return out
+
+
+def gnn_feature_map(graph: GnnGraph, index, device=0):
+    """Feature map ``index`` of the last visual forward as float32 [fh, fw, C], generated or not (``asep_gnn_get_feature_map``; tests)."""
+    lib = _lib.init_device(device)
+    dims = (C.c_int32 * 3)()
+    _lib.check(lib.asep_gnn_get_feature_map(graph.handle(device), int(index), None, 0, dims), "asep_gnn_get_feature_map")
+    out = np.empty((dims[0], dims[1], dims[2]), dtype=np.float32)
+    _lib.check(lib.asep_gnn_get_feature_map(graph.handle(device), int(index), out.ctypes.data, out.size, dims), "asep_gnn_get_feature_map")
     return out
 
 

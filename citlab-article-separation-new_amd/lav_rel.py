@@ -282,7 +282,7 @@ def build_parser():
     p.add_argument("--backbone", type=str, default="ARU_v1")
     p.add_argument("--mvn", default=True, **b)
     cli_flags.define_dict(p, "graph_backbone_params", {})
-    cli_flags.define_dict(p, "feature_map_generation_params", {"layer_depth": [-1, -1, -1]})
+    cli_flags.define_feature_map_layout(p, {"layer_depth": [-1, -1, -1]})   # (+ the extensions --visual_layers / --visual_layer_depths, as in run_gnn_clustering)
     cli_flags.define_dict(p, "input_params", {})
     p.add_argument("--num_p_r_thresholds", type=int, default=20)
     p.add_argument("--gpu_devices", type=int, nargs="*", default=[])
@@ -290,7 +290,6 @@ def build_parser():
     p.add_argument("--batch_limiter", type=int, default=-1)
     p.add_argument("--try_gpu", default=None, **b)                          # default: True if --gpu_devices is given (:59-60)
     # extensions
-    p.add_argument("--visual_layers", type=str, nargs="*", default=None)    # as in run_gnn_clustering
     p.add_argument("--num_workers", type=int, default=1)                    # host workers that prepare pages ahead of the GPU owner
     p.add_argument("--device_resize", default=False, **b)                   # as in run_gnn_clustering: True = the uint8 scan is resized on the device
     return p
@@ -499,7 +498,8 @@ class LavGNN(object):
         logging.info("Start evaluation...")
         json_paths = [p for p in load_list_file(flags.eval_list) if p]
         acc = RelationEval(self.device)                              # (no GPU: the package's error, before any work)
-        graph = gnn_io.load_graph(self._pb_path, visual_layers=flags.visual_layers or None)
+        layers, depths = cli_flags.visual_layout(flags)
+        graph = gnn_io.load_graph(self._pb_path, visual_layers=layers, visual_layer_depths=depths)
         if graph.cfg.visual_dims and not flags.image_input:
             raise ValueError("this model was exported with image_input: pass --image_input True")
         from .gnn_input import check_load_mode

@@ -29,6 +29,7 @@ Message fields decoded (field numbers from tensorflow/core/framework/*.proto); e
     TensorShapeProto{dim=2{size=1}}
 The reader is cross-checked against GraphDefs serialised by ``google.protobuf`` (tests/test_pb_import_protobuf.py).
 """
+import re
 import struct
 from collections import OrderedDict
 
@@ -824,6 +825,41 @@ def aru_from_nodes(nodes, num_scales_att=None, apply_softmax=None):
 _PASS_THROUGH = ("Identity", "Enter", "Switch", "Merge", "NextIteration", "Exit", "StopGradient", "PlaceholderWithDefault")
 
 
+_GEN_1X1 = re.compile(r"(?:^|/)([^/]*)_1_Conv2d_(\d+)_1x1_(\d+)\.0/weights$")
+_GEN_3X3 = re.compile(r"(?:^|/)([^/]*)_2_Conv2d_(\d+)_3x3_s2_(\d+)/weights$")
+
+
+def _generated_map_depths(consts, n_maps, chans):
+    """The feature-map generator's convolutions among the constants (feature_map_generators.py:159,164: '<base>_1_Conv2d_<i>_1x1_<d/2>.0',
+    '<base>_2_Conv2d_<i>_3x3_s2_<d>') -> (layer_depth per map, -1 where none; input channels of the 1x1 per generated map).  Names and
+    shapes that contradict each other are refused."""
+    depths, cin = [-1] * n_maps, {}
+    one, three = {}, {}
+    for k, v in consts.items():
+        m1, m3 = _GEN_1X1.search(k), _GEN_3X3.search(k)
+        if m1:
+            one[int(m1.group(2))] = (k, int(m1.group(3)), tuple(v.shape))
+        elif m3:
+            three[int(m3.group(2))] = (k, int(m3.group(3)), tuple(v.shape))
+    if set(one) != set(three):
+        raise IOError(f"feature-map generator: 1x1 convolutions for the maps {sorted(one)}, 3x3 convolutions for {sorted(three)}: "
+                      "graph_relation.py:100-104 builds both for every generated map")
+    for i in sorted(three):
+        (k1, half, s1), (k3, d, s3) = one[i], three[i]
+        if i >= n_maps:
+            raise IOError(f"{k3}: a generated map {i}, the graph has {n_maps} compression layers")
+        if 2 * half != d:
+            raise IOError(f"{k1} and {k3}: the 1x1 convolution is named for {half} channels, layer_depth / 2 = {d / 2}")
+        if len(s1) != 4 or s1[:2] != (1, 1) or s1[3] != half:
+            raise IOError(f"{k1}: shape {s1}, the name says [1, 1, Cin, {half}]")
+        if s3 != (3, 3, half, d):
+            raise IOError(f"{k3}: shape {s3}, the name says [3, 3, {half}, {d}]")
+        if chans[i] != d:
+            raise IOError(f"{k3}: map {i} has {d} channels, its compression layer reads {chans[i]}")
+        depths[i], cin[i] = d, s1[2]
+    return depths, cin
+
+
 def _find_key(consts, suffix):
     hits = [k for k in consts if k == suffix or k.endswith("/" + suffix)]
     hits.sort(key=len)
@@ -851,7 +887,7 @@ def _count_matmul_users(nodes, const_name):
     return len(hits)
 
 
-def gnn_from_nodes(nodes, undirected_graph=True, visual_layers=None, num_transition_steps=None):
+def gnn_from_nodes(nodes, undirected_graph=True, visual_layers=None, num_transition_steps=None, visual_layer_depths=None):
     """GraphDef of a relation net (model_relation.py / graph_relation.py / graph_gnn.py) -> (tensors, GnnConfig).
 
     Widths come from the constants' shapes; the options an exporter can bake into the graph are read from its STRUCTURE and
@@ -869,6 +905,9 @@ def gnn_from_nodes(nodes, undirected_graph=True, visual_layers=None, num_transit
       incorporate_*_in_update (update_fn_lstm.py:13-16,43-50) = number of tensors the gates' ConcatV2 joins, checked against the gate
                                                       weights' input width x + [h] + [u] -> served; an ambiguous layout is refused
       assign_visual_features_to_edges (graph_relation.py:141-172) = visual_edge_feature_compression_fm_<i> variables -> served
+      feature_map_generation_params layer_depth (feature_map_generators.py:72-197) = the generator's variables
+                                                      <base>_1_Conv2d_<i>_1x1_<d/2>.0 and <base>_2_Conv2d_<i>_3x3_s2_<d>: map i is generated with
+                                                      depth d -> served; shapes that contradict the names are refused
     """
     consts = const_tensors(nodes)
     pref = ("GraphLSTM1/message_fn_default/head_0/calculation_interaction_features/concat_u_and_h/"
@@ -1030,10 +1069,19 @@ def gnn_from_nodes(nodes, undirected_graph=True, visual_layers=None, num_transit
             chans.append(int(wv.shape[0]))
             dims.append(int(wv.shape[1]))
             i += 1
+        depths, gen_cin = _generated_map_depths(consts, len(dims), chans)
+        if visual_layer_depths is not None and [int(d) for d in visual_layer_depths] != depths:
+            raise IOError(f"visual_layer_depths {list(visual_layer_depths)} given, the graph's feature-map generator says {depths}")
         if visual_layers is None:
-            # the from_layer names are not stored with the constants; assume the up-path block outputs of scale 0
+            # the from_layer names are not stored with the constants; assume the up-path block outputs of scale 0.  A generated map reads
+            # the previous map (from_layer '') where its 1x1 filter fits that map's channels, an end point of its filter's width otherwise
             visual_layers = []
-            for c in chans:
+            for i, c in enumerate(chans):
+                if depths[i] != -1:
+                    if i > 0 and gen_cin[i] == chans[i - 1]:
+                        visual_layers.append("")
+                        continue
+                    c = gen_cin[i]
                 lvl = int(round(np.log2(c / bcfg.feat_root)))
                 visual_layers.append(f"scale_0_unet_up_{lvl}_conv")
         if len(visual_layers) != len(dims):
@@ -1042,7 +1090,8 @@ def gnn_from_nodes(nodes, undirected_graph=True, visual_layers=None, num_transit
                   for n in nodes)
         backbone = {k: v for k, v in bcfg.to_dict().items() if k not in ("apply_softmax", "mvn")}
         backbone["mvn"] = bool(bcfg.mvn)
-        vis_kw = dict(visual_dims=dims, visual_layers=list(visual_layers), mvn=mvn, backbone=backbone)
+        vis_kw = dict(visual_dims=dims, visual_layers=list(visual_layers), mvn=mvn, backbone=backbone,
+                      visual_layer_depths=depths if any(d != -1 for d in depths) else [])
         u_in -= sum(dims)
         if u_in < 0:
             raise IOError(f"the visual compression layers produce {sum(dims)} features, the GNN is fed {u_in + sum(dims)}")
@@ -1067,6 +1116,11 @@ def gnn_from_nodes(nodes, undirected_graph=True, visual_layers=None, num_transit
                     output_type=output_type, use_attention=use_attention, num_attention_heads=max(heads, 1) if use_attention else 1,
                     multihead_attention_merge_type=merge,
                     attention_hidden=att_hidden, **vis_kw)
+    if vis_kw:
+        try:
+            cfg.layer_depths()
+        except ValueError as e:
+            raise IOError(f"the graph's feature-map layout cannot be built: {e}")
     if vis_kw and cfg.visual_channels() != chans:
         raise IOError(f"visual_layers {cfg.visual_layers} have {cfg.visual_channels()} channels, the compression "
                       f"layers expect {chans}")

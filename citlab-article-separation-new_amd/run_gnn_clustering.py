@@ -36,7 +36,10 @@ def build_parser():
     p.add_argument("--image_input", type=cli_flags.str2bool, default=False)
     # extension: the backbone end points a graph exported with --image_input reads its visual node features from
     # (the reference fixed them at training time with --feature_map_generation_params from_layer=[...])
-    p.add_argument("--visual_layers", type=str, nargs="*", default=None)
+    # and, for a layout with generated maps (feature_map_generators.py:72-197), their depths: --visual_layer_depths -1 32 32 with '' in
+    # --visual_layers for "from the previous map", or the reference's own spelling
+    # --feature_map_generation_params from_layer=[scale_0_unet_up_1_conv,,] layer_depth=[-1,32,32]
+    cli_flags.define_feature_map_layout(p)
     # extension: True = the scan goes to the device as decoded (uint8) and is resized there (asep_prep_resize_tf1_dev: the host resize bit
     # for bit; a colour file under load_mode=L is decoded as RGB and the kernel takes Pillow's luma).  The default stays the host resize
     # until the device path is no slower on every leg: with host workers it loses on colour scans
@@ -129,7 +132,8 @@ def _finish_page(tb, flags, output, n, page_path):
 
 def _load_session(flags, device):
     from . import gnn_io
-    graph = gnn_io.load_graph(resolve_model_path(flags), visual_layers=flags.visual_layers or None)
+    layers, depths = cli_flags.visual_layout(flags)
+    graph = gnn_io.load_graph(resolve_model_path(flags), visual_layers=layers, visual_layer_depths=depths)
     if graph.cfg.visual_dims and not flags.image_input:
         raise ValueError("this model was exported with image_input: pass --image_input True")
     from .gnn_input import check_load_mode

@@ -91,6 +91,11 @@ def gnn_tensor_shapes(cfg: GnnConfig) -> "OrderedDict[str, tuple]":
             raise ValueError("visual_layers and visual_dims must have the same length")
         for name, shp in aru_tensor_shapes(cfg.backbone_cfg()).items():   # backbone variables live in the same graph
             shapes[name] = shp
+        for gen in cfg.visual_generators():                         # feature_map_generators.py:158-192 (layers.py:234-238 per conv)
+            shapes[gen["conv1"] + "/weights"] = (1, 1, gen["cin"], gen["depth"] // 2)
+            shapes[gen["conv1"] + "/biases"] = (gen["depth"] // 2,)
+            shapes[gen["conv2"] + "/weights"] = (3, 3, gen["depth"] // 2, gen["depth"])
+            shapes[gen["conv2"] + "/biases"] = (gen["depth"],)
         for i, (c, d) in enumerate(zip(cfg.visual_channels(), cfg.visual_dims)):      # misc.py:365-368
             shapes[f"visual_node_feature_compression_fm_{i}/dense/weights"] = (c, d)
             shapes[f"visual_node_feature_compression_fm_{i}/dense/bias"] = (d,)

@@ -47,7 +47,7 @@ const char* asep_version(void);
  * functions refuse a struct whose size is not the one the library was built with -- a caller written against an older or newer
  * header gets ASEP_ERR_ARG + a message instead of fields read from whatever follows its struct on the stack.
  * An added function moves the version too: a binding resolves every name it declares when it loads the library. */
-#define ASEP_ABI_VERSION 7
+#define ASEP_ABI_VERSION 8
 int asep_abi_version(void);
 /* ABI 6: the environment switches this build of the library reads when a model is loaded (one name per line).
  * Anything else in the environment is not a switch: a caller that records the switches a measurement ran under (bench.py) filters
@@ -225,6 +225,22 @@ double asep_gnn_flops(const asep_gnn* g, int N, int E_corrected, int R);
  * The backbone may be loaded with compute_dtype 1 (bf16, BASELINE configs[4]): the ROI kernel then reads its bf16 end points;
  * compression layers, graph and classifier stay fp32. */
 int asep_gnn_attach_backbone(asep_gnn* g, asep_aru* backbone, int n_maps, const char* const* endpoint_names);
+
+/* ABI 8: the same with the whole `feature_map_generation_params` layout (feature_map_generators.py:72-197): layer_depths[i] is the
+ * `layer_depth` of map i (NULL = all -1 = asep_gnn_attach_backbone).  -1: the end point endpoint_names[i] itself.  d > 0 with a name: that end
+ * point through a 1x1 convolution to d/2 channels and a 3x3 convolution to d channels, stride 1.  d > 0 with the EMPTY name "": the same two
+ * convolutions over map i - 1, the 3x3 at stride 2 (TensorFlow's SAME: ceil(n/2) cells, an even side pads 0 in front and 1 behind).  All
+ * convolutions have a bias and a ReLU; fp32 operands and accumulation.  Their variables come from the GNN's weight blob under the reference's
+ * names, <base>_1_Conv2d_<i>_1x1_<d/2>.0/{weights,biases} and <base>_2_Conv2d_<i>_3x3_s2_<d>/{weights,biases}, <base> being the last name
+ * with depth -1 in front of map i ("" before any).  Refused with the reason: "" in position 0, "" with depth -1, an odd or non-positive depth,
+ * a depth above 256.  The generated maps live in the handle (sized at the first forward of a page size, freed by the next attach); the
+ * compression layer of a generated map is [d, layer_compressed_dim]. */
+int asep_gnn_attach_backbone_maps(asep_gnn* g, asep_aru* backbone, int n_maps, const char* const* endpoint_names,
+                                  const int32_t* layer_depths);
+
+/* Feature map `index` of the last asep_gnn_forward_visual* as fp32 [fh, fw, C] (a batch call: of its last page), generated or not; a
+ * bf16 end point is widened.  dims receives {fh, fw, C}; out == NULL asks for the sizes only.  Waits for the forward's stream (tests). */
+int asep_gnn_get_feature_map(asep_gnn* g, int index, float* out, size_t max_floats, int32_t dims[3]);
 
 /* run_gnn_clustering.py:259-269 with the image feeds: node_feat [N, node_feature_dim - visual dims],
  * image float32 [h,w] -- [h,w,3] in R, G, B order when the attached backbone reads three channels (a net trained with load_mode=RGB,
