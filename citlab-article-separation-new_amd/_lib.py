@@ -16,7 +16,7 @@ class AsepError(RuntimeError):
 
 
 MLP_MAX_HIDDEN = 4       # GNN_MLP_MAX (csrc/gnn_kernels.h): hidden layers of the interaction / attention / classifier MLPs
-ABI_VERSION = 8          # ASEP_ABI_VERSION of include/asep_hip.h this table was written against
+ABI_VERSION = 9          # ASEP_ABI_VERSION of include/asep_hip.h this table was written against
 
 
 class _SizedCfg(C.Structure):
@@ -62,6 +62,11 @@ class GnnPage(C.Structure):
                 ("d_edge_regions", C.c_void_p), ("d_edge_num_points", C.c_void_p), ("d_relations", C.c_void_p), ("d_probs_out", C.c_void_p)]
 
 
+class GnnPageU8(C.Structure):
+    """asep_gnn_page_u8: a page of asep_gnn_forward_visual_batch_u8_dev, fed with the uint8 scan [src_h, src_w, src_c]"""
+    _fields_ = [("page", GnnPage), ("d_scan", C.c_void_p), ("src_h", C.c_int32), ("src_w", C.c_int32), ("src_c", C.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/asep_hip.h one to one
 _P = C.c_void_p
 SIGNATURES = {
@@ -101,6 +106,11 @@ SIGNATURES = {
     "asep_gnn_forward_visual_dev": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P,
                                               C.c_int, _P, _P, _P]),
     "asep_gnn_forward_visual_batch_dev": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "asep_gnn_forward_visual_batch_dev2": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, _P]),
+    "asep_gnn_forward_visual_batch_u8_dev": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, _P]),
+    "asep_gnn_get_page_node_features": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
+    "asep_gnn_get_page_feature_map": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_int32)]),
+    "asep_gnn_get_page_image": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_int32)]),
     "asep_gnn_step_mode": (C.c_int, [_P]),
     "asep_gnn_get_node_features": (C.c_int, [_P, _P, C.c_size_t]),
     "asep_post_create": (_P, []),

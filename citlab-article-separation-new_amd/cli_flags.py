@@ -143,3 +143,14 @@ def update_params(class_params, flag_params, name=""):
             logging.critical("Given {0}_params-key '{1}' is not used by {0}-class!".format(name, k))
     class_params.update(flag_params)
     return class_params
+
+
+def pages_per_call(text):
+    """argparse type of ``--pages_per_call`` (run_gnn_clustering, lav_rel): pages of one engine call, at least 1 (= page by page)"""
+    try:
+        n = int(text)
+    except (TypeError, ValueError):
+        raise argparse.ArgumentTypeError(f"--pages_per_call takes a whole number of pages, got {text!r}")
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"--pages_per_call {n}: a call takes at least one page (1 = page by page, the default)")
+    return n

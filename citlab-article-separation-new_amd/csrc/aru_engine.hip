@@ -101,6 +101,7 @@ struct asep_aru {
     float* d_logit_b = nullptr;
     float* d_logit_wd = nullptr;     // two classes: [16][feat_root] class-1 minus class-0 filter + the bias difference (combine_kernel behind a soft-max)
     float* d_stats = nullptr;      // mvn {mean, 1/std}
+    const float* const* page_stats = nullptr;   // aru_set_page_stats: per page of the next forward its {mean, 1/std}, computed by the caller
     double* d_sums = nullptr;
     // A lane = one in-order chain of launches (stream + its buffer pool + a side stream for the attention branch).
     // A batch of pages is split over the lanes so that two independent chains fill each other's launch tails.
@@ -1413,7 +1414,9 @@ int forward_impl(asep_aru* m, asep_aru::Lane& L, int page0, int B, const float* 
             img.H = Hs[b]; img.W = Ws[b]; img.C = cfg.channels;            // (pages of a call may differ in size: every launch carries per-problem dims)
             level0.push_back(img);
             const float* st = nullptr;
-            if (cfg.mvn) {
+            if (cfg.mvn && m->page_stats) {                               // computed for all pages of the call in front of it (aru_moments_pages)
+                st = m->page_stats[page0 + b];
+            } else if (cfg.mvn) {
                 const int nparts = grid_1d((img.count() + 3) / 4);        // 16-byte loads: a thread takes four values per step
                 double* sums = (double*)L.pool.get(2 * (size_t)nparts * sizeof(double));
                 float* stt = (float*)L.pool.get(2 * sizeof(float));
@@ -1608,6 +1611,23 @@ int aru_endpoint_channels(const asep_aru* m, const char* name) {
     return m->cfg.feat_root << l;
 }
 
+void aru_prof_stream(asep_aru* m, hipStream_t st) { if (m) m->stream = st; }
+void aru_set_page_stats(asep_aru* m, const float* const* stats) { if (m) m->page_stats = stats; }
+bool aru_mvn(const asep_aru* m) { return m && m->cfg.mvn; }
+int aru_moments_pages(asep_aru* m, const MomentsPage* d_pages, const int32_t* d_begin, int n, int grid, hipStream_t st) {
+    if (!m || n < 1 || grid < 1) { set_error("aru_moments_pages: bad argument"); return ASEP_ERR_ARG; }
+    m->stream = st;
+    {
+        ProfScope ps(m, "moments_pages_kernel", 0.0, std::to_string(n) + " pages");
+        hipLaunchKernelGGL(moments_pages_kernel, dim3((unsigned)grid), dim3(256), 0, st, d_pages, d_begin, n);
+    }
+    {
+        ProfScope ps(m, "moments_finish_pages_kernel", 0.0, std::to_string(n) + " pages");
+        hipLaunchKernelGGL(moments_finish_pages_kernel, dim3((unsigned)n), dim3(256), 0, st, d_pages);
+    }
+    ASEP_HIP_CHECK(hipGetLastError());
+    return ASEP_OK;
+}
 int aru_num_classes(const asep_aru* m) { return m ? m->cfg.n_classes : -1; }
 int aru_input_channels(const asep_aru* m) { return m ? m->cfg.channels : -1; }
 

@@ -1417,9 +1417,9 @@ __global__ __launch_bounds__(256) void att_head_kernel(const AttHeadArgs a) {
 // mean / E[x^2] partial sums for per-image standardisation (double accumulation; the host side divides).  16-byte loads and four independent
 // accumulator pairs per thread: the first cut read one float per thread and iteration and ran at 1 TB/s (56 us for a 3000 x 4500 page, once per
 // page and step: 2.5 % of the bf16 step).
-__global__ __launch_bounds__(256) void moments_kernel(const float* __restrict__ x, size_t n, double* __restrict__ sums) {
+__device__ __forceinline__ void moments_body(const float* __restrict__ x, size_t n, double* __restrict__ sums, const unsigned bx, const unsigned gx) {
     double s = 0.0, s2 = 0.0;
-    const size_t t0 = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    const size_t t0 = (size_t)bx * 256 + threadIdx.x, stride = (size_t)gx * 256;
     if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {
         const f32x4* __restrict__ x4 = reinterpret_cast<const f32x4*>(x);
         const size_t n4 = n >> 2;
@@ -1453,13 +1453,16 @@ __global__ __launch_bounds__(256) void moments_kernel(const float* __restrict__ 
     // one partial pair per block, summed in a fixed order by moments_finish_kernel (first cut: two fp64 atomicAdds per block on ONE address --
     // 4096 serialised L2 atomics per page -- and a memset launch in front of them)
     if (threadIdx.x == 0) {
-        sums[2 * blockIdx.x] = sh[0][0];
-        sums[2 * blockIdx.x + 1] = sh[1][0];
+        sums[2 * bx] = sh[0][0];
+        sums[2 * bx + 1] = sh[1][0];
     }
+}
+__global__ __launch_bounds__(256) void moments_kernel(const float* __restrict__ x, size_t n, double* __restrict__ sums) {
+    moments_body(x, n, sums, blockIdx.x, gridDim.x);
 }
 
 // one block of 256 threads: partial pairs [nparts][2] -> {mean, 1 / max(sd, 1e-4)}
-__global__ __launch_bounds__(256) void moments_finish_kernel(const double* __restrict__ parts, int nparts, size_t n, float* __restrict__ stats) {
+__device__ __forceinline__ void moments_finish_body(const double* __restrict__ parts, int nparts, size_t n, float* __restrict__ stats) {
     double s = 0.0, s2 = 0.0;
     for (int i = threadIdx.x; i < nparts; i += 256) { s += parts[2 * i]; s2 += parts[2 * i + 1]; }
     __shared__ double sh[2][256];
@@ -1481,6 +1484,21 @@ __global__ __launch_bounds__(256) void moments_finish_kernel(const double* __res
         stats[0] = (float)mean;
         stats[1] = 1.0f / sd;
     }
+}
+__global__ __launch_bounds__(256) void moments_finish_kernel(const double* __restrict__ parts, int nparts, size_t n, float* __restrict__ stats) {
+    moments_finish_body(parts, nparts, n, stats);
+}
+// The same two steps for the pages of a relation net call, of any sizes, in one launch each: a page table in device memory (launch_plan.h:
+// page b owns the blocks begin[b] .. begin[b + 1] - 1, as many as the single-page launcher gives a page of its size); the bodies above with the
+// page's own block number and block count: the same partial sums, added in the same order
+__global__ __launch_bounds__(256) void moments_pages_kernel(const MomentsPage* __restrict__ pages, const int32_t* __restrict__ begin, int n) {
+    const int pg = page_of_unit(begin, n, (int)blockIdx.x);
+    const MomentsPage q = pages[pg];
+    moments_body(q.x, q.n, q.sums, blockIdx.x - (unsigned)begin[pg], (unsigned)q.parts);
+}
+__global__ __launch_bounds__(256) void moments_finish_pages_kernel(const MomentsPage* __restrict__ pages) {
+    const MomentsPage q = pages[blockIdx.x];
+    moments_finish_body(q.sums, q.parts, q.n, q.stats);
 }
 
 // ------------------------------------------------------------------------------------------------

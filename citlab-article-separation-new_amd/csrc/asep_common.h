@@ -124,6 +124,17 @@ int aru_input_channels(const asep_aru* m);
 // nullptr while nothing is recorded, end takes that too.  `name` as rocprofv3 prints the kernel, `detail` the layer text of mode 2.
 void* aru_prof_begin(asep_aru* m, const char* name, const char* detail, double flops, double bytes);
 void aru_prof_end(void* scope);
+// The per-image moments of n pages in two launches over a page table in device memory (launch_plan.h MomentsPage; grid = begin[n]), recorded
+// in the model's launch profile; and the statistics a following forward of `m` reads instead of computing its own: stats[b] = page b's
+// {mean, 1 / sd} in device memory, nullptr = back to the model's own (aru_engine.hip).
+struct MomentsPage;
+struct ResizePage;
+int aru_moments_pages(asep_aru* m, const MomentsPage* d_pages, const int32_t* d_begin, int n, int grid, hipStream_t st);
+void aru_set_page_stats(asep_aru* m, const float* const* stats);
+void aru_prof_stream(asep_aru* m, hipStream_t st);      // the stream aru_prof_begin records on, for launches queued IN FRONT of a forward
+bool aru_mvn(const asep_aru* m);
+// The TF1 bilinear resize of n uint8 scans in one launch over a page table in device memory (post_engine.hip: compiled without contraction)
+int resize_tf1_pages_launch(const ResizePage* d_pages, const int32_t* d_begin, int n, int grid, hipStream_t st);
 // Stream and buffer pool of an asep_post handle (post_engine.hip), for the entry points of other translation units that run
 // on that handle (textblock_engine.hip).
 hipStream_t post_stream(asep_post* p);

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "launch_plan.h"
+
 namespace asep {
 
 struct FmapConvArgs {
@@ -27,9 +29,9 @@ struct FmapConvArgs {
 
 // out[p][m] = relu(b[m] + sum_c in[p][c] W[c][m])
 template <bool BF>
-__global__ void __launch_bounds__(256) fmap_conv1x1_kernel(const FmapConvArgs a) {
+__device__ __forceinline__ void fmap_conv1x1_body(const FmapConvArgs& a, const unsigned blk) {
     const size_t total = (size_t)a.ih * a.iw * a.Co;
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t i = (size_t)blk * 256 + threadIdx.x;
     if (i >= total) return;
     const size_t p = i / a.Co;
     const int m = (int)(i - p * a.Co);
@@ -45,10 +47,13 @@ __global__ void __launch_bounds__(256) fmap_conv1x1_kernel(const FmapConvArgs a)
     a.out[i] = fmaxf(acc, 0.f);
 }
 
+template <bool BF>
+__global__ void __launch_bounds__(256) fmap_conv1x1_kernel(const FmapConvArgs a) { fmap_conv1x1_body<BF>(a, blockIdx.x); }
+
 // out[oy][ox][m] = relu(b[m] + sum_{ky,kx,c} in[oy s - pad_t + ky][ox s - pad_l + kx][c] W[ky][kx][c][m]), taps outside the map are zeros
-__global__ void __launch_bounds__(256) fmap_conv3x3_kernel(const FmapConvArgs a) {
+__device__ __forceinline__ void fmap_conv3x3_body(const FmapConvArgs& a, const unsigned blk) {
     const size_t total = (size_t)a.oh * a.ow * a.Co;
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t i = (size_t)blk * 256 + threadIdx.x;
     if (i >= total) return;
     const size_t p = i / a.Co;
     const int m = (int)(i - p * a.Co);
@@ -67,6 +72,42 @@ __global__ void __launch_bounds__(256) fmap_conv3x3_kernel(const FmapConvArgs a)
         }
     }
     a.out[i] = fmaxf(acc, 0.f);
+}
+__global__ void __launch_bounds__(256) fmap_conv3x3_kernel(const FmapConvArgs a) { fmap_conv3x3_body(a, blockIdx.x); }
+
+// ---- the same two convolutions over the pages of a batch call in ONE launch each, the pages' maps of any sizes: a page table in device memory
+//      (launch_plan.h: page b owns the blocks begin[b] .. begin[b + 1] - 1 of 256 outputs each).  A block looks its page up and runs the body
+//      above on that page's map with its own block number: the same sum, in the same order, per output value ----
+struct FmapPage {
+    const void* in;           // this page's input map
+    float* out;               // and its output
+    int ih, iw, oh, ow;
+    int pad_t, pad_l;         // 3x3 only
+};
+struct FmapPagesArgs {
+    const FmapPage* pages;    // [n_pages], device memory
+    const int32_t* begin;     // [n_pages + 1], device memory
+    int n_pages;
+    const float* W;
+    const float* b;
+    int Ci, Co, stride;
+};
+__device__ __forceinline__ FmapConvArgs fmap_page_args(const FmapPagesArgs& t, const int pg) {
+    const FmapPage q = t.pages[pg];
+    FmapConvArgs a;
+    a.in = q.in; a.W = t.W; a.b = t.b; a.out = q.out;
+    a.ih = q.ih; a.iw = q.iw; a.Ci = t.Ci; a.Co = t.Co; a.oh = q.oh; a.ow = q.ow;
+    a.stride = t.stride; a.pad_t = q.pad_t; a.pad_l = q.pad_l;
+    return a;
+}
+template <bool BF>
+__global__ void __launch_bounds__(256) fmap_conv1x1_pages_kernel(const FmapPagesArgs t) {
+    const int pg = page_of_unit(t.begin, t.n_pages, (int)blockIdx.x);
+    fmap_conv1x1_body<BF>(fmap_page_args(t, pg), blockIdx.x - (unsigned)t.begin[pg]);
+}
+__global__ void __launch_bounds__(256) fmap_conv3x3_pages_kernel(const FmapPagesArgs t) {
+    const int pg = page_of_unit(t.begin, t.n_pages, (int)blockIdx.x);
+    fmap_conv3x3_body(fmap_page_args(t, pg), blockIdx.x - (unsigned)t.begin[pg]);
 }
 
 }  // namespace asep

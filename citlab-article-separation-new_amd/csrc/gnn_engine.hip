@@ -79,6 +79,19 @@ struct asep_gnn {
     BufferPool fmap_pool;                            // intermediates and generated maps of the last page (sized at its first forward)
     std::vector<FmapRef> fmap_last;                  // every map of the last page, generated or not (asep_gnn_get_feature_map)
     std::string fmap_last_prefix;
+    // asep_gnn_forward_visual_batch_dev2: the page tables of a call in device memory.  A ring of page-locked host buffers with their device
+    // copies: a call fills the next two slots (the tables in front of the backbone, the tables behind it), copies them on the call's stream
+    // (asynchronous, no host wait) and records the slot's event behind the last kernel that reads the table; a slot is refilled only once that
+    // event -- four calls back -- has passed.  Buffers grow and are kept.  Like the handle's arenas the ring assumes that the calls of a handle
+    // go to one stream, or that the caller orders them.
+    struct TableSlot { char* h = nullptr; char* d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; };
+    TableSlot tab_ring[8];
+    unsigned tab_next = 0;
+    // what the asep_gnn_get_page_* functions read: per page of the last dev2 call its node count, its rows of d_u_cat and its maps
+    struct PageRec { int N = 0; size_t u_off = 0; std::vector<FmapRef> maps; };
+    std::vector<PageRec> batch_pages;
+    unsigned long long fwd_serial = 0, batch_serial = ~0ull;   // forwards queued so far / the count right after the last dev2 call
+    std::vector<FmapRef> batch_images;               // the resized images of the last u8 call ([h, w, C] fp32)
     float* Wout = nullptr;                           // output_type 1: GraphLSTM1/dense/weights [Uin, H]
     AttHeadW att_w[GNN_MAX_HEADS] = {};              // attention_heads > 0: per-head interaction + attention MLPs
     AttHeadW* d_att_w = nullptr;                     // the same in device memory (kernel argument of gnn_msg_att_kernel)
@@ -125,6 +138,11 @@ struct asep_gnn {
     }
     ~asep_gnn() {
         free_visual();
+        for (TableSlot& t : tab_ring) {
+            if (t.done) (void)hipEventDestroy(t.done);
+            if (t.h) (void)hipHostFree(t.h);
+            if (t.d) (void)hipFree(t.d);
+        }
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (d_u_cat) (void)hipFree(d_u_cat);
         if (d_ef_cat) (void)hipFree(d_ef_cat);
@@ -341,6 +359,7 @@ int forward_impl(asep_gnn* g, BufferPool& pool, int N, int E, const int32_t* d_e
     if ((size_t)N * N > (size_t)1 << 30) { set_error("asep_gnn_forward: N=%d too large for the dense edge table", N); return ASEP_ERR_UNSUPPORTED; }
     g->stream = s;
     g->N = N;
+    ++g->fwd_serial;
     pool.begin();
     EdgeBufs eb{};
     int rc = correct_edges_dev(g, pool, N, E, d_edges, eb, s);
@@ -612,12 +631,6 @@ int forward_batch_impl(asep_gnn* g, BufferPool& pool, int n, GraphCtx* cx, hipSt
     return ASEP_OK;
 }
 #endif
-
-// TensorFlow's SAME rule along one axis for a 3-tap filter: output size and the padding in front (the smaller half)
-inline void same_pad3(int n, int stride, int* out, int* before) {
-    *out = (n + stride - 1) / stride;
-    *before = std::max((*out - 1) * stride + 3 - n, 0) / 2;
-}
 
 // feature_map_generators.py:140-194 for the page whose backbone end points are "<prefix><name>" of the forward queued on s: every generated
 // map into the handle's arena (two launches each, fmap_kernels.h), every map's address into g->fmap_last.  A layout without generated
@@ -1318,6 +1331,467 @@ int asep_gnn_forward_visual_batch_dev(asep_gnn* g, int n_pages, const asep_gnn_p
         g->stream = s;                                       // everything the lanes queued is ordered in front of what follows on s
     }
     return ASEP_OK;
+    ASEP_GUARD_END
+}
+
+}  // extern "C"
+
+namespace {
+
+// one blob of tables, built on the host and copied once: add() returns the offset of a 16-byte aligned section
+struct TableBlob {
+    std::vector<char> bytes;
+    template <class T>
+    size_t add(const T* src, size_t n) {
+        const size_t off = (bytes.size() + 15) & ~(size_t)15;
+        bytes.resize(off + n * sizeof(T));
+        if (n) memcpy(bytes.data() + off, src, n * sizeof(T));
+        return off;
+    }
+};
+
+// the blob into the next slot of the handle's ring, copied on s; returns the slot: its device address, and its event, which the caller records
+// behind the last launch that reads the table (tables_read)
+int put_tables(asep_gnn* g, const TableBlob& blob, hipStream_t s, asep_gnn::TableSlot** slot) {
+    asep_gnn::TableSlot& t = g->tab_ring[g->tab_next++ % 8];
+    if (!t.done) ASEP_HIP_CHECK(hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
+    else ASEP_HIP_CHECK(hipEventSynchronize(t.done));              // (the readers of four calls back: long done unless the caller runs that far ahead)
+    const size_t need = std::max<size_t>(blob.bytes.size(), 16);
+    if (t.cap < need) {
+        const size_t cap = std::max(need, 2 * t.cap);
+        if (t.h) (void)hipHostFree(t.h);
+        if (t.d) (void)hipFree(t.d);
+        t.h = nullptr; t.d = nullptr; t.cap = 0;
+        ASEP_HIP_CHECK(hipHostMalloc((void**)&t.h, cap, hipHostMallocDefault));
+        ASEP_HIP_CHECK(hipMalloc((void**)&t.d, cap));
+        t.cap = cap;
+    }
+    if (!blob.bytes.empty()) memcpy(t.h, blob.bytes.data(), blob.bytes.size());
+    ASEP_HIP_CHECK(hipMemcpyAsync(t.d, t.h, need, hipMemcpyHostToDevice, s));
+    ASEP_HIP_CHECK(hipEventRecord(t.done, s));                     // (at least the copy; tables_read moves it behind the readers)
+    *slot = &t;
+    return ASEP_OK;
+}
+int tables_read(asep_gnn::TableSlot* t, hipStream_t s) {
+    ASEP_HIP_CHECK(hipEventRecord(t->done, s));
+    return ASEP_OK;
+}
+
+struct ScanIn { const uint8_t* d_scan; int H, W, C; };
+
+int visual_batch2_impl(asep_gnn* g, const char* fn, int n_pages, std::vector<asep_gnn_page>& pages, const ScanIn* scans, const int32_t* h,
+                       const int32_t* w, int P, hipStream_t s);
+
+}  // namespace
+
+extern "C" {
+
+// ABI 9: asep_gnn_forward_visual_batch_dev for pages of DIFFERENT image sizes.  One launch per call, over a page table in device memory, for:
+// the resize of uint8 scans (the u8 entry), the per-image moments of the backbone's standardisation, the two convolutions of each generated
+// map, ROI max + compression of all node and interaction regions.  The backbones run as one grouped forward over the page list
+// (asep_aru_forward_batch_dev2's launches), the graphs page by page as before.  The kernels' bodies are the single-page ones.
+namespace {
+int batch2_head_checks(asep_gnn* g, const char* fn, int n_pages, const void* pages, const int32_t* h, const int32_t* w) {
+    if (!g || !g->backbone) { set_error("%s: no backbone attached", fn); return ASEP_ERR_ARG; }
+    if (n_pages < 1) { set_error("%s: n_pages = %d, at least one page is needed", fn, n_pages); return ASEP_ERR_ARG; }
+    if (!pages) { set_error("%s: pages is NULL", fn); return ASEP_ERR_ARG; }
+    if (!h || !w) { set_error("%s: the size array %s is NULL (page 0 and every other page need h[b] x w[b])", fn, !h ? "h" : "w"); return ASEP_ERR_ARG; }
+    return ASEP_OK;
+}
+}  // namespace
+
+int asep_gnn_forward_visual_batch_dev2(asep_gnn* g, int n_pages, const asep_gnn_page* pages, const int32_t* h, const int32_t* w, int P,
+                                       void* stream) {
+    ASEP_GUARD_BEGIN
+    const char* fn = "asep_gnn_forward_visual_batch_dev2";
+    if (int rc = batch2_head_checks(g, fn, n_pages, pages, h, w)) return rc;
+    std::vector<asep_gnn_page> pg(pages, pages + n_pages);
+    return visual_batch2_impl(g, fn, n_pages, pg, nullptr, h, w, P, (hipStream_t)stream);
+    ASEP_GUARD_END
+}
+
+int asep_gnn_forward_visual_batch_u8_dev(asep_gnn* g, int n_pages, const asep_gnn_page_u8* pages, const int32_t* h, const int32_t* w, int P,
+                                         void* stream) {
+    ASEP_GUARD_BEGIN
+    const char* fn = "asep_gnn_forward_visual_batch_u8_dev";
+    if (int rc = batch2_head_checks(g, fn, n_pages, pages, h, w)) return rc;
+    std::vector<asep_gnn_page> pg(n_pages);
+    std::vector<ScanIn> scans(n_pages);
+    for (int b = 0; b < n_pages; ++b) {
+        pg[b] = pages[b].page;
+        scans[b] = ScanIn{pages[b].d_scan, pages[b].src_h, pages[b].src_w, pages[b].src_c};
+    }
+    return visual_batch2_impl(g, fn, n_pages, pg, scans.data(), h, w, P, (hipStream_t)stream);
+    ASEP_GUARD_END
+}
+
+}  // extern "C"
+
+namespace {
+
+int visual_batch2_impl(asep_gnn* g, const char* fn, int n_pages, std::vector<asep_gnn_page>& pages, const ScanIn* scans, const int32_t* h,
+                       const int32_t* w, int P, hipStream_t s) {
+    if (P < 1) { set_error("%s: P = %d region points", fn, P); return ASEP_ERR_ARG; }
+    const int ug = g->Uin - g->vis_total, U = g->Uin, Ed = g->Ed;
+    const int ncls = std::max(1, aru_num_classes(g->backbone)), chans = std::max(1, aru_input_channels(g->backbone));
+    const size_t n_maps = g->vis_names.size();
+    std::vector<size_t> logit_items(n_pages);
+    size_t nu = 0, nef = 0;
+    for (int b = 0; b < n_pages; ++b) {
+        const asep_gnn_page& q = pages[b];
+        if (h[b] < 1 || w[b] < 1) { set_error("%s: page %d has the size %d x %d, both sides must be positive", fn, b, h[b], w[b]); return ASEP_ERR_ARG; }
+        if (scans) {
+            const ScanIn& sc = scans[b];
+            if (!sc.d_scan || sc.H < 1 || sc.W < 1 || (size_t)sc.H * sc.W > 0x7fffffffull || (size_t)h[b] * w[b] > 0x7fffffffull) {
+                set_error("%s: page %d: the scan is NULL or its size %d x %d (target %d x %d) is not served", fn, b, sc.H, sc.W, h[b], w[b]);
+                return ASEP_ERR_ARG;
+            }
+            if (!(sc.C == chans || (sc.C == 3 && chans == 1))) {   // 3 -> 1 is Pillow's luma per tap; 1 -> 3 has no meaning
+                set_error("%s: page %d: the scan has %d image channel(s), the backbone takes %d", fn, b, sc.C, chans);
+                return ASEP_ERR_ARG;
+            }
+        }
+        if (q.N < 1 || q.E < 0 || q.R < 0 || (!scans && !q.d_image) || !q.d_regions || !q.d_num_points || (ug > 0 && !q.d_node_feat) || (q.E > 0 && !q.d_edges) ||
+            (q.R > 0 && !q.d_probs_out) || (g->Ed_fed > 0 && q.E > 0 && !q.d_edge_feat) ||
+            (g->vise_total > 0 && q.E > 0 && (!q.d_edge_regions || !q.d_edge_num_points))) {
+            set_error("%s: bad argument in page %d", fn, b);
+            return ASEP_ERR_ARG;
+        }
+        if ((size_t)q.N * q.N > (size_t)1 << 30) { set_error("%s: page %d: N=%d too large for the dense edge table", fn, b, q.N); return ASEP_ERR_UNSUPPORTED; }
+        logit_items[b] = (size_t)h[b] * w[b] * ncls;
+        nu += (size_t)q.N * U;
+        if (g->vise_total > 0) nef += (size_t)q.E * Ed;
+    }
+    // arenas: ONE buffer each for the pages' logits, node features, edge features and generated maps, carved per page.  Each keeps the largest
+    // sum it has served, so a call whose page mix changes allocates only when its sum is a new maximum
+    std::vector<size_t> off;
+    const size_t logit_total = arena_offsets(logit_items.data(), n_pages, 64, off);
+    g->vis_pool.begin();
+    float* d_logits = (float*)g->vis_pool.get(logit_total * sizeof(float));
+    // (the same three requests in the same order whatever the call needs, so that a buffer keeps its role from call to call)
+    const bool mvn = aru_mvn(g->backbone);
+    std::vector<size_t> img_items(n_pages), img_off, mom_items(n_pages), mom_off;
+    for (int b = 0; b < n_pages; ++b) {
+        img_items[b] = (size_t)h[b] * w[b] * chans;
+        mom_items[b] = 2 * (size_t)moments_parts(img_items[b]) + 2;          // doubles: the partial pairs, then room for {mean, 1 / sd}
+    }
+    const size_t img_total = scans ? arena_offsets(img_items.data(), n_pages, 64, img_off) : 0;
+    const size_t mom_total = mvn ? arena_offsets(mom_items.data(), n_pages, 2, mom_off) : 0;
+    float* d_images = (float*)g->vis_pool.get(img_total * sizeof(float));
+    double* d_mom = (double*)g->vis_pool.get(mom_total * sizeof(double));
+    g->batch_images.clear();
+    if (scans)
+        for (int b = 0; b < n_pages; ++b) {
+            pages[b].d_image = d_images + img_off[b];
+            g->batch_images.push_back(asep_gnn::FmapRef{pages[b].d_image, h[b], w[b], chans, 0});
+        }
+    std::vector<const float*> imgs(n_pages);
+    std::vector<float*> outs(n_pages);
+    for (int b = 0; b < n_pages; ++b) { imgs[b] = pages[b].d_image; outs[b] = d_logits + off[b]; }
+    int rc = reserve_u_cat(g, nu);
+    if (!rc && nef) rc = reserve_ef_cat(g, nef);
+    if (rc) return rc;
+    g->stream = s;
+    aru_prof_stream(g->backbone, s);
+    // ---- in front of the backbone: the scans' resize and the pages' moments, one launch per call each ----
+    std::vector<const float*> stats(n_pages, nullptr);
+    if (scans || mvn) {
+        TableBlob pre;
+        size_t r_pages = 0, r_begin = 0, m_pages = 0, m_begin = 0;
+        std::vector<int32_t> rb, mb;
+        if (scans) {
+            std::vector<ResizePage> rp(n_pages);
+            std::vector<size_t> px(n_pages);
+            for (int b = 0; b < n_pages; ++b) {
+                rp[b] = resize_page(scans[b].d_scan, scans[b].H, scans[b].W, scans[b].C, scans[b].C != chans, h[b], w[b], const_cast<float*>(pages[b].d_image));
+                px[b] = (size_t)h[b] * w[b];
+            }
+            if (!page_unit_table(px.data(), n_pages, 256, rb)) { set_error("%s: the %d pages are too large for one resize launch", fn, n_pages); return ASEP_ERR_UNSUPPORTED; }
+            r_pages = pre.add(rp.data(), rp.size()); r_begin = pre.add(rb.data(), rb.size());
+        }
+        if (mvn) {
+            std::vector<MomentsPage> mp(n_pages);
+            std::vector<size_t> parts(n_pages);
+            for (int b = 0; b < n_pages; ++b) {
+                double* base = d_mom + mom_off[b];
+                mp[b] = MomentsPage{pages[b].d_image, img_items[b], base, (float*)(base + mom_items[b] - 2), moments_parts(img_items[b])};
+                parts[b] = (size_t)mp[b].parts;
+                stats[b] = mp[b].stats;
+            }
+            if (!page_unit_table(parts.data(), n_pages, 1, mb)) { set_error("%s: too many pages for one moments launch", fn); return ASEP_ERR_UNSUPPORTED; }
+            m_pages = pre.add(mp.data(), mp.size()); m_begin = pre.add(mb.data(), mb.size());
+        }
+        asep_gnn::TableSlot* slot = nullptr;
+        rc = put_tables(g, pre, s, &slot);
+        if (rc) return rc;
+        if (scans) {
+            void* ps = aru_prof_begin(g->backbone, "prep_resize_tf1_pages_kernel", (std::to_string(n_pages) + " pages").c_str(), 0.0, 0.0);
+            rc = resize_tf1_pages_launch((const ResizePage*)(slot->d + r_pages), (const int32_t*)(slot->d + r_begin), n_pages, rb[n_pages], s);
+            aru_prof_end(ps);
+            if (rc) return rc;
+        }
+        if (mvn) {
+            rc = aru_moments_pages(g->backbone, (const MomentsPage*)(slot->d + m_pages), (const int32_t*)(slot->d + m_begin), n_pages, mb[n_pages], s);
+            if (rc) return rc;
+        }
+        rc = tables_read(slot, s);
+        if (rc) return rc;
+    }
+    if (mvn) aru_set_page_stats(g->backbone, stats.data());
+    rc = asep_aru_forward_batch_dev2(g->backbone, n_pages, imgs.data(), h, w, outs.data(), nullptr, nullptr, 0.f, s);
+    aru_set_page_stats(g->backbone, nullptr);
+    if (rc) return rc;
+    g->stream = s;
+
+    // ---- every map of every page: the backbone's end points (known once the forward is queued), the generated ones in one arena ----
+    std::vector<asep_gnn::PageRec> recs(n_pages);
+    struct Gen { size_t n1 = 0, n2 = 0; FmapDims d{}; asep_gnn::FmapRef src; float* mid = nullptr; };
+    std::vector<Gen> gens((size_t)n_pages * n_maps);
+    std::vector<size_t> arena_items;                                  // per generated (page, map): the 1x1's output, then the map itself
+    for (int b = 0; b < n_pages; ++b) {
+        const std::string prefix = b ? "p" + std::to_string(b) + "/" : std::string();
+        recs[b].maps.assign(n_maps, asep_gnn::FmapRef{});
+        for (size_t i = 0; i < n_maps; ++i) {
+            const asep_gnn::FmapGen& G = g->vis_gen[i];
+            asep_gnn::FmapRef src{};
+            if (G.depth < 0 || G.stride == 1) {
+                int dims[3];
+                rc = aru_endpoint_dev(g->backbone, (prefix + g->vis_names[i]).c_str(), &src.p, dims, &src.bf);
+                if (rc) return rc;
+                src.fh = dims[0]; src.fw = dims[1]; src.C = dims[2];
+            } else {
+                src = recs[b].maps[i - 1];                          // (a generated one's address follows below)
+            }
+            if (G.depth < 0) {
+                if (src.C != g->vis_C[i]) { set_error("end point %s has %d channels, expected %d", g->vis_names[i].c_str(), src.C, g->vis_C[i]); return ASEP_ERR_ARG; }
+                recs[b].maps[i] = src;
+                continue;
+            }
+            if (src.C != G.Cin) { set_error("feature map %zu reads %d channels, its 1x1 filter was loaded for %d", i, src.C, G.Cin); return ASEP_ERR_ARG; }
+            Gen& ge = gens[(size_t)b * n_maps + i];
+            ge.src = src;
+            ge.d = fmap_dims(src.fh, src.fw, G.stride);
+            ge.n1 = (size_t)src.fh * src.fw * (G.depth / 2);
+            ge.n2 = (size_t)ge.d.oh * ge.d.ow * G.depth;
+            arena_items.push_back(ge.n1);
+            arena_items.push_back(ge.n2);
+            recs[b].maps[i] = asep_gnn::FmapRef{nullptr, ge.d.oh, ge.d.ow, G.depth, 0};
+        }
+    }
+    if (g->n_generated) {
+        std::vector<size_t> aoff;
+        const size_t total = arena_offsets(arena_items.data(), (int)arena_items.size(), 64, aoff);
+        g->fmap_pool.begin();
+        float* base = (float*)g->fmap_pool.get(total * sizeof(float));
+        size_t k = 0;
+        for (int b = 0; b < n_pages; ++b)
+            for (size_t i = 0; i < n_maps; ++i) {
+                if (g->vis_gen[i].depth < 0) continue;
+                Gen& ge = gens[(size_t)b * n_maps + i];
+                ge.mid = base + aoff[k];
+                recs[b].maps[i].p = base + aoff[k + 1];
+                if (g->vis_gen[i].stride == 2) ge.src.p = recs[b].maps[i - 1].p;
+                k += 2;
+            }
+    }
+
+    // ---- the tables: per generated map two (1x1, 3x3), then the regions' entries, fp32 maps and bf16 maps apart ----
+    TableBlob blob;
+    struct FmapLaunch { size_t pages1 = 0, begin1 = 0, pages3 = 0, begin3 = 0; int grid1 = 0, grid3 = 0; bool bf = false; double fl1 = 0, by1 = 0, fl3 = 0, by3 = 0; };
+    std::vector<FmapLaunch> fl(n_maps);
+    for (size_t i = 0; i < n_maps; ++i) {
+        const asep_gnn::FmapGen& G = g->vis_gen[i];
+        if (G.depth < 0) continue;
+        std::vector<FmapPage> p1(n_pages), p3(n_pages);
+        std::vector<size_t> it1(n_pages), it3(n_pages);
+        FmapLaunch& L = fl[i];
+        L.bf = gens[i].src.bf != 0;
+        const int half = G.depth / 2;
+        for (int b = 0; b < n_pages; ++b) {
+            const Gen& ge = gens[(size_t)b * n_maps + i];
+            if ((ge.src.bf != 0) != L.bf) { set_error("%s: end points of one call differ in precision", fn); return ASEP_ERR_ARG; }
+            p1[b] = FmapPage{ge.src.p, ge.mid, ge.d.ih, ge.d.iw, ge.d.ih, ge.d.iw, 0, 0};
+            p3[b] = FmapPage{ge.mid, const_cast<float*>(recs[b].maps[i].p), ge.d.ih, ge.d.iw, ge.d.oh, ge.d.ow, ge.d.pad_t, ge.d.pad_l};
+            it1[b] = ge.n1; it3[b] = ge.n2;
+            L.fl1 += 2.0 * (double)ge.n1 * G.Cin;
+            L.by1 += (double)ge.d.ih * ge.d.iw * G.Cin * (L.bf ? 2 : 4) + 4.0 * (double)ge.n1;
+            L.fl3 += 2.0 * (double)ge.n2 * 9 * half;
+            L.by3 += 4.0 * (double)ge.n1 + 4.0 * (double)ge.n2;
+        }
+        L.by1 += 4.0 * ((double)G.Cin * half + half);
+        L.by3 += 4.0 * (9.0 * half * G.depth + G.depth);
+        std::vector<int32_t> b1, b3;
+        if (!page_unit_table(it1.data(), n_pages, 256, b1) || !page_unit_table(it3.data(), n_pages, 256, b3)) {
+            set_error("%s: feature map %zu of the %d pages is too large for one launch", fn, i, n_pages);
+            return ASEP_ERR_UNSUPPORTED;
+        }
+        L.grid1 = b1[n_pages]; L.grid3 = b3[n_pages];
+        L.pages1 = blob.add(p1.data(), p1.size()); L.begin1 = blob.add(b1.data(), b1.size());
+        L.pages3 = blob.add(p3.data(), p3.size()); L.begin3 = blob.add(b3.data(), b3.size());
+    }
+    struct RoiLaunch { std::vector<RoiArgs> e; std::vector<size_t> rows; size_t eoff = 0, boff = 0; int grid = 0; };
+    RoiLaunch roi[2];                                               // [0] fp32 maps, [1] bf16 maps
+    {
+        size_t urow = 0, efrow = 0;
+        for (int b = 0; b < n_pages; ++b) {
+            const asep_gnn_page& q = pages[b];
+            recs[b].N = q.N; recs[b].u_off = urow * U;
+            int col = ug, ecol = g->Ed_fed;
+            for (size_t i = 0; i < n_maps; ++i) {
+                const asep_gnn::FmapRef& m = recs[b].maps[i];
+                RoiArgs a{};
+                a.fm = m.p; a.fh = m.fh; a.fw = m.fw; a.C = m.C;
+                a.regions = q.d_regions; a.P = P; a.npts = q.d_num_points; a.Wc = g->vis_W[i]; a.bc = g->vis_b[i]; a.d = g->vis_d[i];
+                a.u_out = g->d_u_cat + urow * U; a.ustride = U; a.col0 = col; a.vmax_out = nullptr;
+                roi[m.bf ? 1 : 0].e.push_back(a);
+                roi[m.bf ? 1 : 0].rows.push_back((size_t)q.N);
+                col += g->vis_d[i];
+                if (g->vise_total > 0 && q.E > 0) {
+                    RoiArgs c = a;
+                    c.regions = q.d_edge_regions; c.npts = q.d_edge_num_points; c.Wc = g->vise_W[i]; c.bc = g->vise_b[i]; c.d = g->vise_d[i];
+                    c.u_out = g->d_ef_cat + efrow * Ed; c.ustride = Ed; c.col0 = ecol;
+                    roi[m.bf ? 1 : 0].e.push_back(c);
+                    roi[m.bf ? 1 : 0].rows.push_back((size_t)q.E);
+                    ecol += g->vise_d[i];
+                }
+            }
+            urow += (size_t)q.N;
+            if (g->vise_total > 0) efrow += (size_t)q.E;
+        }
+        for (RoiLaunch& L : roi) {
+            if (L.e.empty()) continue;
+            std::vector<int32_t> bg;
+            if (!page_unit_table(L.rows.data(), (int)L.rows.size(), 1, bg)) { set_error("%s: too many regions for one launch", fn); return ASEP_ERR_UNSUPPORTED; }
+            L.grid = bg.back();
+            L.eoff = blob.add(L.e.data(), L.e.size());
+            L.boff = blob.add(bg.data(), bg.size());
+        }
+    }
+    asep_gnn::TableSlot* slot2 = nullptr;
+    rc = put_tables(g, blob, s, &slot2);
+    if (rc) return rc;
+    const char* tab = slot2->d;
+
+    // ---- launches: one per stage over all pages ----
+    for (size_t i = 0; i < n_maps; ++i) {
+        const asep_gnn::FmapGen& G = g->vis_gen[i];
+        if (G.depth < 0) continue;
+        const FmapLaunch& L = fl[i];
+        const std::string where = "fm_" + std::to_string(i) + " " + std::to_string(n_pages) + " pages";
+        FmapPagesArgs a{};
+        a.pages = (const FmapPage*)(tab + L.pages1); a.begin = (const int32_t*)(tab + L.begin1); a.n_pages = n_pages;
+        a.W = G.W1; a.b = G.b1; a.Ci = G.Cin; a.Co = G.depth / 2; a.stride = 1;
+        if (L.grid1 > 0) {
+            const std::string det = where + " " + std::to_string(G.Cin) + "->" + std::to_string(G.depth / 2);
+            void* ps = aru_prof_begin(g->backbone, L.bf ? "fmap_conv1x1_pages_kernel<true>" : "fmap_conv1x1_pages_kernel<false>", det.c_str(), L.fl1, L.by1);
+            if (L.bf) hipLaunchKernelGGL(fmap_conv1x1_pages_kernel<true>, dim3((unsigned)L.grid1), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL(fmap_conv1x1_pages_kernel<false>, dim3((unsigned)L.grid1), dim3(256), 0, s, a);
+            aru_prof_end(ps);
+        }
+        FmapPagesArgs c = a;
+        c.pages = (const FmapPage*)(tab + L.pages3); c.begin = (const int32_t*)(tab + L.begin3);
+        c.W = G.W2; c.b = G.b2; c.Ci = G.depth / 2; c.Co = G.depth; c.stride = G.stride;
+        if (L.grid3 > 0) {
+            const std::string det = where + " " + std::to_string(G.depth / 2) + "->" + std::to_string(G.depth) + " s" + std::to_string(G.stride);
+            void* ps = aru_prof_begin(g->backbone, "fmap_conv3x3_pages_kernel", det.c_str(), L.fl3, L.by3);
+            hipLaunchKernelGGL(fmap_conv3x3_pages_kernel, dim3((unsigned)L.grid3), dim3(256), 0, s, c);
+            aru_prof_end(ps);
+        }
+    }
+    for (int k = 0; k < 2; ++k) {
+        const RoiLaunch& L = roi[k];
+        if (L.grid < 1) continue;
+        RoiPagesArgs a{(const RoiArgs*)(tab + L.eoff), (const int32_t*)(tab + L.boff), (int)L.e.size()};
+        const std::string det = std::to_string(n_pages) + " pages " + std::to_string(L.e.size()) + " entries " + std::to_string(L.grid) + " regions";
+        void* ps = aru_prof_begin(g->backbone, k ? "gnn_roi_compress_pages_kernel<true>" : "gnn_roi_compress_pages_kernel<false>", det.c_str(), 0.0, 0.0);
+        if (k) hipLaunchKernelGGL(gnn_roi_compress_pages_kernel<true>, dim3((unsigned)L.grid), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(gnn_roi_compress_pages_kernel<false>, dim3((unsigned)L.grid), dim3(256), 0, s, a);
+        aru_prof_end(ps);
+    }
+    ASEP_HIP_CHECK(hipGetLastError());
+    rc = tables_read(slot2, s);
+    if (rc) return rc;
+
+    // ---- the graphs, page by page (they batch nothing across pages today: N, E and R differ) ----
+    float* d_u = g->d_u_cat;
+    float* d_efc = g->d_ef_cat;
+    for (int b = 0; b < n_pages; ++b) {
+        const asep_gnn_page& q = pages[b];
+        if (ug > 0) hipLaunchKernelGGL(gnn_copy_cols_kernel, dim3(cdiv(q.N * ug, 256)), dim3(256), 0, s, q.d_node_feat, q.N, ug, d_u, U);
+        const float* d_ef = q.d_edge_feat;
+        if (g->vise_total > 0) {
+            if (q.E > 0) {
+                if (g->Ed_fed > 0) hipLaunchKernelGGL(gnn_copy_cols_kernel, dim3(cdiv(q.E * g->Ed_fed, 256)), dim3(256), 0, s, q.d_edge_feat, q.E, g->Ed_fed, d_efc, Ed);
+                d_ef = d_efc;
+            }
+            d_efc += (size_t)q.E * Ed;
+        }
+        rc = forward_impl(g, g->pool, q.N, q.E, q.d_edges, d_u, d_ef, q.R, q.d_relations, q.d_probs_out, s);
+        if (rc) return rc;
+        d_u += (size_t)q.N * U;
+    }
+    g->fmap_last = recs[n_pages - 1].maps;                          // as after the old entry: the last page's maps
+    g->fmap_last_prefix = n_pages > 1 ? "p" + std::to_string(n_pages - 1) + "/" : std::string();
+    g->batch_pages = std::move(recs);
+    g->batch_serial = g->fwd_serial;
+    return ASEP_OK;
+}
+
+// page `page` of the handle's last call over a page table, or nullptr with the error set
+const asep_gnn::PageRec* batch_page(asep_gnn* g, const char* fn, int page) {
+    if (!g || g->batch_serial != g->fwd_serial || g->batch_pages.empty()) { set_error("%s: the handle's last forward was not a call over a page table (asep_gnn_forward_visual_batch_dev2 / _u8_dev)", fn); return nullptr; }
+    if (page < 0 || page >= (int)g->batch_pages.size()) { set_error("%s: page %d of a call of %zu pages", fn, page, g->batch_pages.size()); return nullptr; }
+    return &g->batch_pages[page];
+}
+
+int copy_map_out(asep_gnn* g, const char* fn, const asep_gnn::FmapRef& r, float* out, size_t max_floats, int32_t dims[3]) {
+    dims[0] = r.fh; dims[1] = r.fw; dims[2] = r.C;
+    const size_t n = (size_t)r.fh * r.fw * r.C;
+    if (!out) return ASEP_OK;
+    if (max_floats < n) { set_error("%s: buffer too small (%zu floats needed)", fn, n); return ASEP_ERR_ARG; }
+    ASEP_HIP_CHECK(hipStreamSynchronize(g->stream));
+    if (r.bf) {
+        std::vector<uint16_t> hb(n);
+        ASEP_HIP_CHECK(hipMemcpy(hb.data(), r.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) { const uint32_t u = (uint32_t)hb[i] << 16; memcpy(out + i, &u, 4); }
+    } else {
+        ASEP_HIP_CHECK(hipMemcpy(out, r.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return ASEP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int asep_gnn_get_page_node_features(asep_gnn* g, int page, float* out, size_t max_floats) {
+    ASEP_GUARD_BEGIN
+    const asep_gnn::PageRec* r = batch_page(g, "asep_gnn_get_page_node_features", page);
+    if (!r) return ASEP_ERR_ARG;
+    if (!out) { set_error("asep_gnn_get_page_node_features: out is NULL"); return ASEP_ERR_ARG; }
+    const size_t n = (size_t)r->N * g->Uin;
+    if (max_floats < n) { set_error("asep_gnn_get_page_node_features: buffer too small"); return ASEP_ERR_ARG; }
+    ASEP_HIP_CHECK(hipStreamSynchronize(g->stream));
+    ASEP_HIP_CHECK(hipMemcpy(out, g->d_u_cat + r->u_off, n * sizeof(float), hipMemcpyDeviceToHost));
+    return ASEP_OK;
+    ASEP_GUARD_END
+}
+
+int asep_gnn_get_page_feature_map(asep_gnn* g, int page, int index, float* out, size_t max_floats, int32_t dims[3]) {
+    ASEP_GUARD_BEGIN
+    const asep_gnn::PageRec* r = batch_page(g, "asep_gnn_get_page_feature_map", page);
+    if (!r) return ASEP_ERR_ARG;
+    if (!dims || index < 0 || index >= (int)r->maps.size()) { set_error("asep_gnn_get_page_feature_map: bad argument"); return ASEP_ERR_ARG; }
+    return copy_map_out(g, "asep_gnn_get_page_feature_map", r->maps[index], out, max_floats, dims);
+    ASEP_GUARD_END
+}
+
+int asep_gnn_get_page_image(asep_gnn* g, int page, float* out, size_t max_floats, int32_t dims[3]) {
+    ASEP_GUARD_BEGIN
+    const asep_gnn::PageRec* r = batch_page(g, "asep_gnn_get_page_image", page);
+    if (!r) return ASEP_ERR_ARG;
+    if (!dims || g->batch_images.size() != g->batch_pages.size()) { set_error("asep_gnn_get_page_image: the last call was not fed uint8 scans"); return ASEP_ERR_ARG; }
+    return copy_map_out(g, "asep_gnn_get_page_image", g->batch_images[page], out, max_floats, dims);
     ASEP_GUARD_END
 }
 

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch_plan.h"
+
 namespace asep {
 
 constexpr int GNN_H = 32;            // hidden / interaction width handled by the lane mapping
@@ -1362,6 +1364,22 @@ __device__ __forceinline__ void gnn_roi_compress_kernel_body(const RoiArgs& a, c
 }
 template <bool BF>
 __global__ __launch_bounds__(256) void gnn_roi_compress_kernel(const RoiArgs a) { gnn_roi_compress_kernel_body<BF>(a, (int)blockIdx.x, (int)gridDim.x); }
+// asep_gnn_forward_visual_batch_dev2: the regions of ALL pages of a call, of every feature map, in one launch.  An entry = one (page, map)
+// pair's RoiArgs (its map with its own size, the page's regions, the map's compression layer, the page's rows of the feature matrix);
+// the table lies in device memory, entry k owns the blocks begin[k] .. begin[k + 1] - 1, one block per region (launch_plan.h).  Node
+// and interaction regions are entries of the same table.  The body is the single-page kernel's.
+struct RoiPagesArgs {
+    const RoiArgs* e;         // [n]
+    const int32_t* begin;     // [n + 1]
+    int n;
+};
+template <bool BF>
+__global__ __launch_bounds__(256) void gnn_roi_compress_pages_kernel(const RoiPagesArgs t) {
+    const int k = page_of_unit(t.begin, t.n, (int)blockIdx.x);
+    const RoiArgs a = t.e[k];
+    const int b0 = t.begin[k];
+    gnn_roi_compress_kernel_body<BF>(a, (int)blockIdx.x - b0, t.begin[k + 1] - b0);
+}
 #ifdef ASEP_ABLATION
 template <bool BF>
 __global__ __launch_bounds__(256) void gnn_roi_compress_kernel_batch(const GnnBatch<RoiArgs> b) {

@@ -76,4 +76,71 @@ inline std::vector<int32_t> xcd_order(const std::vector<TileDims>& probs, int to
     return sched;
 }
 
+// ---- page tables of the relation net's batched visual stages (gnn_engine.hip: one launch over the pages of a call, whatever their sizes).
+//      The units of a launch (blocks of 256 outputs, or one block per region) are the pages' unit lists one behind the other: page b owns the
+//      units begin[b] .. begin[b + 1] - 1, begin[n_pages] is the grid.  A page may own no unit (an empty map, a page without interactions) ----
+
+// TensorFlow's SAME rule along one axis for a 3-tap filter: output size and the padding in front (the smaller half)
+inline void same_pad3(int n, int stride, int* out, int* before) {
+    *out = (n + stride - 1) / stride;
+    *before = std::max((*out - 1) * stride + 3 - n, 0) / 2;
+}
+
+// what the 3x3 convolution of a generated feature map (stride 1 or 2) makes of an ih x iw map
+struct FmapDims { int ih, iw, oh, ow, pad_t, pad_l; };
+inline FmapDims fmap_dims(int ih, int iw, int stride) {
+    FmapDims d{ih, iw, 0, 0, 0, 0};
+    same_pad3(ih, stride, &d.oh, &d.pad_t);
+    same_pad3(iw, stride, &d.ow, &d.pad_l);
+    return d;
+}
+
+// begin[0 .. n] for pages of items[b] items in units of per_unit items (the last unit of a page is partial when per_unit does not divide its
+// items).  False when the units do not fit one launch (a 31-bit grid): begin is then not to be used.
+inline bool page_unit_table(const size_t* items, int n, size_t per_unit, std::vector<int32_t>& begin) {
+    begin.assign((size_t)n + 1, 0);
+    uint64_t total = 0;
+    for (int b = 0; b < n; ++b) {
+        total += ((uint64_t)items[b] + per_unit - 1) / per_unit;
+        if (total > (uint64_t)INT32_MAX) return false;
+        begin[(size_t)b + 1] = (int32_t)total;
+    }
+    return true;
+}
+
+// the page that owns `unit` (0 <= unit < begin[n]): the last b with begin[b] <= unit, which skips the pages without units.  constexpr: the
+// kernels call the same function
+constexpr int page_of_unit(const int32_t* begin, int n, int unit) {
+    int lo = 0, hi = n;                       // begin[lo] <= unit < begin[hi] throughout: a binary search, log2(n) reads per block
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) / 2;
+        if (begin[mid] <= unit) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// one page of the batched TF1 bilinear resize (post_kernels.h prep_resize_tf1_pages_kernel): the uint8 scan [H, W, C] -> float32 [h, w(, C)];
+// luma: C = 3 in, one channel out.  sy, sx as the single-page launcher forms them: a double division rounded once to float32
+struct ResizePage { const uint8_t* img; float* out; int H, W, h, w; float sy, sx; int C, luma; };
+inline ResizePage resize_page(const uint8_t* img, int H, int W, int C, bool luma, int h, int w, float* out) {
+    return ResizePage{img, out, H, W, h, w, (float)((double)H / (double)h), (float)((double)W / (double)w), C, luma ? 1 : 0};
+}
+
+// one page of the batched per-image moments (aru_kernels.h moments_pages_kernel): n values at x; `parts` blocks leave their partial sums in
+// sums [parts][2]; stats receives {mean, 1 / max(sd, 1e-4)}.  moments_parts: the block count the single-page launcher uses for n values
+struct MomentsPage { const float* x; size_t n; double* sums; float* stats; int parts; };
+inline int moments_parts(size_t n) { return (int)std::min<size_t>(((n + 3) / 4 + 255) / 256, 256 * 8); }
+
+// offsets of n buffers of items[b] elements in one arena, each aligned to `align` elements; returns the arena's size in elements
+inline size_t arena_offsets(const size_t* items, int n, size_t align, std::vector<size_t>& off) {
+    off.assign((size_t)n, 0);
+    size_t total = 0;
+    for (int b = 0; b < n; ++b) {
+        off[(size_t)b] = total;
+        total += (items[b] + align - 1) / align * align;
+    }
+    return total;
+}
+
 }  // namespace asep

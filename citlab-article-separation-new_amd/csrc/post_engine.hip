@@ -320,6 +320,18 @@ int resize_tf1_check(const char* fn, const void* p, const void* img, const void*
     return ASEP_OK;
 }
 
+}  // namespace
+namespace asep {
+// asep_gnn_forward_visual_batch_u8_dev: the scans of a call in one launch; the table lies in device memory, grid = begin[n]
+int resize_tf1_pages_launch(const ResizePage* d_pages, const int32_t* d_begin, int n, int grid, hipStream_t st) {
+    if (grid < 1) return ASEP_OK;
+    prep_resize_tf1_pages_kernel<<<(unsigned)grid, 256, 0, st>>>(d_pages, d_begin, n);
+    ASEP_HIP_CHECK(hipGetLastError());
+    return ASEP_OK;
+}
+}  // namespace asep
+namespace {
+
 int resize_tf1_dev(hipStream_t st, const uint8_t* d_img, int H, int W, int C, int mode, int h, int w, float* d_out) {
     const float sy = (float)((double)H / (double)h), sx = (float)((double)W / (double)w);
     const unsigned nb = blocks_for((size_t)h * w);

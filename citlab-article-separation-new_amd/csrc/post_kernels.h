@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch_plan.h"
+
 namespace asep {
 
 // --------------------------------------------------------------------------------------------------------------
@@ -660,10 +662,10 @@ post_gray_u8_kernel(const uint8_t* __restrict__ bgr, size_t n, uint8_t* __restri
 // sy = float32(H / h), sx = float32(W / w) come from the host (a double division, rounded once).
 // --------------------------------------------------------------------------------------------------------------
 template <int C, bool LUMA>
-__global__ void __launch_bounds__(256)
-prep_resize_tf1_kernel(const uint8_t* __restrict__ img, int H, int W, float sy, float sx, float* __restrict__ out, int h, int w) {
+__device__ __forceinline__ void
+prep_resize_tf1_body(const uint8_t* __restrict__ img, int H, int W, float sy, float sx, float* __restrict__ out, int h, int w, const unsigned blk) {
 #pragma clang fp contract(off)
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;                               // (the launcher keeps h * w below 2^31)
+    const unsigned i = blk * 256u + threadIdx.x;                                      // (the launcher keeps h * w below 2^31)
     if (i >= (unsigned)h * (unsigned)w) return;
     const int y = (int)(i / (unsigned)w), x = (int)(i % (unsigned)w);
     const float ys = (float)y * sy, xs = (float)x * sx;
@@ -687,6 +689,23 @@ prep_resize_tf1_kernel(const uint8_t* __restrict__ img, int H, int W, float sy, 
             out[(size_t)i * C + c] = top * uy + bot * wy;
         }
     }
+}
+
+template <int C, bool LUMA>
+__global__ void __launch_bounds__(256)
+prep_resize_tf1_kernel(const uint8_t* __restrict__ img, int H, int W, float sy, float sx, float* __restrict__ out, int h, int w) {
+    prep_resize_tf1_body<C, LUMA>(img, H, W, sy, sx, out, h, w, blockIdx.x);
+}
+// the scans of ALL pages of a relation net call in one launch: a page table in device memory (launch_plan.h: page b owns the blocks
+// begin[b] .. begin[b + 1] - 1 of 256 output pixels), source and target sizes, channel count and mode per page; the body is the one above
+__global__ void __launch_bounds__(256)
+prep_resize_tf1_pages_kernel(const ResizePage* __restrict__ pages, const int32_t* __restrict__ begin, int n) {
+    const int pg = page_of_unit(begin, n, (int)blockIdx.x);
+    const ResizePage q = pages[pg];
+    const unsigned blk = blockIdx.x - (unsigned)begin[pg];
+    if (q.luma) prep_resize_tf1_body<3, true>(q.img, q.H, q.W, q.sy, q.sx, q.out, q.h, q.w, blk);
+    else if (q.C == 3) prep_resize_tf1_body<3, false>(q.img, q.H, q.W, q.sy, q.sx, q.out, q.h, q.w, blk);
+    else prep_resize_tf1_body<1, false>(q.img, q.H, q.W, q.sy, q.sx, q.out, q.h, q.w, blk);
 }
 
 struct PostBox { int x0, y0, x1, y1; };           // rows [y0, y1), columns [x0, x1), already clipped to the image

@@ -165,10 +165,9 @@ class GnnSession:
     def __exit__(self, *exc):
         return False
 
-    def run(self, fetches, feed_dict):
-        name = _key(fetches)
-        if name != OUTPUT_NODE:
-            raise KeyError(f"The name '{name}' refers to a Tensor which does not exist (only {OUTPUT_NODE})")
+    def page_arrays(self, feed_dict):
+        """the arrays ``run`` takes out of a feed dict, checked the same way (for :func:`run_pages`): N, E, edges, u, ef, rel, and for a
+        visual model image | page_u8 + size, regions, npts, eregions, enpts"""
         feed = {_key(k): v for k, v in feed_dict.items()}
         for k in feed:
             if k not in FEED_NAMES and k != IMAGE_U8:
@@ -181,7 +180,7 @@ class GnnSession:
             raise ValueError("batch size must be 1 (input_dataset.py:134)")
         N = int(num_nodes[0])
         E = int(np.asarray(feed["num_interacting_nodes:0"]).reshape(-1)[0])
-        edges = np.ascontiguousarray(np.asarray(feed["interacting_nodes:0"], dtype=np.int32)[0][:E])
+        a = {"N": N, "E": E, "edges": np.ascontiguousarray(np.asarray(feed["interacting_nodes:0"], dtype=np.int32)[0][:E]).reshape(-1, 2)}
         if "node_features:0" in feed:
             u = np.ascontiguousarray(np.asarray(feed["node_features:0"], dtype=np.float32)[0][:N])
         elif cfg.visual_dims and cfg.node_feature_dim == 0:
@@ -190,13 +189,15 @@ class GnnSession:
             raise KeyError("feed_dict lacks node_features:0")
         if u.shape[1] != cfg.node_feature_dim:
             raise ValueError(f"node_features has dim {u.shape[1]}, model expects {cfg.node_feature_dim}")
-        ef = None
+        a["u"] = u
+        a["ef"] = None
         if cfg.edge_feature_dim:
             ef = np.ascontiguousarray(np.asarray(feed["edge_features:0"], dtype=np.float32)[0][:E])
             if ef.shape[1] != cfg.edge_feature_dim:
                 raise ValueError(f"edge_features has dim {ef.shape[1]}, model expects {cfg.edge_feature_dim}")
-        rel = np.ascontiguousarray(
-            np.asarray(feed["relations_to_consider_belong_to_same_instance:0"], dtype=np.int32)[0])
+            a["ef"] = ef
+        a["rel"] = np.ascontiguousarray(np.asarray(feed["relations_to_consider_belong_to_same_instance:0"], dtype=np.int32)[0]).reshape(-1, 2)
+        a["eregions"] = a["enpts"] = None
         if cfg.visual_dims:
             from_scan = IMAGE_U8 in feed
             for k in ((IMAGE_U8, "image_shape:0") if from_scan else ("image:0",)) + ("visual_regions_nodes:0",
@@ -211,27 +212,112 @@ class GnnSession:
                 if image.dtype != np.uint8:
                     raise ValueError(f"{IMAGE_U8} is the scan as decoded (uint8), got {image.dtype}")
                 ish = np.asarray(feed["image_shape:0"]).reshape(-1, 3)[0]
-            elif "image_shape:0" in feed:                   # crop to the true shape (no padding at batch size 1)
-                ish = np.asarray(feed["image_shape:0"]).reshape(-1, 3)[0]
-                image = image[:int(ish[0]), :int(ish[1])]
-            regions = np.asarray(feed["visual_regions_nodes:0"], dtype=np.float32)[0][:N]
-            npts = np.asarray(feed["num_points_visual_regions_nodes:0"], dtype=np.int32)[0][:N]
-            eregions = enpts = None
+                if int(ish[0]) < 1 or int(ish[1]) < 1:
+                    raise ValueError(f"the target size must be positive, got {int(ish[0])} x {int(ish[1])}")
+                a["page_u8"], a["size"] = image, (int(ish[0]), int(ish[1]))
+            else:
+                if "image_shape:0" in feed:                 # crop to the true shape (no padding at batch size 1)
+                    ish = np.asarray(feed["image_shape:0"]).reshape(-1, 3)[0]
+                    image = image[:int(ish[0]), :int(ish[1])]
+                a["image"] = image
+            a["regions"] = np.ascontiguousarray(np.asarray(feed["visual_regions_nodes:0"], dtype=np.float32)[0][:N])
+            a["npts"] = np.ascontiguousarray(np.asarray(feed["num_points_visual_regions_nodes:0"], dtype=np.int32)[0][:N]).reshape(N)
             if cfg.visual_edges:                            # graph_relation.py:141-146
                 for k in ("visual_regions_edges:0", "num_points_visual_regions_edges:0"):
                     if k not in feed:
                         raise KeyError(f"this graph assigns visual features to edges: feed_dict lacks {k}")
-                eregions = np.asarray(feed["visual_regions_edges:0"], dtype=np.float32)[0][:E]
-                enpts = np.asarray(feed["num_points_visual_regions_edges:0"], dtype=np.int32)[0][:E]
-            if from_scan:
-                probs = gnn_forward_visual_u8(self.graph, N, edges, u, ef, image, int(ish[0]), int(ish[1]), regions, npts, rel,
-                                              self.device, edge_regions=eregions, edge_num_points=enpts)
+                a["eregions"] = np.ascontiguousarray(np.asarray(feed["visual_regions_edges:0"], dtype=np.float32)[0][:E])
+                a["enpts"] = np.ascontiguousarray(np.asarray(feed["num_points_visual_regions_edges:0"], dtype=np.int32)[0][:E]).reshape(E)
+        return a
+
+    def run(self, fetches, feed_dict):
+        name = _key(fetches)
+        if name != OUTPUT_NODE:
+            raise KeyError(f"The name '{name}' refers to a Tensor which does not exist (only {OUTPUT_NODE})")
+        a = self.page_arrays(feed_dict)                      # one parser for run and run_pages
+        cfg = self.graph.cfg
+        N, edges, u, ef, rel = a["N"], a["edges"], a["u"], a["ef"], a["rel"]
+        if cfg.visual_dims:
+            if "page_u8" in a:
+                probs = gnn_forward_visual_u8(self.graph, N, edges, u, ef, a["page_u8"], a["size"][0], a["size"][1], a["regions"], a["npts"], rel,
+                                              self.device, edge_regions=a["eregions"], edge_num_points=a["enpts"])
             else:
-                probs = gnn_forward_visual(self.graph, N, edges, u, ef, image, regions, npts, rel, self.device,
-                                           edge_regions=eregions, edge_num_points=enpts)
+                probs = gnn_forward_visual(self.graph, N, edges, u, ef, a["image"], a["regions"], a["npts"], rel, self.device,
+                                           edge_regions=a["eregions"], edge_num_points=a["enpts"])
         else:
             probs = gnn_forward(self.graph, N, edges, u, ef, rel, self.device)
         return probs[None]
+
+
+def run_pages(sess: GnnSession, feed_dicts):
+    """``[sess.run(OUTPUT_NODE, f) for f in feed_dicts]`` with the pages of a visual model in ONE engine call
+    (:func:`gnn_forward_visual_batch_dev2`), whatever their image sizes; fed as 'image:0' or as 'image_u8:0' scans.  A model without
+    the visual branch, or a single page, goes through ``run``: its graph part has nothing to share between pages.  The outputs are
+    those of ``run`` bit for bit, in the order of ``feed_dicts``."""
+    feeds = list(feed_dicts)
+    cfg = sess.graph.cfg
+    if len(feeds) < 2 or not cfg.visual_dims:
+        return [sess.run(OUTPUT_NODE, f) for f in feeds]
+    import torch
+    device = sess.device
+    handle = sess.graph.handle(device)                       # (initialises the device before torch allocates on it)
+    dev = torch.device("cuda", int(device))
+    chans = cfg.backbone_cfg().channels
+    keep, pages, hs, ws, outs, scans = [], [], [], [], [], []
+    P = None
+    with torch.cuda.device(dev):
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev) if x is not None and x.size else None      # noqa: E731
+        ptr = lambda t: t.data_ptr() if t is not None else None                                                      # noqa: E731
+        for feed in feeds:
+            a = sess.page_arrays(feed)
+            N, E = a["N"], a["E"]
+            _check_node_indices("interacting_nodes", a["edges"], N)
+            _check_node_indices("relations", a["rel"], N)
+            with warnings.catch_warnings():                  # (a page Pillow decoded is read-only: it is only read here)
+                warnings.simplefilter("ignore", UserWarning)
+                if "page_u8" in a:
+                    h, w = a["size"]
+                    resize_mode(a["page_u8"].shape, chans)   # (a gray scan into a colour backbone: the ValueError of the single-page path)
+                    d_image = up(a["page_u8"])
+                    sh = a["page_u8"].shape
+                    scans.append((d_image.data_ptr(), sh[0], sh[1], sh[2] if len(sh) == 3 else 1))
+                else:
+                    img = a["image"]
+                    got = img.shape[2] if img.ndim == 3 else 1
+                    if img.ndim not in (2, 3) or got != chans:
+                        raise ValueError(f"this graph's backbone takes {chans} image channel(s), the image {img.shape} has {got}")
+                    if img.ndim == 3 and chans == 1:
+                        img = img[:, :, 0]
+                    d_image = up(img)
+                    h, w = img.shape[:2]
+            if P is None:
+                P = a["regions"].shape[2]
+            if a["regions"].ndim != 3 or a["regions"].shape[:2] != (N, 2) or a["regions"].shape[2] != P:
+                raise ValueError(f"visual_regions_nodes must be [N, 2, {P}] on every page of a call, got {a['regions'].shape}")
+            if cfg.visual_edges and a["eregions"].shape != (E, 2, P):
+                raise ValueError(f"visual_regions_edges must be [E, 2, P] = {(E, 2, P)}, got {a['eregions'].shape}")
+            t = [up(a[k]) for k in ("edges", "u", "ef", "regions", "npts", "eregions", "enpts", "rel")]
+            R = a["rel"].shape[0]
+            out = torch.empty((R, cfg.num_classes), dtype=torch.float32, device=dev)
+            keep.append((t, d_image))
+            outs.append(out)
+            hs.append(int(h)); ws.append(int(w))
+            pages.append(dict(N=N, E=E, R=R, d_edges=ptr(t[0]), d_node_feat=ptr(t[1]), d_edge_feat=ptr(t[2]) if E else None,
+                              d_image=d_image.data_ptr(), d_regions=ptr(t[3]), d_num_points=ptr(t[4]),
+                              d_edge_regions=ptr(t[5]) if E else None, d_edge_num_points=ptr(t[6]) if E else None,
+                              d_relations=ptr(t[7]), d_probs_out=out.data_ptr() if R else None))
+        if scans and len(scans) != len(pages):
+            raise ValueError("the pages of one call are fed all as image:0 or all as image_u8:0")
+        stream = torch.cuda.current_stream(dev)
+        if scans:                                            # every scan resized in one launch, in front of the grouped backbone
+            for d in pages:
+                d["d_image"] = None
+            gnn_forward_visual_batch_u8_dev(sess.graph, pages, scans, hs, ws, P, stream.cuda_stream or None, device)
+        else:
+            gnn_forward_visual_batch_dev2(sess.graph, pages, hs, ws, P, stream.cuda_stream or None, device)
+        results = [o.cpu().numpy()[None] for o in outs]      # (waits for the stream: the uploads above stay alive until here)
+    del handle, keep
+    return results
 
 
 def gnn_forward(graph: GnnGraph, num_nodes, edges, node_feat, edge_feat, relations=None, device=0):
@@ -410,6 +496,77 @@ def gnn_forward_visual_batch_dev(graph: GnnGraph, pages, h, w, num_region_points
                                                stream)
     _lib.check(rc, "asep_gnn_forward_visual_batch_dev")
     return pages
+
+
+def gnn_forward_visual_batch_dev2(graph: GnnGraph, pages, hs, ws, num_region_points, stream=None, device=0):
+    """``asep_gnn_forward_visual_batch_dev2``: :func:`gnn_forward_visual_batch_dev` for pages of different image sizes, ``hs[b]`` x
+    ``ws[b]`` being page b's.  One grouped backbone forward, one launch per generated-map convolution and one for all regions over
+    a page table, the graphs page by page; per page the results of the single-page call bit for bit.  Like every float entry it trusts
+    ``d_image`` to hold ``hs[b] * ws[b] *`` (the backbone's channels) values: a page struct carries no channel count (the u8 entry does, and
+    checks it).  Queued on ``stream``; the only host wait is on a table buffer whose readers were queued four calls back."""
+    lib = _lib.init_device(device)
+    if not isinstance(pages, C.Array):
+        arr = (_lib.GnnPage * len(pages))()
+        for q, d in zip(arr, pages):
+            for k, v in d.items():
+                setattr(q, k, v)
+        pages = arr
+    n = len(pages)
+    if len(hs) != n or len(ws) != n:
+        raise ValueError(f"{n} pages, {len(hs)} heights and {len(ws)} widths")
+    Ints = C.c_int32 * max(n, 1)
+    rc = lib.asep_gnn_forward_visual_batch_dev2(graph.handle(device), n, pages, Ints(*[int(v) for v in hs]), Ints(*[int(v) for v in ws]),
+                                                int(num_region_points), stream)
+    _lib.check(rc, "asep_gnn_forward_visual_batch_dev2")
+    return pages
+
+
+def gnn_forward_visual_batch_u8_dev(graph: GnnGraph, pages, scans, hs, ws, num_region_points, stream=None, device=0):
+    """``asep_gnn_forward_visual_batch_u8_dev``: :func:`gnn_forward_visual_batch_dev2` fed with the scans as decoded.  ``scans[b]`` =
+    (device address of the uint8 scan, H, W, C); all scans are resized to ``hs[b]`` x ``ws[b]`` in ONE launch
+    (``asep_prep_resize_tf1_dev``'s bytes), ``d_image`` of the page dicts is not read."""
+    lib = _lib.init_device(device)
+    n = len(pages)
+    if len(hs) != n or len(ws) != n or len(scans) != n:
+        raise ValueError(f"{n} pages, {len(scans)} scans, {len(hs)} heights and {len(ws)} widths")
+    arr = (_lib.GnnPageU8 * max(n, 1))()
+    for q, d, (addr, H, W, Cn) in zip(arr, pages, scans):
+        for k, v in d.items():
+            setattr(q.page, k, v)
+        q.d_scan, q.src_h, q.src_w, q.src_c = addr, int(H), int(W), int(Cn)
+    Ints = C.c_int32 * max(n, 1)
+    rc = lib.asep_gnn_forward_visual_batch_u8_dev(graph.handle(device), n, arr, Ints(*[int(v) for v in hs]), Ints(*[int(v) for v in ws]),
+                                                  int(num_region_points), stream)
+    _lib.check(rc, "asep_gnn_forward_visual_batch_u8_dev")
+    return arr
+
+
+def gnn_page_node_features(graph: GnnGraph, page, num_nodes, device=0):
+    """node features [N, u] of page ``page`` of the last call over a page table (tests)"""
+    lib = _lib.init_device(device)
+    out = np.empty((int(num_nodes), graph.cfg.u_in_dim), dtype=np.float32)
+    _lib.check(lib.asep_gnn_get_page_node_features(graph.handle(device), int(page), out.ctypes.data, out.size), "asep_gnn_get_page_node_features")
+    return out
+
+
+def _page_map(graph, fn_name, args, device):
+    lib = _lib.init_device(device)
+    fn = getattr(lib, fn_name)
+    dims = (C.c_int32 * 3)()
+    _lib.check(fn(graph.handle(device), *args, None, 0, dims), fn_name)
+    out = np.empty((dims[0], dims[1], dims[2]), dtype=np.float32)
+    _lib.check(fn(graph.handle(device), *args, out.ctypes.data, out.size, dims), fn_name)
+    return out
+
+
+def gnn_page_feature_map(graph: GnnGraph, page, index, device=0):
+    """feature map ``index`` of page ``page`` of the last call over a page table as float32 [fh, fw, C] (tests)"""
+    return _page_map(graph, "asep_gnn_get_page_feature_map", (int(page), int(index)), device)
+
+
+def gnn_page_image(graph: GnnGraph, page, device=0):
+    """the resized image [h, w, C] of page ``page`` of the last ``asep_gnn_forward_visual_batch_u8_dev`` call (tests)"""
+    return _page_map(graph, "asep_gnn_get_page_image", (int(page),), device)
 
 
 STEP_MODES = {0: "generic", 1: "mfma_registers", 2: "mfma_lds", 3: "factored"}

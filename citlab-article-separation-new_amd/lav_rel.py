@@ -291,6 +291,7 @@ def build_parser():
     p.add_argument("--try_gpu", default=None, **b)                          # default: True if --gpu_devices is given (:59-60)
     # extensions
     p.add_argument("--num_workers", type=int, default=1)                    # host workers that prepare pages ahead of the GPU owner
+    p.add_argument("--pages_per_call", type=cli_flags.pages_per_call, default=1)   # as in run_gnn_clustering: pages of one engine call
     p.add_argument("--device_resize", default=False, **b)                   # as in run_gnn_clustering: True = the uint8 scan is resized on the device
     return p
 
@@ -401,8 +402,39 @@ class LavGNN(object):
 
     def _forward_dev(self, graph, a, keep):
         """one page through the device-resident entries on torch's current stream -> its output buffer [N * N, classes] in HBM"""
-        import torch
+        return self._launch_pages(graph, [self._upload_page(graph, a)], keep)[0]
+
+    def _launch_pages(self, graph, recs, keep):
+        """the uploaded pages of one call (``_upload_page``) -> their output buffers, in order.  One page of a visual model goes through
+        asep_gnn_forward_visual_batch_dev as ever, several -- of whatever image sizes -- through ONE asep_gnn_forward_visual_batch_dev2
+        call; a model without the visual branch runs page by page (its graph part shares nothing between pages)."""
         from . import gnn_io
+        stream = _stream(self.device)
+        cfg = graph.cfg
+        if cfg.visual_dims and len(recs) == 1 and recs[0]["scan"] is None:
+            r = recs[0]
+            gnn_io.gnn_forward_visual_batch_dev(graph, [r["page"]], r["h"], r["w"], r["P"], stream, self.device)
+        elif cfg.visual_dims:
+            if len({r["P"] for r in recs}) != 1:
+                raise ValueError("the pages of one call must have regions of one point count")
+            fed = [r["page"] for r in recs], [r["h"] for r in recs], [r["w"] for r in recs]
+            if all(r["scan"] is not None for r in recs):     # --device_resize: every scan of the call resized in one launch
+                gnn_io.gnn_forward_visual_batch_u8_dev(graph, fed[0], [r["scan"] for r in recs], fed[1], fed[2], recs[0]["P"], stream, self.device)
+            else:
+                gnn_io.gnn_forward_visual_batch_dev2(graph, *fed, recs[0]["P"], stream, self.device)
+        else:
+            lib = _lib.init_device(self.device)
+            for r in recs:
+                q = r["page"]
+                _lib.check(lib.asep_gnn_forward_dev(graph.handle(self.device), q["N"], q["E"], q["d_edges"], q["d_node_feat"], q["d_edge_feat"],
+                                                    q["R"], None, q["d_probs_out"], stream), "asep_gnn_forward_dev")
+        keep.extend(r["t"] for r in recs)
+        return [r["out"] for r in recs]
+
+    def _upload_page(self, graph, a, scan_to_call=False):
+        """the arrays of one page into HBM (+ the device resize of a scan) -> what ``_launch_pages`` takes.  ``scan_to_call``: a scan is
+        left as uploaded, for a call that resizes all its scans in one launch (asep_gnn_forward_visual_batch_u8_dev)"""
+        import torch
         dev = f"cuda:{self.device}"
         up = lambda x: torch.from_numpy(x).to(dev) if x is not None and x.size else None            # noqa: E731
         ptr = lambda t: t.data_ptr() if t is not None else None                                    # noqa: E731
@@ -411,26 +443,27 @@ class LavGNN(object):
         with warnings.catch_warnings():                      # (a page Pillow decoded is read-only: it is only read here)
             warnings.simplefilter("ignore", UserWarning)
             t = {k: up(a.get(k)) for k in ("edges", "u", "ef", "image", "page_u8", "regions", "npts", "eregions", "enpts")}
-        if "resize" in a:
+        scan = None
+        h = w = P = 0
+        if "resize" in a and scan_to_call:
+            h, w, _ = a["resize"]
+            sh = a["page_u8"].shape
+            scan = (t["page_u8"].data_ptr(), sh[0], sh[1], sh[2] if len(sh) == 3 else 1)
+        elif "resize" in a:
             from . import image_ops
             h, w, mode = a["resize"]
             t["image"] = image_ops.resize_tf1_dev(t["page_u8"], h, w, mode, self.device)
             t["page_u8"] = None                              # (queued on torch's current stream: its allocator keeps the block until then)
         out = torch.empty((N * N, cfg.num_classes), dtype=torch.float32, device=dev)
-        stream = _stream(self.device)
         if cfg.visual_dims:
-            h, w = t["image"].shape[:2]
-            page = dict(N=N, E=E, R=N * N, d_edges=ptr(t["edges"]), d_node_feat=ptr(t["u"]), d_edge_feat=ptr(t["ef"]),
-                        d_image=ptr(t["image"]), d_regions=ptr(t["regions"]), d_num_points=ptr(t["npts"]),
-                        d_edge_regions=ptr(t["eregions"]), d_edge_num_points=ptr(t["enpts"]), d_relations=None,
-                        d_probs_out=out.data_ptr())
-            gnn_io.gnn_forward_visual_batch_dev(graph, [page], h, w, a["regions"].shape[2], stream, self.device)
-        else:
-            lib = _lib.init_device(self.device)
-            _lib.check(lib.asep_gnn_forward_dev(graph.handle(self.device), N, E, ptr(t["edges"]), ptr(t["u"]), ptr(t["ef"]), N * N,
-                                                None, out.data_ptr(), stream), "asep_gnn_forward_dev")
-        keep.append(t)
-        return out
+            if scan is None:
+                h, w = t["image"].shape[:2]
+            P = a["regions"].shape[2]
+        page = dict(N=N, E=E, R=N * N, d_edges=ptr(t["edges"]), d_node_feat=ptr(t["u"]), d_edge_feat=ptr(t["ef"]),
+                    d_image=ptr(t["image"]), d_regions=ptr(t["regions"]), d_num_points=ptr(t["npts"]),
+                    d_edge_regions=ptr(t["eregions"]), d_edge_num_points=ptr(t["enpts"]), d_relations=None,
+                    d_probs_out=out.data_ptr())
+        return {"page": page, "h": int(h), "w": int(w), "P": int(P), "t": t, "out": out, "scan": scan}
 
     def _pages(self, json_paths):
         """(feed, N, gt_relations) or None per list entry, prepared by host workers ahead of the caller when --num_workers > 1"""
@@ -515,6 +548,22 @@ class LavGNN(object):
         else:
             limited = json_paths
         pages = self._pages(limited)
+        per_call = max(1, int(getattr(flags, "pages_per_call", 1) or 1))
+        group = []
+
+        def flush():
+            """the collected pages through one engine call; their pairs reach the accumulator in input order"""
+            t0 = time.perf_counter()
+            outs = self._launch_pages(graph, [r for r, _, _ in group], keep)
+            t1 = time.perf_counter()
+            for out, (_, n, gt_relations) in zip(outs, group):
+                acc.append_page(out, n, gt_relations)
+            del group[:]
+            tm["net_s"] += t1 - t0
+            tm["append_s"] += time.perf_counter() - t1
+            if len(keep) > 64:                                        # bounded backlog of uploads the queued kernels read
+                torch.cuda.current_stream(self.device).synchronize()
+                del keep[:]
         try:
             while True:
                 if flags.batch_limiter != -1 and flags.batch_limiter <= batch_counter:
@@ -531,15 +580,13 @@ class LavGNN(object):
                 batch_counter += 1
                 feed, n, gt_relations = page
                 t0 = time.perf_counter()
-                out = self._forward_dev(graph, _feed_arrays(feed, graph.cfg), keep)
+                group.append((self._upload_page(graph, _feed_arrays(feed, graph.cfg), scan_to_call=per_call > 1), n, gt_relations))
                 feed = page = None                                    # (a scan fed from a decode slot: no view outlives its slot)
-                t1 = time.perf_counter()
-                acc.append_page(out, n, gt_relations)
-                tm["net_s"] += t1 - t0
-                tm["append_s"] += time.perf_counter() - t1
-                if len(keep) > 64:                                    # bounded backlog of uploads the queued kernels read
-                    torch.cuda.current_stream(self.device).synchronize()
-                    del keep[:]
+                tm["net_s"] += time.perf_counter() - t0
+                if len(group) >= per_call:
+                    flush()
+            if group:                                                 # the tail: fewer pages than a full call
+                flush()
         finally:
             pages.close()
         tm["pages"] = batch_counter

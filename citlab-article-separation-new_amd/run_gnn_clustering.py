@@ -44,6 +44,9 @@ def build_parser():
     # for bit; a colour file under load_mode=L is decoded as RGB and the kernel takes Pillow's luma).  The default stays the host resize
     # until the device path is no slower on every leg: with host workers it loses on colour scans
     p.add_argument("--device_resize", type=cli_flags.str2bool, default=False)
+    # extension: up to N prepared pages, of whatever image sizes, go through the engine in ONE call (gnn_io.run_pages ->
+    # asep_gnn_forward_visual_batch_dev2); 1 = page by page.  The files written are the same bytes for every N
+    p.add_argument("--pages_per_call", type=cli_flags.pages_per_call, default=1)
     p.add_argument("--assign_visual_features_to_nodes", type=cli_flags.str2bool, default=True)
     p.add_argument("--assign_visual_features_to_edges", type=cli_flags.str2bool, default=False)
     p.add_argument("--mvn", type=cli_flags.str2bool, default=True)
@@ -141,6 +144,18 @@ def _load_session(flags, device):
     return gnn_io.GnnSession(graph, device)
 
 
+def _pages_per_call(flags):
+    return max(1, int(getattr(flags, "pages_per_call", 1) or 1))
+
+
+def _run_group(sess, feeds):
+    """the net outputs of the feed dicts, in their order: one page through ``run`` as ever, several through one engine call"""
+    if len(feeds) == 1:
+        return [sess.run("output_belong_to_same_instance:0", feed_dict=feeds[0])]
+    from . import gnn_io
+    return gnn_io.run_pages(sess, feeds)
+
+
 def gnn_clustering(json_paths, flags, device="0"):
     from .clustering import TextblockClustering
     from .gnn_input import InputGNN
@@ -149,17 +164,27 @@ def gnn_clustering(json_paths, flags, device="0"):
     tb = TextblockClustering(flags)
     results = []
     t0 = time.time()
+    group = []
+
+    def flush():
+        """the collected pages through one engine call; their results leave in input order"""
+        outputs = _run_group(sess, [feed for _, feed, _ in group])
+        for (page_path, _, n), output in zip(group, outputs):
+            out = _finish_page(tb, flags, output, n, page_path)
+            if out is not None:
+                results.append(out)
+        del group[:]
     for count, json_path in enumerate(list(json_paths)):
         if flags.batch_limiter != -1 and flags.batch_limiter <= count:
             break
         page = _prepare_page(input_fn, flags, json_path)
         if page is None:
             continue
-        page_path, feed, n = page
-        output = sess.run("output_belong_to_same_instance:0", feed_dict=feed)
-        out = _finish_page(tb, flags, output, n, page_path)
-        if out is not None:
-            results.append(out)
+        group.append(page)
+        if len(group) >= _pages_per_call(flags):
+            flush()
+    if group:                                               # the tail: fewer pages than a full call
+        flush()
     logging.info(f"Time: {time.time() - t0:.2f} seconds")
     return results
 
@@ -281,6 +306,18 @@ def gnn_clustering_pipelined(json_paths, argv, device="0", host_workers=2):
                 return pool.submit(fn, list(argv), *args)
         ahead = 2 * max(1, host_workers)
         finishing = []
+        per_call = _pages_per_call(flags)
+        group = []
+
+        def flush():
+            outputs = _run_group(sess, [f for _, f, _ in group])
+            for (path, _, nodes), output in zip(group, outputs):
+                finishing.append(submit(_finish_task, output, nodes, path))
+            del group[:]
+            while len(finishing) > 4 * max(1, host_workers):                 # bounded backlog: surface errors early
+                out = finishing.pop(0).result()
+                if out is not None:
+                    results.append(out)
         try:
             prepared = [submit(_prepare_task, p, later) for p in json_paths[:ahead]]   # the workers start on the first pages while the
             sess = _load_session(flags, device)                              # owner imports the engine and loads the model
@@ -295,16 +332,18 @@ def gnn_clustering_pipelined(json_paths, argv, device="0", host_workers=2):
                 if scans is not None:
                     _, scan = next(scans)                                    # (valid until the next one is asked for: run() returns
                     feed.update(input_fn.image_feeds(scan, True))            # after the page's results have arrived)
+                    if per_call > 1:                                         # a page that waits for its call leaves the slot: a copy
+                        feed = {k: (np.array(v) if k == "image_u8:0" else v) for k, v in feed.items()}
                     del scan
-                output = sess.run("output_belong_to_same_instance:0", feed_dict=feed)
+                group.append((page_path, feed, n))
                 feed = page = None                                           # (no view of a slot outlives it)
-                finishing.append(submit(_finish_task, output, n, page_path))
-                while len(finishing) > 4 * max(1, host_workers):                 # bounded backlog: surface errors early
-                    out = finishing.pop(0).result()
-                    if out is not None:
-                        results.append(out)
+                if len(group) >= per_call:
+                    flush()
+            if group:                                                        # the tail: fewer pages than a full call
+                flush()
         finally:
             feed = page = None                                               # (also when run() raised: no view of a slot outlives it)
+            del group[:]
             if scans is not None:
                 scans.close()                                                # stops the decode workers, releases the slots
         for f in finishing:

@@ -47,7 +47,7 @@ const char* asep_version(void);
  * functions refuse a struct whose size is not the one the library was built with -- a caller written against an older or newer
  * header gets ASEP_ERR_ARG + a message instead of fields read from whatever follows its struct on the stack.
  * An added function moves the version too: a binding resolves every name it declares when it loads the library. */
-#define ASEP_ABI_VERSION 8
+#define ASEP_ABI_VERSION 9
 int asep_abi_version(void);
 /* ABI 6: the environment switches this build of the library reads when a model is loaded (one name per line).
  * Anything else in the environment is not a switch: a caller that records the switches a measurement ran under (bench.py) filters
@@ -284,6 +284,46 @@ typedef struct asep_gnn_page {
 } asep_gnn_page;
 int asep_gnn_forward_visual_batch_dev(asep_gnn* g, int n_pages, const asep_gnn_page* pages, int h, int w, int P,
                                       void* stream);
+
+/* ABI 9: asep_gnn_forward_visual_batch_dev for pages of DIFFERENT image sizes: h[b] x w[b] is page b's image size (pages[b].d_image is
+ * [h[b], w[b]] or [h[b], w[b], 3]); everything else as above.  What the reference's input pipeline leaves after its ratio-preserving resize
+ * (image_resizer.py: max side 1024, min side 256) differs from scan to scan, and the reference runs page by page (run_gnn_clustering.py:259-269).
+ * The backbones run as ONE grouped forward over the page list (asep_aru_forward_batch_dev2's launches: nothing is padded to a common frame).
+ * Each of the stages below then runs as ONE launch over a page table in device memory, whatever the pages' sizes; the graphs follow page by
+ * page:
+ *   - the two convolutions of every generated feature map;
+ *   - ROI max + compression of all node and interaction regions.
+ *   - the per-image moments of the backbone's standardisation (mean and variance over the page's own h[b] x w[b] values, sd floor 1e-4);
+ *   - with the u8 entry below, the TF1 bilinear resize of all scans.
+ * Per page the results are those of asep_gnn_forward_visual_dev bit for bit.  Refused with ASEP_ERR_ARG and a message that names the page,
+ * before anything is queued: n_pages < 1, a NULL size array, a non-positive size, a page with a missing array, and -- where the entry can
+ * know it, i.e. in the u8 entry -- a page whose image channels do not match the backbone.  An asep_gnn_page carries no channel count: as
+ * in every float entry, d_image must hold h[b] * w[b] * (the backbone's channels) values.  (What depends on the queued backbone's end points --
+ * an end point of another channel count than the attached layout -- is refused behind the backbone forward.)
+ * Everything is queued on `stream`; the one host wait is on the table buffer a call reuses, whose readers were queued four calls back
+ * (free unless the caller runs that far ahead of the device; it rules these two entries out of a stream capture).
+ * The handle's arenas and table buffers keep the largest call served so far.  Like every entry of a handle, successive calls go to one
+ * stream, or the caller orders them.  Afterwards asep_gnn_get_node_features / asep_gnn_get_feature_map behave as after the old entry;
+ * the asep_gnn_get_page_* functions read any page of the call, until the handle's next forward (the addresses they read, backbone end
+ * points included, belong to that call). */
+int asep_gnn_forward_visual_batch_dev2(asep_gnn* g, int n_pages, const asep_gnn_page* pages, const int32_t* h, const int32_t* w, int P,
+                                       void* stream);
+/* The same fed with the scans as decoded: page.d_image is not read; d_scan is uint8 [src_h, src_w, src_c], src_c = 1 or 3 (R, G, B), and is
+ * resized to h[b] x w[b] on the device (asep_prep_resize_tf1_dev's bytes, all pages in one launch): src_c equal to the backbone's channels
+ * keeps every channel, src_c = 3 into a gray backbone takes Pillow's luma per tap, anything else is the channel mismatch above. */
+typedef struct asep_gnn_page_u8 {
+    asep_gnn_page page;
+    const uint8_t* d_scan;
+    int32_t src_h, src_w, src_c;
+} asep_gnn_page_u8;
+int asep_gnn_forward_visual_batch_u8_dev(asep_gnn* g, int n_pages, const asep_gnn_page_u8* pages, const int32_t* h, const int32_t* w, int P,
+                                         void* stream);
+/* Read-back of page `page` of the handle's last call of the two entries above (tests): the concatenated node features [N, node_feature_dim],
+ * feature map `index` as fp32 [fh, fw, C] (dims receives the sizes, out == NULL asks for them only), and after the u8 entry the resized
+ * image [h, w, C].  Each waits for the call's stream. */
+int asep_gnn_get_page_node_features(asep_gnn* g, int page, float* out, size_t max_floats);
+int asep_gnn_get_page_feature_map(asep_gnn* g, int page, int index, float* out, size_t max_floats, int32_t dims[3]);
+int asep_gnn_get_page_image(asep_gnn* g, int page, float* out, size_t max_floats, int32_t dims[3]);
 
 /* Which message-passing kernel the handle uses: 0 = generic FMA kernels (any widths), 1 = fused MFMA step with the
  * edge-MLP filter in registers (widths 32, node_feature_dim <= 8), 2 = fused MFMA step with the filter in LDS (widths 32,
