@@ -14,8 +14,8 @@ void set_error(const char* fmt, ...) {
 }
 const char* get_error() { return g_err; }
 
-// Engine switches of earlier rounds whose experiments left the tree, and the two that only an ABLATION build reads:
-// a script or a log that still sets one of them measures the DEFAULT path.  Said once per process on stderr when a model is loaded.
+// Engine switches of earlier rounds whose experiments left the tree: a script or a log that still sets one of them
+// measures the DEFAULT path.  Said once per process on stderr when a model is loaded.
 void warn_ignored_switches() {
     static bool done = false;
     if (done) return;
@@ -23,10 +23,7 @@ void warn_ignored_switches() {
     static const char* const gone[] = {
         "ASEP_F32_SPLIT", "ASEP_SPLIT_L0", "ASEP_SPLIT_ALDS", "ASEP_SPLIT_TH16", "ASEP_WINOGRAD", "ASEP_WINO_REG", "ASEP_WINO16", "ASEP_BIGTILE",
         "ASEP_BIGTILE2", "ASEP_XCD_ONESHOT", "ASEP_SIDE_STREAM", "ASEP_FUSED8_VAR", "ASEP_BF_TH8", "ASEP_BF_MTB", "ASEP_BF_W8", "ASEP_BF_R8B",
-        "ASEP_BF_R8F", "ASEP_CONVS_DBG", "ASEP_R8S_DBG", "ASEP_MAXP24",
-#ifndef ASEP_ABLATION
-        "ASEP_GNN_BATCH", "ASEP_GNN_LANES",
-#endif
+        "ASEP_BF_R8F", "ASEP_CONVS_DBG", "ASEP_R8S_DBG", "ASEP_MAXP24", "ASEP_GNN_BATCH", "ASEP_GNN_LANES",
     };
     for (const char* name : gone)
         if (getenv(name))
@@ -115,11 +112,7 @@ const char* asep_version(void) { return "asep_hip 0.5 (gfx950)"; }
 
 // The environment switches this BUILD reads, one name per line.
 const char* asep_engine_switches(void) {
-    return "ASEP_FUSE_POOL\nASEP_FUSE_ACT\nASEP_C12\nASEP_FUSED8\nASEP_R8_VALU\nASEP_XCD_SCHED\nASEP_BF_RES32\nASEP_BF_WALK\nASEP_BF_CONVR\nASEP_SPLIT_DECONV\nASEP_SPLIT_WALK\nASEP_LANES\nASEP_GNN_STEP\nASEP_GNN_FACTOR"
-#ifdef ASEP_ABLATION
-           "\nASEP_GNN_BATCH\nASEP_GNN_LANES"
-#endif
-        ;
+    return "ASEP_FUSE_POOL\nASEP_FUSE_ACT\nASEP_C12\nASEP_FUSED8\nASEP_R8_VALU\nASEP_XCD_SCHED\nASEP_BF_RES32\nASEP_BF_WALK\nASEP_BF_CONVR\nASEP_SPLIT_DECONV\nASEP_SPLIT_WALK\nASEP_LANES\nASEP_GNN_STEP\nASEP_GNN_FACTOR";
 }
 int asep_abi_version(void) { return ASEP_ABI_VERSION; }
 

@@ -104,28 +104,6 @@ struct asep_gnn {
     size_t ef_cat_cap = 0;
     float* d_u_cat = nullptr;                        // concatenated node features of the last visual forward (own buffer)
     size_t u_cat_cap = 0;
-    // Page lanes of the batch entry point (ASEP_GNN_LANES, default 1 = everything on the caller's stream): the graph part of a page
-    // is a chain of ~16 launches of at most N workgroups each (N = 200: less than one workgroup per CU), so the pages of a batch CAN
-    // be dealt over several streams, each with its own arena, that fork behind the grouped backbone forward and join the caller's
-    // stream at the end.  Measured in round 4 (profiles/README.md, r4b): slower -- 412.2 -> 403.1 pages/s (bf16), 121.3 -> 119.9
-    // (fp32) with 4 lanes, the same with 8: the graph chains already run beside the page net's kernels on their own stream, and
-    // four of them at once take more issue slots from those kernels than the shorter chain gives back.  Kept as a switch.
-    struct PageLane {
-        hipStream_t s = nullptr;
-        hipEvent_t done = nullptr;
-        BufferPool pool;
-        ~PageLane() {
-            if (done) (void)hipEventDestroy(done);
-            if (s) (void)hipStreamDestroy(s);
-        }
-    };
-    std::vector<std::unique_ptr<PageLane>> page_lanes;
-    hipEvent_t ev_fork = nullptr;
-    int n_page_lanes = 1;
-    bool batch_graph = false;         // ASEP_GNN_BATCH=1: the pages of asep_gnn_forward_visual_batch_dev stage by stage (forward_batch_impl: ROI kernels, steps,
-                                      // classifier as ONE launch over the pages) instead of one after the other.  Measured (profiles/r4_ab, r4k): 240 -> 90 launches
-                                      // per 16-page call, bit-identical results, step rate unchanged (fp32 120.5 -> 120.8, bf16 419.3 -> 417.9 pages/s): the graph
-                                      // chains already hide behind the page net on their own stream -- off by default
     void free_visual() {
         for (void* p : vis_owned)
             if (p) (void)hipFree(p);
@@ -143,7 +121,6 @@ struct asep_gnn {
             if (t.h) (void)hipHostFree(t.h);
             if (t.d) (void)hipFree(t.d);
         }
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (d_u_cat) (void)hipFree(d_u_cat);
         if (d_ef_cat) (void)hipFree(d_ef_cat);
         for (void* p : owned)
@@ -508,184 +485,112 @@ int forward_impl(asep_gnn* g, BufferPool& pool, int N, int E, const int32_t* d_e
     return ASEP_OK;
 }
 
-#ifdef ASEP_ABLATION
-// ---- several pages' graphs, stage by stage (asep_gnn_forward_visual_batch_dev) --------------------------------------------------
-// The graph of one page is ~15 launches of at most 200 workgroups whose duration is the latency of ONE workgroup's work (a transition
-// step: 60-100 us for 200 nodes); sixteen pages one after the other are 48 such step launches per call.  Here every stage that is a
-// fused kernel runs ONCE for all pages (blockIdx.y = page, GnnBatch): the ROI kernels per feature map, the transition steps, the pair
-// classifier.  Same kernel bodies on the same values: bit-identical to the page-by-page form (tests/test_gnn_visual_gpu.py).
-struct GraphCtx {
-    int N = 0, E = 0, R = 0;
-    const float* d_u = nullptr;       // node features the steps read (compressed if the model compresses)
-    const float* d_fed = nullptr;     // as fed
-    const float* d_ef = nullptr;
-    const int32_t* d_rel = nullptr;
-    const int32_t* d_edges_in = nullptr;
-    float* d_out = nullptr;
-    EdgeBufs eb{};
-    float* h[2] = {nullptr, nullptr};
-    float* cs[2] = {nullptr, nullptr};
-    float *Pt = nullptr, *Qt = nullptr, *upad = nullptr;
-};
+// ---- the visual branch in front of the graph (graph_relation.py:84-172): what its three entries share --------------------------------------
 
-bool graph_batch_eligible(const asep_gnn* g) {
-    const int mode = g->use_step ? g->mode : STEP_GENERIC;
-    return (mode == STEP_BIG || mode == STEP_SMALL) && g->cfg.attention_heads == 0 && g->cfg.output_type == 0 && !g->Wc;
-}
+// the end points of page b of a grouped backbone forward are "<page_prefix(b)><name>"
+std::string page_prefix(int b) { return b ? "p" + std::to_string(b) + "/" : std::string(); }
 
-// n <= GNN_BATCH pages: edges / buffers per page, then the steps and the classifier as batched launches.  The pool is NOT reset between pages.
-int forward_batch_impl(asep_gnn* g, BufferPool& pool, int n, GraphCtx* cx, hipStream_t s) {
-    const asep_gnn_cfg& c = g->cfg;
-    const int H = g->H;
-    const int mode = g->use_step ? g->mode : STEP_GENERIC;
-    int maxN = 0, maxR = 0;
-    for (int b = 0; b < n; ++b) {
-        GraphCtx& q = cx[b];
-        if (q.N < 1 || q.E < 0 || q.R < 0) { set_error("asep_gnn_forward: bad sizes N=%d E=%d R=%d", q.N, q.E, q.R); return ASEP_ERR_ARG; }
-        if ((size_t)q.N * q.N > (size_t)1 << 30) { set_error("asep_gnn_forward: N=%d too large for the dense edge table", q.N); return ASEP_ERR_UNSUPPORTED; }
-        int rc = correct_edges_dev(g, pool, q.N, q.E, q.d_edges_in, q.eb, s);
-        if (rc) return rc;
-        const size_t nh = (size_t)q.N * H;
-        q.h[0] = (float*)pool.get(nh * 4); q.h[1] = (float*)pool.get(nh * 4);
-        q.cs[0] = (float*)pool.get(nh * 4); q.cs[1] = (float*)pool.get(nh * 4);
-        q.Pt = (float*)pool.get((size_t)q.N * c.cls_hidden1 * 4);
-        q.Qt = (float*)pool.get((size_t)q.N * c.cls_hidden1 * 4);
-        if (mode == STEP_BIG) {
-            q.upad = (float*)pool.get((size_t)q.N * g->Upad * 4);
-            hipLaunchKernelGGL(gnn_pad_rows_kernel, dim3(cdiv(q.N * g->Upad, 256)), dim3(256), 0, s, q.d_u, q.N, g->U, q.upad, g->Upad);
-        }
-        ASEP_HIP_CHECK(hipMemsetAsync(q.h[0], 0, nh * 4, s));
-        ASEP_HIP_CHECK(hipMemsetAsync(q.cs[0], 0, nh * 4, s));
-        maxN = std::max(maxN, q.N);
-        maxR = std::max(maxR, q.R);
+asep_gnn::FmapRef map_ref(const float* p, const FmapShape& m) { return asep_gnn::FmapRef{p, m.fh, m.fw, m.C, m.bf}; }
+
+// the per-page arguments of the single (b < 0: its message names no page), the uniform and the table entries
+int check_visual_page(const asep_gnn* g, const char* fn, int b, const asep_gnn_page& q, bool need_image) {
+    const int ug = g->Uin - g->vis_total;
+    if (q.N < 1 || q.E < 0 || q.R < 0 || (need_image && !q.d_image) || !q.d_regions || !q.d_num_points || (ug > 0 && !q.d_node_feat) ||
+        (q.E > 0 && !q.d_edges) || (q.R > 0 && !q.d_probs_out) || (g->Ed_fed > 0 && q.E > 0 && !q.d_edge_feat) ||
+        (g->vise_total > 0 && q.E > 0 && (!q.d_edge_regions || !q.d_edge_num_points))) {
+        if (b < 0) set_error("%s: bad argument", fn);
+        else set_error("%s: bad argument in page %d", fn, b);
+        return ASEP_ERR_ARG;
     }
-    int cur = 0;
-    for (int t = 0; t < c.num_transition_steps; ++t) {
-        if (mode == STEP_BIG) {
-            GnnBatch<StepBigArgs> ba{};
-            for (int b = 0; b < n; ++b) {
-                GraphCtx& q = cx[b];
-                StepBigArgs& sa = ba.p[b];
-                sa.u = q.upad; sa.h_in = q.h[cur]; sa.c_in = q.cs[cur]; sa.ef = q.d_ef;
-                sa.tptr = q.eb.colptr; sa.tsrc = q.eb.tsrc; sa.tfirst = q.eb.tfirst;
-                sa.A1 = (const gf32x4*)g->A1; sa.A2 = (const gf32x4*)g->A2; sa.b1 = g->b1; sa.b2 = g->b2;
-                for (int k = 0; k < 4; ++k) { sa.Wg[k] = g->Wg[k]; sa.bg[k] = g->bg[k]; }
-                sa.h_out = q.h[cur ^ 1]; sa.c_out = q.cs[cur ^ 1];
-                sa.N = q.N; sa.U = g->U; sa.Upad = g->Upad; sa.Ed = g->Ed; sa.E = std::max(q.E, 1); sa.nch = g->nch;
-                sa.qdesc = g->qdesc;
-                ba.nx[b] = q.N;
-            }
-            hipLaunchKernelGGL(gnn_step_big_kernel_batch, dim3(maxN, n), dim3(256), g->big_lds, s, ba);
-        } else {
-            GnnBatch<StepArgs> ba{};
-            for (int b = 0; b < n; ++b) {
-                GraphCtx& q = cx[b];
-                StepArgs& sa = ba.p[b];
-                sa.u = q.d_u; sa.h_in = q.h[cur]; sa.c_in = q.cs[cur]; sa.ef = q.d_ef;
-                sa.tptr = q.eb.colptr; sa.tsrc = q.eb.tsrc; sa.tfirst = q.eb.tfirst;
-                sa.A1 = (const gf32x4*)g->A1; sa.A2 = (const gf32x4*)g->A2; sa.b1 = g->b1; sa.b2 = g->b2;
-                for (int k = 0; k < 4; ++k) { sa.Wg[k] = g->Wg[k]; sa.bg[k] = g->bg[k]; }
-                sa.h_out = q.h[cur ^ 1]; sa.c_out = q.cs[cur ^ 1];
-                sa.N = q.N; sa.U = g->U; sa.Ed = g->Ed; sa.E = std::max(q.E, 1); sa.nch = g->nch;
-                sa.qdesc = g->qdesc;
-                ba.nx[b] = q.N;
-            }
-            hipLaunchKernelGGL(gnn_step_kernel_batch, dim3(maxN, n), dim3(256), 0, s, ba);
-        }
-        cur ^= 1;
-    }
-    g->d_h = cx[n - 1].h[cur];
-    g->N = cx[n - 1].N;
-    if (maxR > 0) {
-        GnnBatch<PairPreArgs> bp{};
-        int maxpre = 0;
-        for (int b = 0; b < n; ++b) {
-            GraphCtx& q = cx[b];
-            bp.p[b] = PairPreArgs{q.h[cur], q.N, H, g->C1, c.cls_hidden1, q.Pt, q.Qt};
-            bp.nx[b] = q.R > 0 ? std::min(cdiv(q.N * c.cls_hidden1, 256), 1024) : 0;
-            maxpre = std::max(maxpre, bp.nx[b]);
-        }
-        hipLaunchKernelGGL(gnn_pair_pre_kernel_batch, dim3(maxpre, n), dim3(256), 0, s, bp);
-        if (g->cls_fast) {
-            GnnBatch<PairArgs> ba{};
-            for (int b = 0; b < n; ++b) {
-                GraphCtx& q = cx[b];
-                PairArgs& pa = ba.p[b];
-                pa.Pt = q.Pt; pa.Qt = q.Qt; pa.b1 = g->cb1; pa.W2 = g->C2; pa.b2 = g->cb2; pa.W3 = g->C3; pa.b3 = g->cb3;
-                pa.rel = q.d_rel; pa.out = q.d_out; pa.N = q.N; pa.R = q.R;
-                ba.nx[b] = cdiv(q.R, 256);
-            }
-            hipLaunchKernelGGL((gnn_pair_cls_kernel_batch<64, 32, 2>), dim3(cdiv(maxR, 256), n), dim3(256), 0, s, ba);
-        } else {
-            for (int b = 0; b < n; ++b) {
-                GraphCtx& q = cx[b];
-                if (q.R < 1) continue;
-                PairGenArgs pg{};
-                pg.Pt = q.Pt; pg.Qt = q.Qt; pg.b1 = g->cb1; pg.rest = g->cls_rest; pg.rel = q.d_rel; pg.out = q.d_out; pg.N = q.N; pg.R = q.R;
-                pg.maxw = g->cls_maxw;
-                hipLaunchKernelGGL(gnn_pair_cls_generic_kernel, dim3(cdiv(q.R, PAIRG_P)), dim3(256), 2 * (size_t)PAIRG_P * g->cls_maxw * sizeof(float), s, pg);
-            }
-        }
-    }
-    ASEP_HIP_CHECK(hipGetLastError());
     return ASEP_OK;
 }
-#endif
+
+int reserve_floats(float** p, size_t* cap, size_t n) {          // a grow-only buffer of the handle (d_u_cat, d_ef_cat)
+    if (*cap < n) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr; *cap = 0;
+        ASEP_HIP_CHECK(hipMalloc((void**)p, n * sizeof(float)));
+        *cap = n;
+    }
+    return ASEP_OK;
+}
+
+int endpoint_ref(asep_gnn* g, const std::string& name, asep_gnn::FmapRef* m) {
+    int dims[3];
+    int rc = aru_endpoint_dev(g->backbone, name.c_str(), &m->p, dims, &m->bf);
+    if (rc) return rc;
+    m->fh = dims[0]; m->fw = dims[1]; m->C = dims[2];
+    return ASEP_OK;
+}
+
+// The maps of the page whose backbone end points are "<prefix><name>" of the forward that is queued: the plan of launch_plan.h over the handle's
+// layout, with the end points' addresses (end_p[i] where map i is or reads one), and its channel verdicts as errors.
+int page_map_plan(asep_gnn* g, const std::string& prefix, std::vector<FmapStep>& plan, std::vector<const float*>& end_p) {
+    const size_t n = g->vis_names.size();
+    std::vector<FmapSpec> spec(n);
+    std::vector<FmapShape> ends(n, FmapShape{});
+    end_p.assign(n, nullptr);
+    for (size_t i = 0; i < n; ++i) {
+        const asep_gnn::FmapGen& G = g->vis_gen[i];
+        spec[i] = FmapSpec{G.depth, G.stride, G.Cin};
+        if (G.depth >= 0 && G.stride != 1) continue;        // (reads map i - 1)
+        asep_gnn::FmapRef m{};
+        int rc = endpoint_ref(g, prefix + g->vis_names[i], &m);
+        if (rc) return rc;
+        end_p[i] = m.p;
+        ends[i] = FmapShape{m.fh, m.fw, m.C, m.bf};
+    }
+    plan = fmap_plan(spec.data(), ends.data(), g->vis_C.data(), (int)n);
+    for (size_t i = 0; i < n; ++i) {
+        if (!plan[i].bad_channels) continue;
+        if (plan[i].generated) set_error("feature map %zu reads %d channels, its 1x1 filter was loaded for %d", i, plan[i].in.C, spec[i].Cin);
+        else set_error("end point %s has %d channels, expected %d", g->vis_names[i].c_str(), plan[i].out.C, g->vis_C[i]);
+        return ASEP_ERR_ARG;
+    }
+    return ASEP_OK;
+}
 
 // feature_map_generators.py:140-194 for the page whose backbone end points are "<prefix><name>" of the forward queued on s: every generated
 // map into the handle's arena (two launches each, fmap_kernels.h), every map's address into g->fmap_last.  A layout without generated
 // maps returns at once: it allocates and launches nothing.
 int generate_maps_dev(asep_gnn* g, const std::string& prefix, hipStream_t s) {
     if (g->n_generated == 0) return ASEP_OK;
-    const size_t n = g->vis_names.size();
-    g->fmap_last.assign(n, asep_gnn::FmapRef{});
+    std::vector<FmapStep> plan;
+    std::vector<const float*> end_p;
+    int rc = page_map_plan(g, prefix, plan, end_p);
+    if (rc) return rc;
+    g->fmap_last.assign(plan.size(), asep_gnn::FmapRef{});
     g->fmap_last_prefix = prefix;
-    for (size_t i = 0; i < n; ++i) {
+    for (size_t i = 0; i < plan.size(); ++i) {
+        const FmapStep& k = plan[i];
+        if (!k.generated) { g->fmap_last[i] = map_ref(end_p[i], k.out); continue; }
         const asep_gnn::FmapGen& G = g->vis_gen[i];
-        asep_gnn::FmapRef src{};
-        if (G.depth < 0 || G.stride == 1) {                 // a backbone end point: the map itself, or what the two convolutions read
-            int dims[3];
-            int rc = aru_endpoint_dev(g->backbone, (prefix + g->vis_names[i]).c_str(), &src.p, dims, &src.bf);
-            if (rc) return rc;
-            src.fh = dims[0]; src.fw = dims[1]; src.C = dims[2];
-        } else {
-            src = g->fmap_last[i - 1];
-        }
-        if (G.depth < 0) { g->fmap_last[i] = src; continue; }
-        if (src.C != G.Cin) { set_error("feature map %zu reads %d channels, its 1x1 filter was loaded for %d", i, src.C, G.Cin); return ASEP_ERR_ARG; }
         const int half = G.depth / 2;
         FmapConvArgs a{};
-        a.in = src.p; a.W = G.W1; a.b = G.b1; a.ih = src.fh; a.iw = src.fw; a.Ci = src.C; a.Co = half; a.oh = src.fh; a.ow = src.fw;
-        a.stride = 1;
-        const size_t n1 = (size_t)src.fh * src.fw * half;
-        float* mid = (float*)g->fmap_pool.get(n1 * sizeof(float));
+        a.in = k.src < 0 ? end_p[i] : g->fmap_last[k.src].p; a.W = G.W1; a.b = G.b1; a.ih = k.d.ih; a.iw = k.d.iw; a.Ci = k.in.C; a.Co = half;
+        a.oh = k.d.ih; a.ow = k.d.iw; a.stride = 1;
+        float* mid = (float*)g->fmap_pool.get(k.n1 * sizeof(float));
         a.out = mid;
         FmapConvArgs c{};
-        c.in = mid; c.W = G.W2; c.b = G.b2; c.ih = src.fh; c.iw = src.fw; c.Ci = half; c.Co = G.depth; c.stride = G.stride;
-        same_pad3(src.fh, G.stride, &c.oh, &c.pad_t);
-        same_pad3(src.fw, G.stride, &c.ow, &c.pad_l);
-        const size_t n2 = (size_t)c.oh * c.ow * G.depth;
-        c.out = (float*)g->fmap_pool.get(n2 * sizeof(float));
-        if (n1 + 255 > ((size_t)1 << 31) * 256 || n2 + 255 > ((size_t)1 << 31) * 256) { set_error("feature map %zu is too large for one launch", i); return ASEP_ERR_UNSUPPORTED; }
-        const std::string where = "fm_" + std::to_string(i) + " " + std::to_string(src.fh) + "x" + std::to_string(src.fw);
-        const size_t ebytes = src.bf ? 2 : 4;
-        {   // algorithmic bytes: the input once, the filter and bias once, the output once
-            const std::string det = where + " " + std::to_string(src.C) + "->" + std::to_string(half);
-            void* ps = aru_prof_begin(g->backbone, src.bf ? "fmap_conv1x1_kernel<true>" : "fmap_conv1x1_kernel<false>", det.c_str(),
-                                      2.0 * (double)n1 * src.C,
-                                      (double)src.fh * src.fw * src.C * ebytes + 4.0 * ((double)src.C * half + half) + 4.0 * (double)n1);
-            if (src.bf) hipLaunchKernelGGL(fmap_conv1x1_kernel<true>, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL(fmap_conv1x1_kernel<false>, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, a);
+        c.in = mid; c.W = G.W2; c.b = G.b2; c.ih = k.d.ih; c.iw = k.d.iw; c.Ci = half; c.Co = G.depth; c.stride = G.stride;
+        c.oh = k.d.oh; c.ow = k.d.ow; c.pad_t = k.d.pad_t; c.pad_l = k.d.pad_l;
+        c.out = (float*)g->fmap_pool.get(k.n2 * sizeof(float));
+        if (k.n1 + 255 > ((size_t)1 << 31) * 256 || k.n2 + 255 > ((size_t)1 << 31) * 256) { set_error("feature map %zu is too large for one launch", i); return ASEP_ERR_UNSUPPORTED; }
+        const std::string where = "fm_" + std::to_string(i) + " " + std::to_string(k.d.ih) + "x" + std::to_string(k.d.iw);
+        {
+            const std::string det = where + " " + std::to_string(k.in.C) + "->" + std::to_string(half);
+            void* ps = aru_prof_begin(g->backbone, k.in.bf ? "fmap_conv1x1_kernel<true>" : "fmap_conv1x1_kernel<false>", det.c_str(), k.fl1, k.io1 + k.w1);
+            if (k.in.bf) hipLaunchKernelGGL(fmap_conv1x1_kernel<true>, dim3((unsigned)((k.n1 + 255) / 256)), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL(fmap_conv1x1_kernel<false>, dim3((unsigned)((k.n1 + 255) / 256)), dim3(256), 0, s, a);
             aru_prof_end(ps);
         }
         {
             const std::string det = where + " " + std::to_string(half) + "->" + std::to_string(G.depth) + " s" + std::to_string(G.stride);
-            void* ps = aru_prof_begin(g->backbone, "fmap_conv3x3_kernel", det.c_str(), 2.0 * (double)n2 * 9 * half,
-                                      4.0 * (double)n1 + 4.0 * (9.0 * half * G.depth + G.depth) + 4.0 * (double)n2);
-            hipLaunchKernelGGL(fmap_conv3x3_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, c);
+            void* ps = aru_prof_begin(g->backbone, "fmap_conv3x3_kernel", det.c_str(), k.fl3, k.io3 + k.w3);
+            hipLaunchKernelGGL(fmap_conv3x3_kernel, dim3((unsigned)((k.n2 + 255) / 256)), dim3(256), 0, s, c);
             aru_prof_end(ps);
         }
-        g->fmap_last[i] = asep_gnn::FmapRef{c.out, c.oh, c.ow, G.depth, 0};
+        g->fmap_last[i] = map_ref(c.out, k.out);
     }
     ASEP_HIP_CHECK(hipGetLastError());
     return ASEP_OK;
@@ -693,103 +598,92 @@ int generate_maps_dev(asep_gnn* g, const std::string& prefix, hipStream_t s) {
 
 // map i of the page "<prefix>": the backbone's end point (the default layout: exactly the lookup the ROI launchers always made) or, in a
 // layout with generated maps, what generate_maps_dev left for this page
-int visual_map_dev(asep_gnn* g, const std::string& prefix, size_t i, const float** fm, int dims[3], int* bf) {
-    if (g->n_generated == 0) return aru_endpoint_dev(g->backbone, (prefix + g->vis_names[i]).c_str(), fm, dims, bf);
+int visual_map_dev(asep_gnn* g, const std::string& prefix, size_t i, asep_gnn::FmapRef* m) {
+    if (g->n_generated == 0) return endpoint_ref(g, prefix + g->vis_names[i], m);
     if (i >= g->fmap_last.size() || !g->fmap_last[i].p || g->fmap_last_prefix != prefix) { set_error("feature map %zu of this page was not generated", i); return ASEP_ERR_ARG; }
-    const asep_gnn::FmapRef& r = g->fmap_last[i];
-    *fm = r.p; dims[0] = r.fh; dims[1] = r.fw; dims[2] = r.C; *bf = r.bf;
+    *m = g->fmap_last[i];
     return ASEP_OK;
 }
 
-// graph_relation.py:84-139 in front of the graph: backbone, ROI max + compression per feature map, concatenation.
-// ROI max + compression of one page's nodes from the backbone end points "<prefix><name>" of the forward that is queued
-// on s; d_ug [N, U - visual dims] -> d_u [N, U]
-int visual_rois_dev(asep_gnn* g, int N, const float* d_ug, const std::string& prefix, const float* d_reg, int P,
-                    const int32_t* d_np, float* d_u, hipStream_t s) {
-    const int U = g->Uin, ug = U - g->vis_total;            // width of the FED (concatenated) features
-    if (ug > 0) hipLaunchKernelGGL(gnn_copy_cols_kernel, dim3(cdiv(N * ug, 256)), dim3(256), 0, s, d_ug, N, ug, d_u, U);
-    int col = ug;
+// ROI max + compression (graph_relation.py:84-172, misc.py:384-470) has two sides, the nodes' regions and the interactions': per map a
+// compression layer d[i] wide whose output goes behind the `fed` columns of the features as fed, in rows `stride` wide.  want_C: the maps'
+// channels where the side checks them (the nodes' side)
+struct RoiSide { const std::vector<float*>& W; const std::vector<float*>& b; const std::vector<int>& d; int fed, stride; const int* want_C; };
+RoiSide node_side(const asep_gnn* g) { return RoiSide{g->vis_W, g->vis_b, g->vis_d, g->Uin - g->vis_total, g->Uin, g->vis_C.data()}; }
+RoiSide edge_side(const asep_gnn* g) { return RoiSide{g->vise_W, g->vise_b, g->vise_d, g->Ed_fed, g->Ed, nullptr}; }
+
+// one launch's (or one table entry's) arguments: the regions of one page on map i -> columns col .. col + d[i] - 1 of out
+RoiArgs roi_entry(const asep_gnn::FmapRef& m, const float* regions, int P, const int32_t* npts, const RoiSide& sd, size_t i, float* out, int col) {
+    RoiArgs a{};
+    a.fm = m.p; a.fh = m.fh; a.fw = m.fw; a.C = m.C;
+    a.regions = regions; a.P = P; a.npts = npts; a.Wc = sd.W[i]; a.bc = sd.b[i]; a.d = sd.d[i];
+    a.u_out = out; a.ustride = sd.stride; a.col0 = col; a.vmax_out = nullptr;
+    return a;
+}
+
+// one side of one page from the maps "<prefix>..." of the forward that is queued on s: d_fed [rows, fed] -> d_out [rows, stride]
+int visual_rois_dev(asep_gnn* g, const RoiSide& sd, int rows, const float* d_fed, const std::string& prefix, const float* d_reg, int P,
+                    const int32_t* d_np, float* d_out, hipStream_t s) {
+    if (rows < 1) return ASEP_OK;
+    if (sd.fed > 0) hipLaunchKernelGGL(gnn_copy_cols_kernel, dim3(cdiv(rows * sd.fed, 256)), dim3(256), 0, s, d_fed, rows, sd.fed, d_out, sd.stride);
+    int col = sd.fed;
     for (size_t i = 0; i < g->vis_names.size(); ++i) {
-        const float* fm = nullptr;
-        int dims[3];
-        int bf = 0;                                         // a bf16 backbone (compute_dtype 1) hands over bf16 maps
-        int rc = visual_map_dev(g, prefix, i, &fm, dims, &bf);
+        asep_gnn::FmapRef m{};                              // (a bf16 backbone, compute_dtype 1, hands over bf16 maps)
+        int rc = visual_map_dev(g, prefix, i, &m);
         if (rc) return rc;
-        if (dims[2] != g->vis_C[i]) { set_error("end point %s has %d channels, expected %d", g->vis_names[i].c_str(), dims[2], g->vis_C[i]); return ASEP_ERR_ARG; }
-        RoiArgs a{};
-        a.fm = fm; a.fh = dims[0]; a.fw = dims[1]; a.C = dims[2];
-        a.regions = d_reg; a.P = P; a.npts = d_np; a.Wc = g->vis_W[i]; a.bc = g->vis_b[i]; a.d = g->vis_d[i];
-        a.u_out = d_u; a.ustride = U; a.col0 = col; a.vmax_out = nullptr;
-        if (bf) hipLaunchKernelGGL(gnn_roi_compress_kernel<true>, dim3(N), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(gnn_roi_compress_kernel<false>, dim3(N), dim3(256), 0, s, a);
-        col += g->vis_d[i];
+        if (sd.want_C && m.C != sd.want_C[i]) { set_error("end point %s has %d channels, expected %d", g->vis_names[i].c_str(), m.C, sd.want_C[i]); return ASEP_ERR_ARG; }
+        const RoiArgs a = roi_entry(m, d_reg, P, d_np, sd, i, d_out, col);
+        if (m.bf) hipLaunchKernelGGL(gnn_roi_compress_kernel<true>, dim3(rows), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(gnn_roi_compress_kernel<false>, dim3(rows), dim3(256), 0, s, a);
+        col += sd.d[i];
     }
     ASEP_HIP_CHECK(hipGetLastError());
     return ASEP_OK;
 }
 
-// graph_relation.py:141-172 + misc.py:384-470: the same ROI max + compression for the E interactions' regions; the compressed
-// features go behind the fed edge features: d_ef_fed [E, Ed_fed] -> d_ef [E, Ed]
-int visual_edge_rois_dev(asep_gnn* g, int E, const float* d_ef_fed, const std::string& prefix, const float* d_reg, int P,
-                         const int32_t* d_np, float* d_ef, hipStream_t s) {
-    if (E < 1) return ASEP_OK;
-    const int Ed = g->Ed, ef = g->Ed_fed;
-    if (ef > 0) hipLaunchKernelGGL(gnn_copy_cols_kernel, dim3(cdiv(E * ef, 256)), dim3(256), 0, s, d_ef_fed, E, ef, d_ef, Ed);
-    int col = ef;
-    for (size_t i = 0; i < g->vis_names.size(); ++i) {
-        const float* fm = nullptr;
-        int dims[3];
-        int bf = 0;
-        int rc = visual_map_dev(g, prefix, i, &fm, dims, &bf);
+// Everything of one page behind its backbone forward, queued on s: generated maps, ROI max + compression of nodes and interactions, the graph.
+// The page's rows go to *d_u (and *d_efc), which move on to the next page's.
+int visual_page_dev(asep_gnn* g, const asep_gnn_page& q, const std::string& prefix, int P, float** d_u, float** d_efc, hipStream_t s) {
+    g->fmap_pool.begin();                                   // the pages of a call share the arena's buffers: page b + 1's generator is ordered behind page b's ROI kernels
+    int rc = generate_maps_dev(g, prefix, s);
+    if (rc) return rc;
+    rc = visual_rois_dev(g, node_side(g), q.N, q.d_node_feat, prefix, q.d_regions, P, q.d_num_points, *d_u, s);
+    if (rc) return rc;
+    const float* d_ef = q.d_edge_feat;
+    if (g->vise_total > 0 && q.E > 0) {
+        rc = visual_rois_dev(g, edge_side(g), q.E, q.d_edge_feat, prefix, q.d_edge_regions, P, q.d_edge_num_points, *d_efc, s);
         if (rc) return rc;
-        RoiArgs a{};
-        a.fm = fm; a.fh = dims[0]; a.fw = dims[1]; a.C = dims[2];
-        a.regions = d_reg; a.P = P; a.npts = d_np; a.Wc = g->vise_W[i]; a.bc = g->vise_b[i]; a.d = g->vise_d[i];
-        a.u_out = d_ef; a.ustride = Ed; a.col0 = col; a.vmax_out = nullptr;
-        if (bf) hipLaunchKernelGGL(gnn_roi_compress_kernel<true>, dim3(E), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(gnn_roi_compress_kernel<false>, dim3(E), dim3(256), 0, s, a);
-        col += g->vise_d[i];
+        d_ef = *d_efc;
+        *d_efc += (size_t)q.E * g->Ed;
     }
-    ASEP_HIP_CHECK(hipGetLastError());
+    rc = forward_impl(g, g->pool, q.N, q.E, q.d_edges, *d_u, d_ef, q.R, q.d_relations, q.d_probs_out, s);
+    if (rc) return rc;
+    *d_u += (size_t)q.N * g->Uin;
     return ASEP_OK;
 }
 
-int reserve_ef_cat(asep_gnn* g, size_t n) {
-    if (g->ef_cat_cap < n) {
-        if (g->d_ef_cat) (void)hipFree(g->d_ef_cat);
-        g->d_ef_cat = nullptr; g->ef_cat_cap = 0;
-        ASEP_HIP_CHECK(hipMalloc((void**)&g->d_ef_cat, n * sizeof(float)));
-        g->ef_cat_cap = n;
-    }
-    return ASEP_OK;
-}
-
-int reserve_u_cat(asep_gnn* g, size_t nu) {
-    if (g->u_cat_cap < nu) {
-        if (g->d_u_cat) (void)hipFree(g->d_u_cat);
-        g->d_u_cat = nullptr; g->u_cat_cap = 0;
-        ASEP_HIP_CHECK(hipMalloc((void**)&g->d_u_cat, nu * sizeof(float)));
-        g->u_cat_cap = nu;
+// read-backs (tests): a map as fp32 [fh, fw, C] (out == nullptr: the sizes only), and N rows of the concatenated node features from row offset off
+int copy_map_out(asep_gnn* g, const char* fn, const asep_gnn::FmapRef& r, float* out, size_t max_floats, int32_t dims[3]) {
+    dims[0] = r.fh; dims[1] = r.fw; dims[2] = r.C;
+    const size_t n = (size_t)r.fh * r.fw * r.C;
+    if (!out) return ASEP_OK;
+    if (max_floats < n) { set_error("%s: buffer too small (%zu floats needed)", fn, n); return ASEP_ERR_ARG; }
+    ASEP_HIP_CHECK(hipStreamSynchronize(g->stream));
+    if (r.bf) {                                             // a bf16 end point widens exactly
+        std::vector<uint16_t> hb(n);
+        ASEP_HIP_CHECK(hipMemcpy(hb.data(), r.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) { const uint32_t u = (uint32_t)hb[i] << 16; memcpy(out + i, &u, 4); }
+    } else {
+        ASEP_HIP_CHECK(hipMemcpy(out, r.p, n * sizeof(float), hipMemcpyDeviceToHost));
     }
     return ASEP_OK;
 }
 
-// d_ug [N, U - visual dims]; everything on stream s; returns the concatenated features [N, U] in *d_u_out.
-int visual_features_dev(asep_gnn* g, int N, const float* d_ug, const float* d_img, int h, int w, const float* d_reg, int P,
-                        const int32_t* d_np, float** d_u_out, hipStream_t s) {
-    g->vis_pool.begin();
-    const int ncls = std::max(1, aru_num_classes(g->backbone));
-    float* d_bo = (float*)g->vis_pool.get((size_t)h * w * ncls * sizeof(float));   // backbone logits (not used by the graph)
-    int rc = reserve_u_cat(g, (size_t)N * g->Uin);
-    if (rc) return rc;
-    rc = asep_aru_forward_dev(g->backbone, d_img, h, w, d_bo, nullptr, nullptr, 0.f, s);
-    if (rc) return rc;
-    g->fmap_pool.begin();
-    rc = generate_maps_dev(g, std::string(), s);
-    if (rc) return rc;
-    rc = visual_rois_dev(g, N, d_ug, std::string(), d_reg, P, d_np, g->d_u_cat, s);
-    if (rc) return rc;
-    *d_u_out = g->d_u_cat;
+int copy_node_features_out(asep_gnn* g, const char* fn, size_t off, int N, float* out, size_t max_floats) {
+    const size_t n = (size_t)N * g->Uin;
+    if (max_floats < n) { set_error("%s: buffer too small", fn); return ASEP_ERR_ARG; }
+    ASEP_HIP_CHECK(hipStreamSynchronize(g->stream));
+    ASEP_HIP_CHECK(hipMemcpy(out, g->d_u_cat + off, n * sizeof(float), hipMemcpyDeviceToHost));
     return ASEP_OK;
 }
 
@@ -914,9 +808,6 @@ asep_gnn* asep_gnn_load(const void* weight_blob, size_t nbytes, const asep_gnn_c
     warn_ignored_switches();
     if (const char* ev = getenv("ASEP_GNN_STEP")) g->use_step = atoi(ev) != 0;
     if (const char* ev = getenv("ASEP_GNN_FACTOR")) g->use_fact = atoi(ev) != 0;
-#ifdef ASEP_ABLATION   // measured and not adopted (DESIGN_LESSONS 28, 36); `make ABLATION=1` builds them for scripts/r4_ab.sh
-    if (const char* ev = getenv("ASEP_GNN_BATCH")) g->batch_graph = atoi(ev) != 0; if (const char* e2 = getenv("ASEP_GNN_LANES")) g->n_page_lanes = std::max(1, std::min(16, atoi(e2)));
-#endif
     // the fused MFMA step kernels serve the reference's defaults: widths 32 / [32] / 32, degree-normalised SUM, both LSTM inputs
     const bool default_widths = H == GNN_H && I == GNN_H && Hm == GNN_H && ih.size() == 1 && heads == 0 && cfg->aggregation_type == 0 &&
                                 g->cfg.lstm_use_hidden && g->cfg.lstm_use_input;
@@ -1153,24 +1044,11 @@ int asep_gnn_attach_backbone_maps(asep_gnn* g, asep_aru* backbone, int n_maps, c
 int asep_gnn_get_feature_map(asep_gnn* g, int index, float* out, size_t max_floats, int32_t dims[3]) {
     ASEP_GUARD_BEGIN
     if (!g || !g->backbone || !dims || index < 0 || index >= (int)g->vis_names.size()) { set_error("asep_gnn_get_feature_map: bad argument"); return ASEP_ERR_ARG; }
-    const float* p = nullptr;
-    int d[3], bf = 0;
+    asep_gnn::FmapRef m{};
     // the maps of the page the last forward served last (a batch: its last page)
-    int rc = visual_map_dev(g, g->n_generated ? g->fmap_last_prefix : std::string(), (size_t)index, &p, d, &bf);
+    int rc = visual_map_dev(g, g->n_generated ? g->fmap_last_prefix : std::string(), (size_t)index, &m);
     if (rc) return rc;
-    dims[0] = d[0]; dims[1] = d[1]; dims[2] = d[2];
-    const size_t n = (size_t)d[0] * d[1] * d[2];
-    if (!out) return ASEP_OK;                            // sizes only
-    if (max_floats < n) { set_error("asep_gnn_get_feature_map: buffer too small (%zu floats needed)", n); return ASEP_ERR_ARG; }
-    ASEP_HIP_CHECK(hipStreamSynchronize(g->stream));
-    if (bf) {                                            // a bf16 end point widens exactly
-        std::vector<uint16_t> h(n);
-        ASEP_HIP_CHECK(hipMemcpy(h.data(), p, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; ++i) { const uint32_t u = (uint32_t)h[i] << 16; memcpy(out + i, &u, 4); }
-    } else {
-        ASEP_HIP_CHECK(hipMemcpy(out, p, n * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    return ASEP_OK;
+    return copy_map_out(g, "asep_gnn_get_feature_map", m, out, max_floats, dims);
     ASEP_GUARD_END
 }
 
@@ -1179,43 +1057,38 @@ int asep_gnn_forward_visual_dev(asep_gnn* g, int N, int E, const int32_t* d_edge
                                 const int32_t* d_num_points, const float* d_edge_regions, const int32_t* d_edge_num_points,
                                 int R, const int32_t* d_relations, float* d_probs_out, void* stream) {
     ASEP_GUARD_BEGIN
-    if (!g || !g->backbone) { set_error("asep_gnn_forward_visual_dev: no backbone attached"); return ASEP_ERR_ARG; }
-    const int ug = g->Uin - g->vis_total;
-    if (N < 1 || h < 1 || w < 1 || P < 1 || !d_image || !d_regions || !d_num_points || (ug > 0 && !d_node_feat) ||
-        (E > 0 && !d_edges) || (R > 0 && !d_probs_out) || (g->Ed_fed > 0 && E > 0 && !d_edge_feat) ||
-        (g->vise_total > 0 && E > 0 && (!d_edge_regions || !d_edge_num_points))) {
-        set_error("asep_gnn_forward_visual_dev: bad argument");
-        return ASEP_ERR_ARG;
-    }
-    float* d_u = nullptr;
-    int rc = visual_features_dev(g, N, d_node_feat, d_image, h, w, d_regions, P, d_num_points, &d_u, (hipStream_t)stream);
+    const char* fn = "asep_gnn_forward_visual_dev";
+    if (!g || !g->backbone) { set_error("%s: no backbone attached", fn); return ASEP_ERR_ARG; }
+    if (h < 1 || w < 1 || P < 1) { set_error("%s: bad argument", fn); return ASEP_ERR_ARG; }
+    const asep_gnn_page q{N, E, R, d_edges, d_node_feat, d_edge_feat, d_image, d_regions, d_num_points, d_edge_regions, d_edge_num_points,
+                          d_relations, d_probs_out};
+    int rc = check_visual_page(g, fn, -1, q, true);
     if (rc) return rc;
-    if (g->vise_total > 0 && E > 0) {
-        rc = reserve_ef_cat(g, (size_t)E * g->Ed);
-        if (!rc) rc = visual_edge_rois_dev(g, E, d_edge_feat, std::string(), d_edge_regions, P, d_edge_num_points, g->d_ef_cat, (hipStream_t)stream);
-        if (rc) return rc;
-        d_edge_feat = g->d_ef_cat;
-    }
-    return forward_impl(g, g->pool, N, E, d_edges, d_u, d_edge_feat, R, d_relations, d_probs_out, (hipStream_t)stream);
+    hipStream_t s = (hipStream_t)stream;
+    g->vis_pool.begin();
+    const int ncls = std::max(1, aru_num_classes(g->backbone));
+    float* d_bo = (float*)g->vis_pool.get((size_t)h * w * ncls * sizeof(float));   // backbone logits (not used by the graph)
+    rc = reserve_floats(&g->d_u_cat, &g->u_cat_cap, (size_t)N * g->Uin);
+    if (!rc && g->vise_total > 0 && E > 0) rc = reserve_floats(&g->d_ef_cat, &g->ef_cat_cap, (size_t)E * g->Ed);
+    if (rc) return rc;
+    rc = asep_aru_forward_dev(g->backbone, d_image, h, w, d_bo, nullptr, nullptr, 0.f, s);
+    if (rc) return rc;
+    float* d_u = g->d_u_cat;
+    float* d_efc = g->d_ef_cat;
+    return visual_page_dev(g, q, std::string(), P, &d_u, &d_efc, s);
     ASEP_GUARD_END
 }
 
 int asep_gnn_forward_visual_batch_dev(asep_gnn* g, int n_pages, const asep_gnn_page* pages, int h, int w, int P, void* stream) {
     ASEP_GUARD_BEGIN
-    if (!g || !g->backbone) { set_error("asep_gnn_forward_visual_batch_dev: no backbone attached"); return ASEP_ERR_ARG; }
-    if (n_pages < 1 || !pages || h < 1 || w < 1 || P < 1) { set_error("asep_gnn_forward_visual_batch_dev: bad argument"); return ASEP_ERR_ARG; }
-    const int ug = g->Uin - g->vis_total;
+    const char* fn = "asep_gnn_forward_visual_batch_dev";
+    if (!g || !g->backbone) { set_error("%s: no backbone attached", fn); return ASEP_ERR_ARG; }
+    if (n_pages < 1 || !pages || h < 1 || w < 1 || P < 1) { set_error("%s: bad argument", fn); return ASEP_ERR_ARG; }
     size_t nu = 0, nef = 0;
     for (int b = 0; b < n_pages; ++b) {
-        const asep_gnn_page& q = pages[b];
-        if (q.N < 1 || !q.d_image || !q.d_regions || !q.d_num_points || (ug > 0 && !q.d_node_feat) || (q.E > 0 && !q.d_edges) ||
-            (q.R > 0 && !q.d_probs_out) || (g->Ed_fed > 0 && q.E > 0 && !q.d_edge_feat) ||
-            (g->vise_total > 0 && q.E > 0 && (!q.d_edge_regions || !q.d_edge_num_points))) {
-            set_error("asep_gnn_forward_visual_batch_dev: bad argument in page %d", b);
-            return ASEP_ERR_ARG;
-        }
-        nu += (size_t)q.N * g->Uin;
-        if (g->vise_total > 0) nef += (size_t)q.E * g->Ed;
+        if (int rc = check_visual_page(g, fn, b, pages[b], true)) return rc;
+        nu += (size_t)pages[b].N * g->Uin;
+        if (g->vise_total > 0) nef += (size_t)pages[b].E * g->Ed;
     }
     hipStream_t s = (hipStream_t)stream;
     g->vis_pool.begin();
@@ -1226,110 +1099,17 @@ int asep_gnn_forward_visual_batch_dev(asep_gnn* g, int n_pages, const asep_gnn_p
         imgs[b] = pages[b].d_image;
         outs[b] = (float*)g->vis_pool.get((size_t)h * w * ncls * sizeof(float));      // backbone logits (not used by the graph)
     }
-    int rc = reserve_u_cat(g, nu);
-    if (!rc && nef) rc = reserve_ef_cat(g, nef);
+    int rc = reserve_floats(&g->d_u_cat, &g->u_cat_cap, nu);
+    if (!rc && nef) rc = reserve_floats(&g->d_ef_cat, &g->ef_cat_cap, nef);
     if (rc) return rc;
-    // ONE grouped backbone forward for all pages (every layer is one launch over the page list), then per page the ROI
-    // kernels and the graph, queued back to back on the same stream
+    // ONE grouped backbone forward for all pages (every layer is one launch over the page list), then per page the generated maps, the ROI
+    // kernels and the graph -- the single-page call's launches -- queued back to back on the same stream
     rc = asep_aru_forward_batch_dev(g->backbone, n_pages, imgs.data(), h, w, outs.data(), nullptr, nullptr, 0.f, s);
     if (rc) return rc;
-    // page lanes: ROI kernels + graph of page b on lane b % L, forked behind the backbone, joined into s at the end
-    const int L = std::max(1, std::min(g->n_page_lanes, n_pages));
-    if (L > 1) {
-        while ((int)g->page_lanes.size() < L) {
-            std::unique_ptr<asep_gnn::PageLane> pl(new asep_gnn::PageLane());
-            ASEP_HIP_CHECK(hipStreamCreateWithFlags(&pl->s, hipStreamNonBlocking));
-            ASEP_HIP_CHECK(hipEventCreateWithFlags(&pl->done, hipEventDisableTiming));
-            g->page_lanes.push_back(std::move(pl));
-        }
-        if (!g->ev_fork) ASEP_HIP_CHECK(hipEventCreateWithFlags(&g->ev_fork, hipEventDisableTiming));
-        ASEP_HIP_CHECK(hipEventRecord(g->ev_fork, s));
-        for (int l = 0; l < L; ++l) ASEP_HIP_CHECK(hipStreamWaitEvent(g->page_lanes[l]->s, g->ev_fork, 0));
-    }
     float* d_u = g->d_u_cat;
     float* d_efc = g->d_ef_cat;
-#ifdef ASEP_ABLATION
-    if (L == 1 && g->batch_graph && n_pages > 1 && g->vise_total == 0 && g->n_generated == 0 && graph_batch_eligible(g)) {
-        // stage by stage over all pages (forward_batch_impl): ROI kernels per feature map, steps, classifier as one launch each
-        const int U = g->Uin, ugc = U - g->vis_total;
-        g->stream = s;
-        g->pool.begin();
-        for (int b0 = 0; b0 < n_pages; b0 += GNN_BATCH) {
-            const int nb = std::min(GNN_BATCH, n_pages - b0);
-            GraphCtx cx[GNN_BATCH];
-            int maxN = 0;
-            float* du = d_u;
-            for (int b = 0; b < nb; ++b) {
-                const asep_gnn_page& q = pages[b0 + b];
-                if (ugc > 0) hipLaunchKernelGGL(gnn_copy_cols_kernel, dim3(cdiv(q.N * ugc, 256)), dim3(256), 0, s, q.d_node_feat, q.N, ugc, du, U);
-                cx[b].N = q.N; cx[b].E = q.E; cx[b].R = q.R;
-                cx[b].d_u = du; cx[b].d_fed = du; cx[b].d_ef = q.d_edge_feat;
-                cx[b].d_edges_in = q.d_edges; cx[b].d_rel = q.d_relations; cx[b].d_out = q.d_probs_out;
-                du += (size_t)q.N * U;
-                maxN = std::max(maxN, q.N);
-            }
-            int col = ugc;
-            for (size_t i = 0; i < g->vis_names.size(); ++i) {
-                GnnBatch<RoiArgs> ba{};
-                int any_bf = -1;
-                for (int b = 0; b < nb; ++b) {
-                    const asep_gnn_page& q = pages[b0 + b];
-                    const std::string prefix = (b0 + b) ? "p" + std::to_string(b0 + b) + "/" : std::string();
-                    const float* fm = nullptr;
-                    int dims[3];
-                    int bf = 0;
-                    rc = aru_endpoint_dev(g->backbone, (prefix + g->vis_names[i]).c_str(), &fm, dims, &bf);
-                    if (rc) return rc;
-                    if (dims[2] != g->vis_C[i]) { set_error("end point %s has %d channels, expected %d", g->vis_names[i].c_str(), dims[2], g->vis_C[i]); return ASEP_ERR_ARG; }
-                    if (any_bf >= 0 && any_bf != bf) { set_error("end points of one call differ in precision"); return ASEP_ERR_ARG; }
-                    any_bf = bf;
-                    RoiArgs& a = ba.p[b];
-                    a.fm = fm; a.fh = dims[0]; a.fw = dims[1]; a.C = dims[2];
-                    a.regions = q.d_regions; a.P = P; a.npts = q.d_num_points; a.Wc = g->vis_W[i]; a.bc = g->vis_b[i]; a.d = g->vis_d[i];
-                    a.u_out = const_cast<float*>(cx[b].d_u); a.ustride = U; a.col0 = col; a.vmax_out = nullptr;
-                    ba.nx[b] = q.N;
-                }
-                if (any_bf) hipLaunchKernelGGL(gnn_roi_compress_kernel_batch<true>, dim3(maxN, nb), dim3(256), 0, s, ba);
-                else hipLaunchKernelGGL(gnn_roi_compress_kernel_batch<false>, dim3(maxN, nb), dim3(256), 0, s, ba);
-                col += g->vis_d[i];
-            }
-            rc = forward_batch_impl(g, g->pool, nb, cx, s);
-            if (rc) return rc;
-            d_u = du;
-        }
-        return ASEP_OK;
-    }
-#endif
-    for (int b = 0; b < n_pages; ++b) {
-        const asep_gnn_page& q = pages[b];
-        hipStream_t ls = L > 1 ? g->page_lanes[b % L]->s : s;
-        BufferPool& lp = L > 1 ? g->page_lanes[b % L]->pool : g->pool;
-        const std::string prefix = b ? "p" + std::to_string(b) + "/" : std::string();
-        // generated maps page by page, the same two launches as the single-page call: on one stream the pages share the arena's buffers
-        // (page b + 1's generator is ordered behind page b's ROI kernels), on page lanes every page keeps its own
-        if (b == 0 || L == 1) g->fmap_pool.begin();
-        rc = generate_maps_dev(g, prefix, ls);
-        if (rc) return rc;
-        rc = visual_rois_dev(g, q.N, q.d_node_feat, prefix, q.d_regions, P, q.d_num_points, d_u, ls);
-        if (rc) return rc;
-        const float* d_ef = q.d_edge_feat;
-        if (g->vise_total > 0 && q.E > 0) {
-            rc = visual_edge_rois_dev(g, q.E, q.d_edge_feat, prefix, q.d_edge_regions, P, q.d_edge_num_points, d_efc, ls);
-            if (rc) return rc;
-            d_ef = d_efc;
-            d_efc += (size_t)q.E * g->Ed;
-        }
-        rc = forward_impl(g, lp, q.N, q.E, q.d_edges, d_u, d_ef, q.R, q.d_relations, q.d_probs_out, ls);
-        if (rc) return rc;
-        d_u += (size_t)q.N * g->Uin;
-    }
-    if (L > 1) {
-        for (int l = 0; l < L; ++l) {
-            ASEP_HIP_CHECK(hipEventRecord(g->page_lanes[l]->done, g->page_lanes[l]->s));
-            ASEP_HIP_CHECK(hipStreamWaitEvent(s, g->page_lanes[l]->done, 0));
-        }
-        g->stream = s;                                       // everything the lanes queued is ordered in front of what follows on s
-    }
+    for (int b = 0; b < n_pages; ++b)
+        if ((rc = visual_page_dev(g, pages[b], page_prefix(b), P, &d_u, &d_efc, s))) return rc;
     return ASEP_OK;
     ASEP_GUARD_END
 }
@@ -1451,12 +1231,7 @@ int visual_batch2_impl(asep_gnn* g, const char* fn, int n_pages, std::vector<ase
                 return ASEP_ERR_ARG;
             }
         }
-        if (q.N < 1 || q.E < 0 || q.R < 0 || (!scans && !q.d_image) || !q.d_regions || !q.d_num_points || (ug > 0 && !q.d_node_feat) || (q.E > 0 && !q.d_edges) ||
-            (q.R > 0 && !q.d_probs_out) || (g->Ed_fed > 0 && q.E > 0 && !q.d_edge_feat) ||
-            (g->vise_total > 0 && q.E > 0 && (!q.d_edge_regions || !q.d_edge_num_points))) {
-            set_error("%s: bad argument in page %d", fn, b);
-            return ASEP_ERR_ARG;
-        }
+        if (int rc = check_visual_page(g, fn, b, q, !scans)) return rc;
         if ((size_t)q.N * q.N > (size_t)1 << 30) { set_error("%s: page %d: N=%d too large for the dense edge table", fn, b, q.N); return ASEP_ERR_UNSUPPORTED; }
         logit_items[b] = (size_t)h[b] * w[b] * ncls;
         nu += (size_t)q.N * U;
@@ -1488,8 +1263,8 @@ int visual_batch2_impl(asep_gnn* g, const char* fn, int n_pages, std::vector<ase
     std::vector<const float*> imgs(n_pages);
     std::vector<float*> outs(n_pages);
     for (int b = 0; b < n_pages; ++b) { imgs[b] = pages[b].d_image; outs[b] = d_logits + off[b]; }
-    int rc = reserve_u_cat(g, nu);
-    if (!rc && nef) rc = reserve_ef_cat(g, nef);
+    int rc = reserve_floats(&g->d_u_cat, &g->u_cat_cap, nu);
+    if (!rc && nef) rc = reserve_floats(&g->d_ef_cat, &g->ef_cat_cap, nef);
     if (rc) return rc;
     g->stream = s;
     aru_prof_stream(g->backbone, s);
@@ -1545,37 +1320,22 @@ int visual_batch2_impl(asep_gnn* g, const char* fn, int n_pages, std::vector<ase
 
     // ---- every map of every page: the backbone's end points (known once the forward is queued), the generated ones in one arena ----
     std::vector<asep_gnn::PageRec> recs(n_pages);
-    struct Gen { size_t n1 = 0, n2 = 0; FmapDims d{}; asep_gnn::FmapRef src; float* mid = nullptr; };
-    std::vector<Gen> gens((size_t)n_pages * n_maps);
+    std::vector<std::vector<FmapStep>> plans(n_pages);
+    std::vector<const float*> src_p((size_t)n_pages * n_maps, nullptr);   // per generated (page, map): the end point its 1x1 reads, if it reads one
+    std::vector<float*> mid(src_p.size(), nullptr);                       // ... and the 1x1's output
     std::vector<size_t> arena_items;                                  // per generated (page, map): the 1x1's output, then the map itself
     for (int b = 0; b < n_pages; ++b) {
-        const std::string prefix = b ? "p" + std::to_string(b) + "/" : std::string();
-        recs[b].maps.assign(n_maps, asep_gnn::FmapRef{});
+        std::vector<const float*> end_p;
+        rc = page_map_plan(g, page_prefix(b), plans[b], end_p);
+        if (rc) return rc;
+        recs[b].maps.resize(n_maps);
         for (size_t i = 0; i < n_maps; ++i) {
-            const asep_gnn::FmapGen& G = g->vis_gen[i];
-            asep_gnn::FmapRef src{};
-            if (G.depth < 0 || G.stride == 1) {
-                int dims[3];
-                rc = aru_endpoint_dev(g->backbone, (prefix + g->vis_names[i]).c_str(), &src.p, dims, &src.bf);
-                if (rc) return rc;
-                src.fh = dims[0]; src.fw = dims[1]; src.C = dims[2];
-            } else {
-                src = recs[b].maps[i - 1];                          // (a generated one's address follows below)
-            }
-            if (G.depth < 0) {
-                if (src.C != g->vis_C[i]) { set_error("end point %s has %d channels, expected %d", g->vis_names[i].c_str(), src.C, g->vis_C[i]); return ASEP_ERR_ARG; }
-                recs[b].maps[i] = src;
-                continue;
-            }
-            if (src.C != G.Cin) { set_error("feature map %zu reads %d channels, its 1x1 filter was loaded for %d", i, src.C, G.Cin); return ASEP_ERR_ARG; }
-            Gen& ge = gens[(size_t)b * n_maps + i];
-            ge.src = src;
-            ge.d = fmap_dims(src.fh, src.fw, G.stride);
-            ge.n1 = (size_t)src.fh * src.fw * (G.depth / 2);
-            ge.n2 = (size_t)ge.d.oh * ge.d.ow * G.depth;
-            arena_items.push_back(ge.n1);
-            arena_items.push_back(ge.n2);
-            recs[b].maps[i] = asep_gnn::FmapRef{nullptr, ge.d.oh, ge.d.ow, G.depth, 0};
+            const FmapStep& k = plans[b][i];
+            recs[b].maps[i] = map_ref(k.generated ? nullptr : end_p[i], k.out);   // (a generated one's address follows below)
+            if (!k.generated) continue;
+            src_p[(size_t)b * n_maps + i] = end_p[i];
+            arena_items.push_back(k.n1);
+            arena_items.push_back(k.n2);
         }
     }
     if (g->n_generated) {
@@ -1586,11 +1346,9 @@ int visual_batch2_impl(asep_gnn* g, const char* fn, int n_pages, std::vector<ase
         size_t k = 0;
         for (int b = 0; b < n_pages; ++b)
             for (size_t i = 0; i < n_maps; ++i) {
-                if (g->vis_gen[i].depth < 0) continue;
-                Gen& ge = gens[(size_t)b * n_maps + i];
-                ge.mid = base + aoff[k];
+                if (!plans[b][i].generated) continue;
+                mid[(size_t)b * n_maps + i] = base + aoff[k];
                 recs[b].maps[i].p = base + aoff[k + 1];
-                if (g->vis_gen[i].stride == 2) ge.src.p = recs[b].maps[i - 1].p;
                 k += 2;
             }
     }
@@ -1605,21 +1363,18 @@ int visual_batch2_impl(asep_gnn* g, const char* fn, int n_pages, std::vector<ase
         std::vector<FmapPage> p1(n_pages), p3(n_pages);
         std::vector<size_t> it1(n_pages), it3(n_pages);
         FmapLaunch& L = fl[i];
-        L.bf = gens[i].src.bf != 0;
-        const int half = G.depth / 2;
+        L.bf = plans[0][i].in.bf != 0;
         for (int b = 0; b < n_pages; ++b) {
-            const Gen& ge = gens[(size_t)b * n_maps + i];
-            if ((ge.src.bf != 0) != L.bf) { set_error("%s: end points of one call differ in precision", fn); return ASEP_ERR_ARG; }
-            p1[b] = FmapPage{ge.src.p, ge.mid, ge.d.ih, ge.d.iw, ge.d.ih, ge.d.iw, 0, 0};
-            p3[b] = FmapPage{ge.mid, const_cast<float*>(recs[b].maps[i].p), ge.d.ih, ge.d.iw, ge.d.oh, ge.d.ow, ge.d.pad_t, ge.d.pad_l};
-            it1[b] = ge.n1; it3[b] = ge.n2;
-            L.fl1 += 2.0 * (double)ge.n1 * G.Cin;
-            L.by1 += (double)ge.d.ih * ge.d.iw * G.Cin * (L.bf ? 2 : 4) + 4.0 * (double)ge.n1;
-            L.fl3 += 2.0 * (double)ge.n2 * 9 * half;
-            L.by3 += 4.0 * (double)ge.n1 + 4.0 * (double)ge.n2;
+            const FmapStep& k = plans[b][i];
+            if ((k.in.bf != 0) != L.bf) { set_error("%s: end points of one call differ in precision", fn); return ASEP_ERR_ARG; }
+            float* m1 = mid[(size_t)b * n_maps + i];
+            p1[b] = FmapPage{k.src < 0 ? src_p[(size_t)b * n_maps + i] : recs[b].maps[k.src].p, m1, k.d.ih, k.d.iw, k.d.ih, k.d.iw, 0, 0};
+            p3[b] = FmapPage{m1, const_cast<float*>(recs[b].maps[i].p), k.d.ih, k.d.iw, k.d.oh, k.d.ow, k.d.pad_t, k.d.pad_l};
+            it1[b] = k.n1; it3[b] = k.n2;
+            L.fl1 += k.fl1; L.by1 += k.io1; L.fl3 += k.fl3; L.by3 += k.io3;
         }
-        L.by1 += 4.0 * ((double)G.Cin * half + half);
-        L.by3 += 4.0 * (9.0 * half * G.depth + G.depth);
+        L.by1 += plans[0][i].w1;                                      // (the filter and bias once per launch)
+        L.by3 += plans[0][i].w3;
         std::vector<int32_t> b1, b3;
         if (!page_unit_table(it1.data(), n_pages, 256, b1) || !page_unit_table(it3.data(), n_pages, 256, b3)) {
             set_error("%s: feature map %zu of the %d pages is too large for one launch", fn, i, n_pages);
@@ -1632,6 +1387,7 @@ int visual_batch2_impl(asep_gnn* g, const char* fn, int n_pages, std::vector<ase
     struct RoiLaunch { std::vector<RoiArgs> e; std::vector<size_t> rows; size_t eoff = 0, boff = 0; int grid = 0; };
     RoiLaunch roi[2];                                               // [0] fp32 maps, [1] bf16 maps
     {
+        const RoiSide nodes = node_side(g), edges = edge_side(g);
         size_t urow = 0, efrow = 0;
         for (int b = 0; b < n_pages; ++b) {
             const asep_gnn_page& q = pages[b];
@@ -1639,18 +1395,11 @@ int visual_batch2_impl(asep_gnn* g, const char* fn, int n_pages, std::vector<ase
             int col = ug, ecol = g->Ed_fed;
             for (size_t i = 0; i < n_maps; ++i) {
                 const asep_gnn::FmapRef& m = recs[b].maps[i];
-                RoiArgs a{};
-                a.fm = m.p; a.fh = m.fh; a.fw = m.fw; a.C = m.C;
-                a.regions = q.d_regions; a.P = P; a.npts = q.d_num_points; a.Wc = g->vis_W[i]; a.bc = g->vis_b[i]; a.d = g->vis_d[i];
-                a.u_out = g->d_u_cat + urow * U; a.ustride = U; a.col0 = col; a.vmax_out = nullptr;
-                roi[m.bf ? 1 : 0].e.push_back(a);
+                roi[m.bf ? 1 : 0].e.push_back(roi_entry(m, q.d_regions, P, q.d_num_points, nodes, i, g->d_u_cat + urow * U, col));
                 roi[m.bf ? 1 : 0].rows.push_back((size_t)q.N);
                 col += g->vis_d[i];
                 if (g->vise_total > 0 && q.E > 0) {
-                    RoiArgs c = a;
-                    c.regions = q.d_edge_regions; c.npts = q.d_edge_num_points; c.Wc = g->vise_W[i]; c.bc = g->vise_b[i]; c.d = g->vise_d[i];
-                    c.u_out = g->d_ef_cat + efrow * Ed; c.ustride = Ed; c.col0 = ecol;
-                    roi[m.bf ? 1 : 0].e.push_back(c);
+                    roi[m.bf ? 1 : 0].e.push_back(roi_entry(m, q.d_edge_regions, P, q.d_edge_num_points, edges, i, g->d_ef_cat + efrow * Ed, ecol));
                     roi[m.bf ? 1 : 0].rows.push_back((size_t)q.E);
                     ecol += g->vise_d[i];
                 }
@@ -1731,7 +1480,7 @@ int visual_batch2_impl(asep_gnn* g, const char* fn, int n_pages, std::vector<ase
         d_u += (size_t)q.N * U;
     }
     g->fmap_last = recs[n_pages - 1].maps;                          // as after the old entry: the last page's maps
-    g->fmap_last_prefix = n_pages > 1 ? "p" + std::to_string(n_pages - 1) + "/" : std::string();
+    g->fmap_last_prefix = page_prefix(n_pages - 1);
     g->batch_pages = std::move(recs);
     g->batch_serial = g->fwd_serial;
     return ASEP_OK;
@@ -1744,22 +1493,6 @@ const asep_gnn::PageRec* batch_page(asep_gnn* g, const char* fn, int page) {
     return &g->batch_pages[page];
 }
 
-int copy_map_out(asep_gnn* g, const char* fn, const asep_gnn::FmapRef& r, float* out, size_t max_floats, int32_t dims[3]) {
-    dims[0] = r.fh; dims[1] = r.fw; dims[2] = r.C;
-    const size_t n = (size_t)r.fh * r.fw * r.C;
-    if (!out) return ASEP_OK;
-    if (max_floats < n) { set_error("%s: buffer too small (%zu floats needed)", fn, n); return ASEP_ERR_ARG; }
-    ASEP_HIP_CHECK(hipStreamSynchronize(g->stream));
-    if (r.bf) {
-        std::vector<uint16_t> hb(n);
-        ASEP_HIP_CHECK(hipMemcpy(hb.data(), r.p, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; ++i) { const uint32_t u = (uint32_t)hb[i] << 16; memcpy(out + i, &u, 4); }
-    } else {
-        ASEP_HIP_CHECK(hipMemcpy(out, r.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    return ASEP_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1769,11 +1502,7 @@ int asep_gnn_get_page_node_features(asep_gnn* g, int page, float* out, size_t ma
     const asep_gnn::PageRec* r = batch_page(g, "asep_gnn_get_page_node_features", page);
     if (!r) return ASEP_ERR_ARG;
     if (!out) { set_error("asep_gnn_get_page_node_features: out is NULL"); return ASEP_ERR_ARG; }
-    const size_t n = (size_t)r->N * g->Uin;
-    if (max_floats < n) { set_error("asep_gnn_get_page_node_features: buffer too small"); return ASEP_ERR_ARG; }
-    ASEP_HIP_CHECK(hipStreamSynchronize(g->stream));
-    ASEP_HIP_CHECK(hipMemcpy(out, g->d_u_cat + r->u_off, n * sizeof(float), hipMemcpyDeviceToHost));
-    return ASEP_OK;
+    return copy_node_features_out(g, "asep_gnn_get_page_node_features", r->u_off, r->N, out, max_floats);
     ASEP_GUARD_END
 }
 
@@ -1840,11 +1569,7 @@ int asep_gnn_forward_visual(asep_gnn* g, int N, int E, const int32_t* edges, con
 int asep_gnn_get_node_features(asep_gnn* g, float* out, size_t max_floats) {
     ASEP_GUARD_BEGIN
     if (!g || !out || !g->d_u_cat) { set_error("asep_gnn_get_node_features: no visual forward has run"); return ASEP_ERR_ARG; }
-    const size_t n = (size_t)g->N * g->Uin;
-    if (max_floats < n) { set_error("asep_gnn_get_node_features: buffer too small"); return ASEP_ERR_ARG; }
-    ASEP_HIP_CHECK(hipStreamSynchronize(g->stream));
-    ASEP_HIP_CHECK(hipMemcpy(out, g->d_u_cat, n * sizeof(float), hipMemcpyDeviceToHost));
-    return ASEP_OK;
+    return copy_node_features_out(g, "asep_gnn_get_node_features", 0, g->N, out, max_floats);
     ASEP_GUARD_END
 }
 

@@ -202,17 +202,6 @@ typedef float gf32x4 __attribute__((ext_vector_type(4)));
 enum { GQ_ZERO = 0, GQ_UI, GQ_UJ, GQ_DU, GQ_DU2, GQ_EF, GQ_HI, GQ_HJ, GQ_DH, GQ_DH2 };
 constexpr int GNN_MAXCH = 16;          // K chunks of 16 slots (U <= 8, Ed <= 4 -> 11 chunks)
 
-#ifdef ASEP_ABLATION   // (make ABLATION=1: the stage-by-stage form of the batched relation nets, measured and not adopted -- DESIGN_LESSONS 36)
-// Several pages' launches of one graph kernel as ONE launch (asep_gnn_forward_visual_batch_dev): blockIdx.y = page, p[page] = the arguments the
-// per-page launch would get, nx[page] = its grid size along x (blocks beyond it leave at once).  By value in the kernel arguments (< 4 KB).
-constexpr int GNN_BATCH = 16;
-template <class A>
-struct GnnBatch {
-    A p[GNN_BATCH];
-    int nx[GNN_BATCH];
-};
-#endif
-
 struct StepArgs {
     const float* u; const float* h_in; const float* c_in; const float* ef;
     const int* tptr; const int* tsrc; const int* tfirst;
@@ -357,12 +346,6 @@ __device__ __forceinline__ void gnn_step_kernel_body(const StepArgs& a, const in
     }
 }
 __global__ __launch_bounds__(256) void gnn_step_kernel(const StepArgs a) { gnn_step_kernel_body(a, (int)blockIdx.x, (int)gridDim.x); }
-#ifdef ASEP_ABLATION
-__global__ __launch_bounds__(256) void gnn_step_kernel_batch(const GnnBatch<StepArgs> b) {
-    if ((int)blockIdx.x >= b.nx[blockIdx.y]) return;
-    gnn_step_kernel_body(b.p[blockIdx.y], (int)blockIdx.x, b.nx[blockIdx.y]);
-}
-#endif
 
 
 // ------------------------------------------------------------------------------------------------
@@ -515,12 +498,6 @@ __device__ __forceinline__ void gnn_step_big_kernel_body(const StepBigArgs& a, c
     }
 }
 __global__ __launch_bounds__(256) void gnn_step_big_kernel(const StepBigArgs a) { gnn_step_big_kernel_body(a, (int)blockIdx.x, (int)gridDim.x); }
-#ifdef ASEP_ABLATION
-__global__ __launch_bounds__(256) void gnn_step_big_kernel_batch(const GnnBatch<StepBigArgs> b) {
-    if ((int)blockIdx.x >= b.nx[blockIdx.y]) return;
-    gnn_step_big_kernel_body(b.p[blockIdx.y], (int)blockIdx.x, b.nx[blockIdx.y]);
-}
-#endif
 
 
 // ------------------------------------------------------------------------------------------------
@@ -1093,28 +1070,6 @@ __global__ __launch_bounds__(256) void gnn_pair_pre_kernel(const float* __restri
     }
 }
 
-struct PairPreArgs {
-    const float* h; int N, H; const float* W1; int H1; float* Pt; float* Qt;
-};
-#ifdef ASEP_ABLATION
-// gnn_pair_pre_kernel for several pages (GnnBatch): the same grid-stride loop per page, nx[page] blocks
-__global__ __launch_bounds__(256) void gnn_pair_pre_kernel_batch(const GnnBatch<PairPreArgs> b) {
-    if ((int)blockIdx.x >= b.nx[blockIdx.y]) return;
-    const PairPreArgs& a = b.p[blockIdx.y];
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.N * a.H1; i += b.nx[blockIdx.y] * 256) {
-        const int n = i % a.N, k = i / a.N;
-        float p = 0.f, q = 0.f;
-        for (int d = 0; d < a.H; ++d) {
-            const float hv = a.h[(size_t)n * a.H + d];
-            p = fmaf(hv, a.W1[d * a.H1 + k], p);
-            q = fmaf(hv, a.W1[(a.H + d) * a.H1 + k], q);
-        }
-        a.Pt[(size_t)k * a.N + n] = p;
-        a.Qt[(size_t)k * a.N + n] = q;
-    }
-}
-#endif
-
 struct PairArgs {
     const float* Pt; const float* Qt;   // [H1][N]
     const float* b1;                    // [H1]
@@ -1175,13 +1130,6 @@ __device__ __forceinline__ void gnn_pair_cls_kernel_body(const PairArgs& a, cons
 }
 template <int H1, int H2, int NC>
 __global__ __launch_bounds__(256) void gnn_pair_cls_kernel(const PairArgs a) { gnn_pair_cls_kernel_body<H1, H2, NC>(a, (int)blockIdx.x, (int)gridDim.x); }
-#ifdef ASEP_ABLATION
-template <int H1, int H2, int NC>
-__global__ __launch_bounds__(256) void gnn_pair_cls_kernel_batch(const GnnBatch<PairArgs> b) {
-    if ((int)blockIdx.x >= b.nx[blockIdx.y]) return;
-    gnn_pair_cls_kernel_body<H1, H2, NC>(b.p[blockIdx.y], (int)blockIdx.x, b.nx[blockIdx.y]);
-}
-#endif
 
 
 // any classifier widths (trainer_rel.py:17 num_hidden_units is a free parameter): one thread per pair, the second
@@ -1380,13 +1328,6 @@ __global__ __launch_bounds__(256) void gnn_roi_compress_pages_kernel(const RoiPa
     const int b0 = t.begin[k];
     gnn_roi_compress_kernel_body<BF>(a, (int)blockIdx.x - b0, t.begin[k + 1] - b0);
 }
-#ifdef ASEP_ABLATION
-template <bool BF>
-__global__ __launch_bounds__(256) void gnn_roi_compress_kernel_batch(const GnnBatch<RoiArgs> b) {
-    if ((int)blockIdx.x >= b.nx[blockIdx.y]) return;
-    gnn_roi_compress_kernel_body<BF>(b.p[blockIdx.y], (int)blockIdx.x, b.nx[blockIdx.y]);
-}
-#endif
 
 
 // graph_gnn.py:102-109 compress_node_feature_dim: y[n][d] = tanh(b[d] + sum_k x[n][k] W[k][d])  (layers.ff_layer with tanh)

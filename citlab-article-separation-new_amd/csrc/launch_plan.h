@@ -95,6 +95,50 @@ inline FmapDims fmap_dims(int ih, int iw, int stride) {
     return d;
 }
 
+// The maps of one page's layout (feature_map_generators.py:140-194).  Map i is a backbone end point (depth < 0) or generated with two
+// convolutions: a 1x1 to depth / 2 channels, then a 3x3 of stride 1 (reads its own end point) or 2 (reads map i - 1) to depth channels.
+struct FmapSpec { int depth, stride, Cin; };          // Cin: the channels the 1x1 filter was loaded for
+struct FmapShape { int fh, fw, C, bf; };              // bf: bf16 elements (an end point of a bf16 backbone); generated maps are fp32
+struct FmapStep {
+    bool generated, bad_channels;   // bad_channels: what a generated map reads is not Cin wide / an end point is not want_C[i] wide
+    int src;                        // what a generated map reads: -1 = its own end point, else map `src`
+    FmapShape in, out;              // what the 1x1 reads (generated maps only), and the map itself
+    FmapDims d;                     // the 3x3's geometry
+    size_t n1, n2;                  // outputs of the 1x1 and of the 3x3
+    // the profiler's figures per launch: flops; algorithmic bytes of this page (the input once, the output once); the filter and bias (once per launch)
+    double fl1, io1, w1, fl3, io3, w3;
+};
+// ends[i]: the end point of map i where one is read (depth < 0 or stride 1); want_C[i]: the channels map i was attached with
+inline std::vector<FmapStep> fmap_plan(const FmapSpec* spec, const FmapShape* ends, const int* want_C, int n) {
+    std::vector<FmapStep> plan((size_t)n, FmapStep{});
+    for (int i = 0; i < n; ++i) {
+        FmapStep& k = plan[(size_t)i];
+        const FmapSpec& G = spec[i];
+        k.src = -1;
+        if (G.depth < 0) {
+            k.out = ends[i];
+            k.bad_channels = k.out.C != want_C[i];
+            continue;
+        }
+        k.generated = true;
+        if (G.stride != 1) k.src = i - 1;
+        k.in = k.src < 0 ? ends[i] : plan[(size_t)k.src].out;
+        k.bad_channels = k.in.C != G.Cin;
+        const int half = G.depth / 2;
+        k.d = fmap_dims(k.in.fh, k.in.fw, G.stride);
+        k.out = FmapShape{k.d.oh, k.d.ow, G.depth, 0};
+        k.n1 = (size_t)k.in.fh * k.in.fw * half;
+        k.n2 = (size_t)k.d.oh * k.d.ow * G.depth;
+        k.fl1 = 2.0 * (double)k.n1 * k.in.C;
+        k.io1 = (double)k.in.fh * k.in.fw * k.in.C * (k.in.bf ? 2 : 4) + 4.0 * (double)k.n1;
+        k.w1 = 4.0 * ((double)k.in.C * half + half);
+        k.fl3 = 2.0 * (double)k.n2 * 9 * half;
+        k.io3 = 4.0 * (double)k.n1 + 4.0 * (double)k.n2;
+        k.w3 = 4.0 * (9.0 * half * G.depth + G.depth);
+    }
+    return plan;
+}
+
 // begin[0 .. n] for pages of items[b] items in units of per_unit items (the last unit of a page is partial when per_unit does not divide its
 // items).  False when the units do not fit one launch (a 31-bit grid): begin is then not to be used.
 inline bool page_unit_table(const size_t* items, int n, size_t per_unit, std::vector<int32_t>& begin) {

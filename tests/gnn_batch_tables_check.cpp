@@ -1,5 +1,5 @@
 // Host check of the page-table builders csrc/launch_plan.h gained for the relation net's batched visual stages (same_pad3, fmap_dims,
-// page_unit_table, page_of_unit, arena_offsets) against brute-force restatements.  Plain C++17, no HIP: tests/test_gnn_batch_host.py builds it
+// fmap_plan, page_unit_table, page_of_unit, arena_offsets) against brute-force restatements.  Plain C++17, no HIP: tests/test_gnn_batch_host.py builds it
 // with the host compiler under the address and undefined-behaviour sanitizers.  Called as `check stride channels h0 w0 h1 w1 ...` it also prints
 // the tables of those map sizes for the numpy restatement of the test.
 #include <cstdio>
@@ -60,6 +60,66 @@ int main(int argc, char** argv) {
         CHECK(d.oh == 1 && d.ow == 1 && d.pad_t == 1 && d.pad_l == 1);
         d = fmap_dims(0, 5, 2);
         CHECK(d.oh == 0 && d.ow == 3);
+    }
+    // ---- fmap_plan: one page's maps for the layout [end point, depth 8 stride 1, depth 6 stride 2, depth 2 stride 2] over end points of four
+    //      sizes, fp32 and bf16, against fmap_dims and the products; heap arrays of their exact length ----
+    {
+        const int n = 4, C = 5;                                      // the end points' channels
+        const FmapSpec layout[n] = {{-1, 1, 0}, {8, 1, C}, {6, 2, 8}, {2, 2, 6}};
+        const int want_src[n] = {-1, -1, 1, 2};
+        const int sizes[4][2] = {{1, 1}, {1, 5}, {5, 4}, {36, 27}};
+        for (const auto& hw : sizes)
+            for (int bf = 0; bf <= 1; ++bf)
+                for (int wrong = -1; wrong < n; ++wrong) {           // -1: every filter fits; else map `wrong` was loaded for (or attached with) one channel more
+                    std::unique_ptr<FmapSpec[]> spec(new FmapSpec[n]);
+                    std::unique_ptr<FmapShape[]> ends(new FmapShape[n]);
+                    std::unique_ptr<int[]> want_C(new int[n]);
+                    for (int i = 0; i < n; ++i) {
+                        spec[i] = layout[i];
+                        ends[i] = i < 2 ? FmapShape{hw[0], hw[1], C, bf} : FmapShape{-7, -7, -7, -7};   // (maps 2 and 3 read no end point)
+                        want_C[i] = layout[i].depth < 0 ? C : layout[i].depth;
+                    }
+                    if (wrong == 0) ++want_C[0];
+                    else if (wrong > 0) ++spec[wrong].Cin;
+                    const std::vector<FmapStep> plan = fmap_plan(spec.get(), ends.get(), want_C.get(), n);
+                    CHECK((int)plan.size() == n);
+                    CHECK(!plan[0].generated && plan[0].out.fh == hw[0] && plan[0].out.fw == hw[1] && plan[0].out.C == C && plan[0].out.bf == bf);
+                    for (int i = 0; i < n; ++i) CHECK(plan[i].bad_channels == (i == wrong));
+                    FmapShape in{hw[0], hw[1], C, bf};                // what map 1 reads; then each map's output
+                    for (int i = 1; i < n; ++i) {
+                        const FmapStep& k = plan[i];
+                        const int depth = layout[i].depth, half = depth / 2;
+                        const FmapDims d = fmap_dims(in.fh, in.fw, layout[i].stride);
+                        CHECK(k.generated && k.src == want_src[i]);
+                        CHECK(k.in.fh == in.fh && k.in.fw == in.fw && k.in.C == in.C && k.in.bf == in.bf);
+                        CHECK(k.d.ih == d.ih && k.d.iw == d.iw && k.d.oh == d.oh && k.d.ow == d.ow && k.d.pad_t == d.pad_t && k.d.pad_l == d.pad_l);
+                        CHECK(k.n1 == (size_t)in.fh * in.fw * half && k.n2 == (size_t)d.oh * d.ow * depth);
+                        CHECK(k.out.fh == d.oh && k.out.fw == d.ow && k.out.C == depth && k.out.bf == 0);
+                        CHECK(k.fl1 == 2.0 * k.n1 * in.C && k.fl3 == 2.0 * k.n2 * 9 * half);
+                        CHECK(k.io1 == (double)in.fh * in.fw * in.C * (in.bf ? 2 : 4) + 4.0 * k.n1 && k.io3 == 4.0 * k.n1 + 4.0 * k.n2);
+                        CHECK(k.w1 == 4.0 * (in.C * half + half) && k.w3 == 4.0 * (9 * half * depth + depth));
+                        in = k.out;
+                    }
+                }
+        {   // the 36 x 27 end point's chain, spelled out: 36 x 27 x 8, 18 x 14 x 6, 9 x 7 x 2
+            const FmapShape ends[n] = {{36, 27, C, 1}, {36, 27, C, 1}, {}, {}};
+            const int want_C[n] = {C, 8, 6, 2};
+            const std::vector<FmapStep> plan = fmap_plan(layout, ends, want_C, n);
+            CHECK(plan[1].out.fh == 36 && plan[1].out.fw == 27 && plan[1].d.pad_t == 1 && plan[1].d.pad_l == 1 && plan[1].n1 == 36 * 27 * 4 && plan[1].n2 == 36 * 27 * 8);
+            CHECK(plan[2].out.fh == 18 && plan[2].out.fw == 14 && plan[2].d.pad_t == 0 && plan[2].d.pad_l == 1 && plan[2].n1 == 36 * 27 * 3 && plan[2].n2 == 18 * 14 * 6);
+            CHECK(plan[3].out.fh == 9 && plan[3].out.fw == 7 && plan[3].n1 == 18 * 14 * 1 && plan[3].n2 == 9 * 7 * 2);
+            CHECK(plan[1].in.bf == 1 && plan[2].in.bf == 0 && plan[3].in.bf == 0);      // only the end point is bf16
+        }
+        {   // the default layout (every depth -1): no generated entry, every map its end point
+            const FmapSpec all_ends[3] = {{-1, 1, 0}, {-1, 1, 0}, {-1, 1, 0}};
+            const FmapShape ends[3] = {{5, 4, 16, 0}, {3, 2, 32, 0}, {1, 1, 64, 0}};
+            const int want_C[3] = {16, 32, 64};
+            const std::vector<FmapStep> plan = fmap_plan(all_ends, ends, want_C, 3);
+            for (int i = 0; i < 3; ++i)
+                CHECK(!plan[i].generated && !plan[i].bad_channels && plan[i].src == -1 && plan[i].n1 == 0 && plan[i].n2 == 0 && plan[i].out.fh == ends[i].fh &&
+                      plan[i].out.fw == ends[i].fw && plan[i].out.C == ends[i].C);
+            CHECK(fmap_plan(all_ends, ends, want_C, 0).empty());
+        }
     }
     // ---- page_unit_table / page_of_unit: heap arrays of their exact length ----
     const std::vector<std::vector<size_t>> item_sets = {

@@ -1,5 +1,5 @@
 """The host side of the relation net's pages-per-call path, without a GPU: the page-table builders csrc/launch_plan.h gained
-(same_pad3, fmap_dims, page_unit_table, page_of_unit, arena_offsets) and the parsing of --pages_per_call.
+(same_pad3, fmap_dims, fmap_plan, page_unit_table, page_of_unit, arena_offsets) and the parsing of --pages_per_call.
 
 tests/gnn_batch_tables_check.cpp is a stand-alone program (its own main) compiled with the host C++ compiler under the address and
 undefined-behaviour sanitizers and run as a child process: nothing sanitized is loaded into Python.  It checks the builders against

@@ -44,13 +44,13 @@ def _same(a, b):
     return a.shape == b.shape and np.array_equal(a, b)
 
 
-def _host_pages(cfg, sizes, seed=17):
+def _host_pages(cfg, sizes, seed=17, nodes=NODES):
     """numpy inputs of the pages: a different image, graph and region set each"""
     from citlab_article_separation_new_amd import synth
     rng = np.random.default_rng(seed)
     chans = cfg.backbone_cfg().channels
     pages = []
-    for b, ((h, w), N) in enumerate(zip(sizes, NODES)):
+    for b, ((h, w), N) in enumerate(zip(sizes, nodes)):
         E = 0 if b == 1 else 3 * N                                   # page 1: no interactions
         edges = rng.integers(0, N, size=(E, 2)).astype(np.int32)
         img = synth.synth_page(20 + b, W=w, H=h).astype(np.float32)
@@ -65,7 +65,7 @@ def _host_pages(cfg, sizes, seed=17):
         regions[0, 0, :] = [0.0, 1.0, 1.0, 0.0]                      # x = y = 1.0: floor(1.0 * fw) = fw clamps to the last cell
         regions[0, 1, :] = [0.0, 0.0, 1.0, 1.0]
         npts = np.full(N, P, np.int32)
-        npts[1] = 0                                                  # no points -> cell (0, 0)
+        npts[1:2] = 0                                                # no points -> cell (0, 0)
         eregions = np.zeros((E, 2, P), np.float32)
         for e, (i, j) in enumerate(edges):
             x0, x1 = min(regions[i, 0].min(), regions[j, 0].min()), max(regions[i, 0].max(), regions[j, 0].max())
@@ -213,6 +213,55 @@ def test_four_pages_of_one_size_equal_the_uniform_batch_entry(cases):
     torch.cuda.synchronize()
     for b, (t, _) in enumerate(dev):
         assert np.isfinite(old[b]).all() and _same(t["out"].cpu().numpy(), old[b]), b
+
+
+@pytest.mark.parametrize("dtype,hw", [("f32", (71, 53)), ("bf16", (64, 96))])
+def test_uniform_entry_with_visual_edges_over_stride_1_and_stride_2_maps_equals_the_single_page_calls(dtype, hw):
+    """asep_gnn_forward_visual_batch_dev (pages of ONE size, page by page behind a grouped backbone) on a model with interaction visual
+    features and a layout of an end point, a generated stride-1 map and a generated stride-2 map: three pages of N = 1, 3 and 4 nodes, the
+    second without interactions, P = 4, against asep_gnn_forward_visual_dev bit for bit.  fp32: 71 x 53, the smallest page of this file with
+    a generated stride-2 map; bf16: 64 x 96, the smallest of them that the bf16 backbone is given here (at least 64 both ways, see above).
+
+    The uniform entry has no per-page read-back: asep_gnn_get_feature_map serves the LAST page of a call, asep_gnn_get_node_features the
+    first N(last page) rows of the call's node features.  So the three pages go through the entry in their three rotations: every page is last
+    once (its maps), the probabilities of every page are compared in every call, and the node-feature rows the read-back reaches are compared
+    with the same rows of the single-page results one behind the other.  Row 3 of the four-node page is reached by no three-page call: that
+    page also goes through the entry alone."""
+    import torch
+    from citlab_article_separation_new_amd import gnn_io
+    from citlab_article_separation_new_amd.config import GnnConfig
+    from citlab_article_separation_new_amd.weights import init_gnn_weights
+    cfg = GnnConfig(node_feature_dim=7, mvn=True, visual_layers=[UP1, UP1, ""], visual_layer_depths=[-1, 6, 2], visual_dims=[8, 4, 4], visual_edges=True,
+                    backbone={"compute_dtype": dtype})
+    graph = gnn_io.GnnGraph(init_gnn_weights(cfg, 11, bias_jitter=0.05), cfg)
+    h, w = hw
+    host = _host_pages(cfg, [hw] * 3, seed=23, nodes=[1, 3, 4])
+    assert [p["E"] for p in host] == [3, 0, 12]
+    dev = [_upload(p, cfg.num_classes) for p in host]
+    singles = [_single(graph, t, q, h, w, 3) for t, q in dev]
+    assert [m.shape[2] for m in singles[2][2]] == [cfg.visual_channels()[0], 6, 2]
+    assert singles[2][2][1].shape[:2] == singles[2][2][0].shape[:2] and singles[2][2][2].shape[0] == (singles[2][2][1].shape[0] + 1) // 2   # strides 1 and 2
+    rows_seen = [0, 0, 0]
+    for order in ([0, 1, 2], [1, 2, 0], [2, 0, 1], [2]):
+        for b in order:
+            dev[b][0]["out"].zero_()
+        gnn_io.gnn_forward_visual_batch_dev(graph, [dev[b][1] for b in order], h, w, P)
+        torch.cuda.synchronize()
+        for b in order:
+            p0 = singles[b][0]
+            assert np.isfinite(p0).all() and _same(dev[b][0]["out"].cpu().numpy(), p0), (dtype, order, "probabilities of page", b)
+        last = order[-1]
+        for i in range(3):
+            assert _same(gnn_io.gnn_feature_map(graph, i), singles[last][2][i]), (dtype, order, "feature map", i, "of page", last)
+        n_read = host[last]["N"]
+        want = np.concatenate([singles[b][1] for b in order])[:n_read]
+        assert _same(gnn_io.gnn_node_features(graph, n_read), want), (dtype, order, "node features")
+        left = n_read
+        for b in order:
+            rows_seen[b] = max(rows_seen[b], min(left, host[b]["N"]))
+            left = max(left - host[b]["N"], 0)
+    assert rows_seen == [1, 3, 4]                                     # every row of every page was compared
+    graph.close()
 
 
 def _records(graph, run):
