@@ -16,7 +16,7 @@ class AsepError(RuntimeError):
 
 
 MLP_MAX_HIDDEN = 4       # GNN_MLP_MAX (csrc/gnn_kernels.h): hidden layers of the interaction / attention / classifier MLPs
-ABI_VERSION = 9          # ASEP_ABI_VERSION of include/asep_hip.h this table was written against
+ABI_VERSION = 10         # ASEP_ABI_VERSION of include/asep_hip.h this table was written against
 
 
 class _SizedCfg(C.Structure):
@@ -29,7 +29,7 @@ class _SizedCfg(C.Structure):
 class AruCfg(_SizedCfg):
     _fields_ = [(n, C.c_int32) for n in (
         "struct_size", "channels", "n_classes", "feat_root", "scale_space_num", "res_depth", "num_scales_att",
-        "use_attention", "mvn", "apply_softmax", "compute_dtype", "activation", "plain_u")]
+        "use_attention", "mvn", "apply_softmax", "compute_dtype", "activation", "plain_u", "input_pyramid", "inp4up")]
 
 
 class GnnCfg(_SizedCfg):

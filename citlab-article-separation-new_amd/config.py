@@ -12,7 +12,8 @@ from typing import List
 
 @dataclass
 class AruConfig:
-    graph: str = "ARU"            # 'U' (plain conv1 + conv2 blocks), 'RU' (residual blocks) or 'ARU' (+ attention), ARU_v1.py:92-97
+    graph: str = "ARU"            # 'U' (plain conv1 + conv2 blocks), 'RU' (residual blocks) or 'ARU' (+ attention), ARU_v1.py:92-97;
+                                  # 'RU_v2' (RU_v2.py): the RU-Net with the average-pooled page concatenated into conv1 of its blocks
     channels: int = 1             # image channels: 1 (gray) or, for the graphs without attention (RU / U), 3 (RGB, interleaved [H,W,3])
     n_classes: int = 2
     feat_root: int = 8
@@ -31,10 +32,20 @@ class AruConfig:
     #   'f32':  every product on the fp32 pipes (v_mfma_f32_16x16x4_f32, Winograd F(2x2,3x3) from 32 channels, v_pk_fma_f32 at level 0)
     #   'bf16': BASELINE configs[4] "bf16 convs": bf16 tensors and MFMA operands, fp32 accumulation (its own, wider gates)
     compute_dtype: str = "f32s"
+    inp4up: bool = True           # graph 'RU_v2' only (RU_v2.py:13,143): the pooled page also goes into conv1 of the up blocks
 
     @property
     def use_attention(self) -> bool:
         return "ARU" in self.graph
+
+    @property
+    def input_pyramid(self) -> bool:
+        return self.graph == "RU_v2"
+
+    @property
+    def root_scope(self) -> str:
+        """the variable scope of the graph: RU_v2.py:48 'ru_net', ARU_v1.py 'aru_net'"""
+        return "ru_net" if self.input_pyramid else "aru_net"
 
     @property
     def use_residual(self) -> bool:
@@ -58,6 +69,12 @@ class AruConfig:
         if self.channels == 3 and self.use_attention:
             raise ValueError("3-channel input needs a graph without attention (RU or U): the attention graph upsamples its attention "
                              "map to the input's shape with a one-channel filter (ARU_v1.py:115)")
+
+    def check_graph(self):
+        """what the engine serves of the graph 'RU_v2'; raises ``ValueError`` with the reason otherwise (the same rules as ``asep_aru_load``)"""
+        if self.input_pyramid and self.compute_dtype == "bf16":
+            raise ValueError("graph 'RU_v2' runs on the fp32 engines (compute_dtype 'f32s' or 'f32'): the bf16 engine's fused block tails round "
+                             "conv1's result to bfloat16 before the pooled page's term could be added")
 
     def to_dict(self):
         return asdict(self)
@@ -106,6 +123,9 @@ class GnnConfig:
         kw = dict(graph="RU", apply_softmax=False)
         kw.update(self.backbone)
         kw["mvn"] = bool(kw.get("mvn", False) or self.mvn)
+        if kw["graph"] == "RU_v2":
+            raise ValueError("graph 'RU_v2' cannot be the relation net's backbone: RU_v2_CNN.infer returns no end points (RU_v2.py:31), and the "
+                             "visual branch picks its feature maps from the backbone's end points by name (graph_relation.py:96-105)")
         return AruConfig(**kw)
 
     MAX_LAYER_DEPTH = 256             # widest generated map the engine serves (asep_gnn_attach_backbone_maps)

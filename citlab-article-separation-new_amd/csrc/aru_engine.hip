@@ -15,6 +15,7 @@
 #include "launch_plan.h"
 #include "convr_kernels.h"
 #include "split_kernels.h"
+#include "pyr_kernels.h"
 #include "asep_common.h"
 #include "aru_pack.h"
 
@@ -56,6 +57,7 @@ struct asep_aru {
     std::map<std::string, PackedConv> convs;   // keyed by variable scope, e.g. "aru_net/featMapG/unet_down_1/convR_0"
     struct ResB { int C = 0; bf16_t* d_w = nullptr; float* d_b = nullptr; };
     std::map<std::string, ResB> resb;          // bf16 path: fused residual-block tails (8- / 16-channel levels), keyed by block scope
+    std::map<std::string, float*> taps;        // RU_v2 (cfg.input_pyramid): the image rows of a block's conv1 [9][channels][cout] (pyr_tap_kernel), keyed by the conv's scope
     // bf16 path, whole level-0 blocks in one kernel each (res8b_kernel): pixel-pair A fragments
     bf16_t* d_r8b_down_w = nullptr;  // [3 convs][3 ky][64][8]
     float* d_r8b_down_b = nullptr;   // [3][8]
@@ -373,8 +375,13 @@ void launch_conv_k(asep_aru* m, const PackedConv& pc, const ConvArgs& a, int tot
     else ASEP_CONV_LAUNCH(KH, KW, 1, false, CONV_TH, true, false, false, 2);
 }
 
-enum PoolKind { POOL_MAX, POOL_AVG_C1, POOL_CHANSUM };
+enum PoolKind { POOL_MAX, POOL_AVG_C1, POOL_CHANSUM, POOL_AVG_C3 };
 TL run_pool(asep_aru* m, const TL& in, PoolKind kind);
+// launchers of the kernels that are instantiated at the end of this file (see the note there)
+void launch_conv_c1_12(asep_aru* m, const C1Args& a, int tiles);
+void launch_avgpool_c3(asep_aru* m, const PoolArgs& a, dim3 grid);
+void launch_pyr_tap(asep_aru* m, const TapArgs& a, int ch, int tiles);
+void launch_combine12(const CombineArgs& ca, dim3 grid, int nsct, hipStream_t stream);
 
 // launches convs_kernel<...> under that instantiation's name
 #define ASEP_CONVS_LAUNCH(KH_, KW_, C16_, MT_, TH_, MB_)                                                              \
@@ -627,6 +634,7 @@ TL run_direct(asep_aru* m, const DirectConv& dc, const TL& imgs, bool relu, cons
         else if (bf) hipLaunchKernelGGL((conv_c1_kernel<3, 8, true>), grid, dim3(256), 0, m->stream, a);
         else if (dc.k == 3 && dc.cout == 8) hipLaunchKernelGGL((conv_c1_kernel<3, 8>), grid, dim3(256), 0, m->stream, a);
         else if (dc.k == 3 && dc.cout == 16) hipLaunchKernelGGL((conv_c1_kernel<3, 16>), grid, dim3(256), 0, m->stream, a);
+        else if (dc.k == 3 && dc.cout == 12) launch_conv_c1_12(m, a, tiles);
         else if (dc.k == 4 && dc.cout == 12) hipLaunchKernelGGL((conv_c1_kernel<4, 12>), grid, dim3(256), 0, m->stream, a);
         else { set_error("first-layer conv k=%d cout=%d not instantiated", dc.k, dc.cout); throw ArgError(); }
     });
@@ -655,7 +663,7 @@ TL run_pool(asep_aru* m, const TL& in, PoolKind kind) {
         if (kind == POOL_CHANSUM) out.push_back(new_tensor(m, t.H, t.W, 1));
         else out.push_back(new_tensor(m, cdiv(t.H, 2), cdiv(t.W, 2), t.C));
     }
-    stream_pass<PoolArgs>(m, in, kind == POOL_MAX ? "maxpool2_kernel" : (kind == POOL_AVG_C1 ? "avgpool2_c1_kernel" : "chansum_kernel"), POOL_ITEMS,
+    stream_pass<PoolArgs>(m, in, kind == POOL_MAX ? "maxpool2_kernel" : (kind == POOL_AVG_C1 ? "avgpool2_c1_kernel" : (kind == POOL_AVG_C3 ? "avgpool2_cn_kernel<3>" : "chansum_kernel")), POOL_ITEMS,
         [&](PoolProb& p, size_t i, Chunk& k) {
             k.bytes += tbytes(in[i]) + tbytes(out[i]);
             p.in = in[i].p; p.out = out[i].p; p.H = in[i].H; p.W = in[i].W; p.Ho = out[i].H; p.Wo = out[i].W;
@@ -663,6 +671,7 @@ TL run_pool(asep_aru* m, const TL& in, PoolKind kind) {
         }, [&](const PoolArgs& a, dim3 grid) {
             if (kind == POOL_MAX) hipLaunchKernelGGL(maxpool2_kernel, grid, dim3(256), 0, m->stream, a);
             else if (kind == POOL_AVG_C1) hipLaunchKernelGGL(avgpool2_c1_kernel, grid, dim3(256), 0, m->stream, a);
+            else if (kind == POOL_AVG_C3) launch_avgpool_c3(m, a, grid);
             else hipLaunchKernelGGL(chansum_kernel, grid, dim3(256), 0, m->stream, a);
         });
     return out;
@@ -1266,6 +1275,30 @@ TL res_block_tail(asep_aru* m, const std::string& scope, const TL& t, TL* pooled
     return r;
 }
 
+// RU_v2: t += tap(I_l) behind conv1 `scope` (pyr_kernels.h): imgs = the pyramid level of the block, t = conv1's result, one launch for all pages
+void run_tap(asep_aru* m, const std::string& scope, const TL& imgs, const TL& t, const std::vector<const float*>& stats) {
+    auto it = m->taps.find(scope);
+    if (it == m->taps.end()) { set_error("internal: input-pyramid tap of %s not loaded", scope.c_str()); throw ArgError(); }
+    const int ch = imgs[0].C, cout = t[0].C;
+    for (size_t i = 0; i < t.size(); ++i)
+        if (imgs[i].H != t[i].H || imgs[i].W != t[i].W) {
+            set_error("internal: input pyramid %dx%d against %dx%d at %s", imgs[i].H, imgs[i].W, t[i].H, t[i].W, scope.c_str());
+            throw ArgError();
+        }
+    for_chunks<TapArgs>(t.size(), 9.0 * ch * cout * 4.0, [&](TapProb& p, size_t i, Chunk& k) {
+        p.img = imgs[i].p; p.t = t[i].p; p.stats = stats.empty() ? nullptr : stats[i];
+        p.H = t[i].H; p.W = t[i].W;
+        set_tiles(p, k.units.next_tiles(p.H, p.W, PYR_TW, PYR_TH));
+        k.flops += 2.0 * t[i].H * t[i].W * 9.0 * ch * cout;
+        k.bytes += tbytes(imgs[i]) + 2.0 * tbytes(t[i]);       // t is read and written
+    }, [&](TapArgs& a, const Chunk& k) {
+        a.w = it->second; a.cout = cout;
+        ProfScope ps(m, "pyr_tap_kernel<" + ti(ch) + ">", k.flops, layer_text(scope + " tap", k.sub(t), ch, cout));
+        ps.bytes = k.bytes;
+        launch_pyr_tap(m, a, ch, k.units.total);
+    });
+}
+
 // names[i] = end-point prefix of problem i ("scale_<s>" for page 0, "p<b>/scale_<s>" otherwise)
 TL det_cnn(asep_aru* m, const TL& imgs, const std::vector<std::string>& names, const std::vector<const float*>& stats) {
     const int n = m->cfg.scale_space_num;
@@ -1274,6 +1307,14 @@ TL det_cnn(asep_aru* m, const TL& imgs, const std::vector<std::string>& names, c
     // colour pages (3 channels, graphs RU / U): the fused level-0 DOWN forms contain the 1-channel conv1, so the block runs as conv_c3_kernel +
     // the block tail (or conv2), the path of the graph variants; the UP block and the deeper levels never see the page
     const bool rgb = m->det_first.cin == 3;
+    // RU_v2 (cfg.input_pyramid): the page average-pooled once per level (RU_v2.py:92-96; with mvn the taps standardise while they load: the pool
+    // commutes with the affine map); conv1 of the down blocks l >= 1 and, with inp4up, of the up blocks gets tap(I_l) added to its result
+    const bool pyr = m->cfg.input_pyramid != 0, pyr_up = pyr && m->cfg.inp4up != 0;
+    std::vector<TL> ipyr;
+    if (pyr) {
+        ipyr.push_back(imgs);
+        for (int l = 1; l < n; ++l) ipyr.push_back(run_pool(m, ipyr.back(), rgb ? POOL_AVG_C3 : POOL_AVG_C1));
+    }
     auto publish = [&](const TL& l, const std::string& suffix) {
         for (size_t i = 0; i < l.size(); ++i) m->endpoints[names[i] + suffix] = l[i];
     };
@@ -1299,6 +1340,7 @@ TL det_cnn(asep_aru* m, const TL& imgs, const std::vector<std::string>& names, c
             d = conv(scope + "/conv2", c1, nullptr, true, pool ? &pooled : nullptr);
         } else {                                             // conv1 -> t, then the block tail, whose last conv also emits maxpool2(d)
             TL t = (l == 0) ? first(false) : conv(scope + "/conv1", u, nullptr, false);
+            if (pyr && l > 0) run_tap(m, scope + "/conv1", ipyr[l], t, stats);
             d = res_block_tail(m, scope, t, pool ? &pooled : nullptr);
         }
         skips.push_back(d);
@@ -1310,7 +1352,7 @@ TL det_cnn(asep_aru* m, const TL& imgs, const std::vector<std::string>& names, c
         const TL& skip = skips[l];
         TL v = deconv(scope + "/deconv", u, skip);
         publish(v, "_unet_up_" + std::to_string(l) + "_deconv");
-        if (l == 0 && (m->bf16 ? m->d_r8b_up_w1 != nullptr : (m->use_fused8 || (m->fused8_var && r8v_fits(skip))) && m->d_r8_up_w1)) {
+        if (l == 0 && !pyr_up && (m->bf16 ? m->d_r8b_up_w1 != nullptr : (m->use_fused8 || (m->fused8_var && r8v_fits(skip))) && m->d_r8_up_w1)) {
             TL d, none;                                      // conv1 over [skip, deconv] + the tail in one kernel
             if (m->bf16) run_res8b(m, true, skip, &v, {}, false, &d, &none);
             else run_res8(m, true, skip, &v, {}, false, &d, &none);
@@ -1320,6 +1362,7 @@ TL det_cnn(asep_aru* m, const TL& imgs, const std::vector<std::string>& names, c
             u = conv(scope + "/conv2", c1, nullptr, true);
         } else {
             TL t = conv(scope + "/conv1", skip, &v, false);  // concat [skip, deconv]
+            if (pyr_up) run_tap(m, scope + "/conv1", ipyr[l], t, stats);   // RU_v2.py:142-144: [skip, deconv, I_l]
             u = res_block_tail(m, scope, t);
         }
         publish(u, "_unet_up_" + std::to_string(l) + "_conv");
@@ -1506,12 +1549,7 @@ int forward_impl(asep_aru* m, asep_aru::Lane& L, int page0, int B, const float* 
             // below 4 GB; anything else takes the run-time form
             const bool small = (size_t)H * W * std::max(cfg.feat_root, cfg.n_classes) * sizeof(float) < ((size_t)1 << 32);
             const int nsct = small && (nsc == 1 || nsc == 3) ? nsc : 0;
-            ProfScope ps(m, "combine_kernel" + targs({ti(cfg.feat_root), ti(cfg.n_classes), tb(m->bf16), ti(nsct)}), 2.0 * H * W * 16.0 * cfg.feat_root * cfg.n_classes);
-            // scale-0 feature map + per further scale its channel sum + the attention maps in; probabilities (+ uint8 / threshold images) out
-            ps.bytes = tbytes(feat[b * nsc]) + (double)H * W * cfg.n_classes * (4.0 + (ca.out_u8 ? 1.0 : 0.0) + (ca.out_mask ? 1.0 : 0.0));
-            if (ca.wd) ps.xflops = 2.0 * H * W * 16.0 * cfg.feat_root;   // two classes behind a soft-max: the logits conv runs on the difference filter (half the products)
-            for (int s2 = 1; s2 < nsc; ++s2) ps.bytes += tbytes(fsum[b * (nsc - 1) + (s2 - 1)]);
-            for (int s2 = 0; s2 < nsc && cfg.use_attention; ++s2) ps.bytes += tbytes(att[b * nsc + s2]);
+            const std::string cname = "combine_kernel" + targs({ti(cfg.feat_root), ti(cfg.n_classes), tb(m->bf16), ti(nsct)});
 #define ASEP_COMB_N(FR, NC, BF)                                                                    \
         if (nsct == 3) hipLaunchKernelGGL((combine_kernel<FR, NC, BF, 3>), grid, dim3(256), 0, stream, ca);      \
         else if (nsct == 1) hipLaunchKernelGGL((combine_kernel<FR, NC, BF, 1>), grid, dim3(256), 0, stream, ca); \
@@ -1524,12 +1562,34 @@ int forward_impl(asep_aru* m, asep_aru::Lane& L, int page0, int B, const float* 
     if (cfg.feat_root == 8 && cfg.n_classes == NC && m->bf16) {                                    \
         ASEP_COMB_N(8, NC, true)                                                                   \
     } else
-            ASEP_COMBB(1) ASEP_COMBB(2) ASEP_COMBB(3) ASEP_COMBB(4)
-            ASEP_COMB(8, 1) ASEP_COMB(8, 2) ASEP_COMB(8, 3) ASEP_COMB(8, 4) ASEP_COMB(16, 2)
-            { set_error("combine: feat_root=%d n_classes=%d not instantiated", cfg.feat_root, cfg.n_classes); return ASEP_ERR_UNSUPPORTED; }
+            auto launch_combine = [&](const CombineArgs& ca) {
+                ASEP_COMBB(1) ASEP_COMBB(2) ASEP_COMBB(3) ASEP_COMBB(4)
+                ASEP_COMB(8, 1) ASEP_COMB(8, 2) ASEP_COMB(8, 3) ASEP_COMB(8, 4) ASEP_COMB(16, 2)
+                if (cfg.feat_root == 12 && cfg.n_classes == 2 && !m->bf16) launch_combine12(ca, grid, nsct, stream);
+                else return false;
+                return true;
+            };
 #undef ASEP_COMB
 #undef ASEP_COMBB
 #undef ASEP_COMB_N
+            if (cfg.input_pyramid) {
+                // RU_v2: the logits as an end point of their own ("logits", "p<b>/logits"; the probabilities do not determine them): the same
+                // kernel once more without the soft-max, 4 (feat_root + n_classes) bytes per pixel
+                const Tensor lg = new_tensor(m, H, W, cfg.n_classes);
+                m->endpoints[(page0 + b ? "p" + std::to_string(page0 + b) + "/" : std::string()) + "logits"] = lg;
+                CombineArgs cl = ca;
+                cl.out = lg.p; cl.out_u8 = nullptr; cl.out_mask = nullptr; cl.softmax = 0; cl.wd = nullptr;
+                ProfScope pl(m, cname, 2.0 * H * W * 16.0 * cfg.feat_root * cfg.n_classes, "logits end point");
+                pl.bytes = tbytes(feat[b * nsc]) + tbytes(lg);
+                launch_combine(cl);                          // (an unserved width is reported by the launch below)
+            }
+            ProfScope ps(m, cname, 2.0 * H * W * 16.0 * cfg.feat_root * cfg.n_classes);
+            // scale-0 feature map + per further scale its channel sum + the attention maps in; probabilities (+ uint8 / threshold images) out
+            ps.bytes = tbytes(feat[b * nsc]) + (double)H * W * cfg.n_classes * (4.0 + (ca.out_u8 ? 1.0 : 0.0) + (ca.out_mask ? 1.0 : 0.0));
+            if (ca.wd) ps.xflops = 2.0 * H * W * 16.0 * cfg.feat_root;   // two classes behind a soft-max: the logits conv runs on the difference filter (half the products)
+            for (int s2 = 1; s2 < nsc; ++s2) ps.bytes += tbytes(fsum[b * (nsc - 1) + (s2 - 1)]);
+            for (int s2 = 0; s2 < nsc && cfg.use_attention; ++s2) ps.bytes += tbytes(att[b * nsc + s2]);
+            if (!launch_combine(ca)) { set_error("combine: feat_root=%d n_classes=%d not instantiated", cfg.feat_root, cfg.n_classes); return ASEP_ERR_UNSUPPORTED; }
         }
         ASEP_HIP_CHECK(hipGetLastError());
     } catch (const HipError&) {
@@ -1551,6 +1611,7 @@ double flops_impl(const asep_aru_cfg& cfg, int H, int W) {
             const int f = cfg.feat_root << l;
             dims.push_back({hh, ww});
             mac += (double)hh * ww * (9.0 * last * f + cfg.res_depth * 9.0 * f * f);
+            if (cfg.input_pyramid && l > 0) mac += (double)hh * ww * 9.0 * cfg.channels * f;      // RU_v2: the tap of the pooled page
             last = f;
             if (l < cfg.scale_space_num - 1) { hh = cdiv(hh, 2); ww = cdiv(ww, 2); }
         }
@@ -1560,6 +1621,7 @@ double flops_impl(const asep_aru_cfg& cfg, int H, int W) {
             const auto& d = dims[l];
             mac += (double)di.first * di.second * 9.0 * last * f;                       // deconv, input resolution
             mac += (double)d.first * d.second * (9.0 * 2 * f * f + cfg.res_depth * 9.0 * f * f);
+            if (cfg.input_pyramid && cfg.inp4up) mac += (double)d.first * d.second * 9.0 * cfg.channels * f;
             last = f;
         }
         return mac;
@@ -1802,8 +1864,27 @@ asep_aru* asep_aru_load(const void* weight_blob, size_t nbytes, const asep_aru_c
     if (cfg->activation < 0 || cfg->activation > 2) { set_error("asep_aru_load: activation %d unknown (0 = relu, 1 = elu, 2 = leaky)", cfg->activation); return nullptr; }
     const bool variant = cfg->activation != 0 || cfg->plain_u != 0;
     if (cfg->plain_u && cfg->use_attention) { set_error("asep_aru_load: graph 'U' has no attention branch (ARU_v1.py:92-97)"); return nullptr; }
+    if (cfg->inp4up && !cfg->input_pyramid) { set_error("asep_aru_load: inp4up is an option of the input-pyramid graph (RU_v2.py:143): set input_pyramid"); return nullptr; }
+    if (cfg->input_pyramid && (cfg->use_attention || cfg->plain_u)) {
+        set_error("asep_aru_load: the input-pyramid graph (RU_v2) is a residual U-Net without attention (RU_v2.py:56: useResidual=True, no attMapG): "
+                  "use_attention and plain_u must be 0");
+        return nullptr;
+    }
+    if (cfg->input_pyramid && cfg->compute_dtype == 1) {
+        set_error("asep_aru_load: the input-pyramid graph (RU_v2) is served by the fp32 engines (compute_dtype 0 or 2): the bf16 engine's fused block "
+                  "tails round conv1's result to bfloat16 before the pooled page's term could be added");
+        return nullptr;
+    }
     std::map<std::string, HostTensor> blob;
     if (!parse_blob(weight_blob, nbytes, blob)) return nullptr;
+    std::map<std::string, std::vector<float>> taps;
+    if (cfg->input_pyramid) {
+        try {
+            blob = split_pyramid_blob(blob, *cfg, taps);       // ru_net/... -> the names and conv1 shapes of the packers + the taps' rows
+        } catch (const PackRefusal&) {
+            return nullptr;
+        }
+    }
     warn_ignored_switches();
     std::unique_ptr<asep_aru> m(new asep_aru());
     m->cfg = *cfg;
@@ -1842,6 +1923,7 @@ asep_aru* asep_aru_load(const void* weight_blob, size_t nbytes, const asep_aru_c
         m->lanes.push_back(std::move(L));
     }
     m->cur = m->lanes[0].get();
+    for (const auto& t : taps) m->taps[t.first] = m->put(t.second);
     try {
         load_weights(m.get(), blob, variant);
     } catch (const PackRefusal&) {                           // (the error text is set)
@@ -2082,6 +2164,17 @@ void launch_conv_c3(asep_aru* m, const C1Args& a, int cout, bool bf, int tiles) 
     if (bf) hipLaunchKernelGGL((conv_c3_kernel<8, true>), dim3(tiles), dim3(256), 0, m->stream, a);
     else if (cout == 16) hipLaunchKernelGGL((conv_c3_kernel<16, false>), dim3(tiles), dim3(256), 0, m->stream, a);
     else hipLaunchKernelGGL((conv_c3_kernel<8, false>), dim3(tiles), dim3(256), 0, m->stream, a);
+}
+// The RU_v2 kernels (pyr_kernels.h) and the feat_root 12 forms of the first layer and the logits kernel follow them for the same reason.
+void launch_avgpool_c3(asep_aru* m, const PoolArgs& a, dim3 grid) { hipLaunchKernelGGL(avgpool2_cn_kernel<3>, grid, dim3(256), 0, m->stream, a); }
+void launch_pyr_tap(asep_aru* m, const TapArgs& a, int ch, int tiles) {
+    if (ch == 3) hipLaunchKernelGGL(pyr_tap_kernel<3>, dim3(tiles), dim3(256), pyr_tap_lds(3, a.cout), m->stream, a);
+    else hipLaunchKernelGGL(pyr_tap_kernel<1>, dim3(tiles), dim3(256), pyr_tap_lds(1, a.cout), m->stream, a);
+}
+void launch_conv_c1_12(asep_aru* m, const C1Args& a, int tiles) { hipLaunchKernelGGL((conv_c1_kernel<3, 12>), dim3(tiles), dim3(256), 0, m->stream, a); }
+void launch_combine12(const CombineArgs& ca, dim3 grid, int nsct, hipStream_t stream) {
+    if (nsct == 1) hipLaunchKernelGGL((combine_kernel<12, 2, false, 1>), grid, dim3(256), 0, stream, ca);
+    else hipLaunchKernelGGL((combine_kernel<12, 2, false, 0>), grid, dim3(256), 0, stream, ca);
 }
 }  // namespace
 

@@ -2,6 +2,7 @@
 // from the blob's filters to std::vector<float> / std::vector<bf16_t>.  Plain C++17 without HIP: tests/aru_pack_check.cpp compares
 // every order with recorded digests on the CPU under the sanitizers.  aru_engine.hip decides which vector goes into which member.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -513,6 +514,45 @@ inline std::vector<float> pack_logit_diff(const Layer& L) {
     for (size_t i = 0; i + 1 < wd.size(); ++i) wd[i] = w[2 * i + 1] - w[2 * i];
     wd.back() = L.b.data[1] - L.b.data[0];
     return wd;
+}
+
+
+// ---- RU_v2 (asep_aru_cfg.input_pyramid) -------------------------------------------------------------
+// The graph's variables live under ru_net/..., and conv1 of every block that reads the pooled page I_l has `channels` more input rows, LAST in
+// the concat (RU_v2.py:101,144): down blocks l >= 1 [3,3,f_{l-1} + channels,f_l], with inp4up up blocks [3,3,2 f_l + channels,f_l].  Returns the
+// blob that the packers above read -- the same tensors under aru_net/..., those filters cut to their main rows (the layer the conv kernels run)
+// -- and leaves the image rows [9][channels][f_l] (pyr_tap_kernel's order) in taps[<aru_net scope of the conv1>].
+inline WeightBlob split_pyramid_blob(const WeightBlob& in, const asep_aru_cfg& cfg, std::map<std::string, std::vector<float>>& taps) {
+    WeightBlob out;
+    for (const auto& kv : in) out[kv.first.compare(0, 7, "ru_net/") == 0 ? "aru_" + kv.first.substr(3) : kv.first] = kv.second;
+    const int n = cfg.scale_space_num, ch = cfg.channels;
+    auto cut = [&](const std::string& scope, int cmain, int f) {
+        if (f % 4 != 0 || f > 256) {
+            set_error("weights: %s has %d output channels: the input-pyramid tap serves multiples of 4 up to 256", scope.c_str(), f);
+            throw PackRefusal{ASEP_ERR_UNSUPPORTED};
+        }
+        auto wi = out.find(scope + "/weights");
+        if (wi == out.end() || !has_shape(wi->second, 3, 3, cmain + ch, f)) {
+            set_error("weights: ru%s/weights must be [3,3,%d,%d] (%d channels + the %d of the pooled page, RU_v2.py:101,144)", scope.c_str() + 3,
+                      cmain + ch, f, cmain, ch);
+            throw PackRefusal{ASEP_ERR_WEIGHTS};
+        }
+        const std::vector<float> w = wi->second.data;
+        HostTensor& mainw = wi->second;
+        mainw.dims[2] = cmain;
+        mainw.data.resize((size_t)9 * cmain * f);
+        std::vector<float>& tap = taps[scope];
+        tap.resize((size_t)9 * ch * f);
+        for (int t = 0; t < 9; ++t) {
+            const float* row = &w[(size_t)t * (cmain + ch) * f];
+            std::copy(row, row + (size_t)cmain * f, &mainw.data[(size_t)t * cmain * f]);
+            std::copy(row + (size_t)cmain * f, row + (size_t)(cmain + ch) * f, &tap[(size_t)t * ch * f]);
+        }
+    };
+    for (int l = 1; l < n; ++l) cut("aru_net/featMapG/unet_down_" + std::to_string(l) + "/conv1", cfg.feat_root << (l - 1), cfg.feat_root << l);
+    if (cfg.inp4up)
+        for (int l = 0; l + 1 < n; ++l) cut("aru_net/featMapG/unet_up_" + std::to_string(l) + "/conv1", 2 * (cfg.feat_root << l), cfg.feat_root << l);
+    return out;
 }
 
 }  // namespace asep

@@ -55,11 +55,13 @@ class AruGraph:
             lib = _lib.init_device(device_id)
             c = self.cfg
             c.check_channels()
+            c.check_graph()
             if c.compute_dtype not in COMPUTE_DTYPES:
                 raise ValueError(f"compute_dtype must be one of {sorted(COMPUTE_DTYPES)}, got {c.compute_dtype!r}")
             cfg = _lib.AruCfg(c.channels, c.n_classes, c.feat_root, c.scale_space_num, c.res_depth,
                               c.num_scales_att, int(c.use_attention), int(c.mvn), int(c.apply_softmax),
-                              COMPUTE_DTYPES[c.compute_dtype], c.activation_code, 0 if c.use_residual else 1)
+                              COMPUTE_DTYPES[c.compute_dtype], c.activation_code, 0 if c.use_residual else 1,
+                              int(c.input_pyramid), int(c.input_pyramid and c.inp4up))
             blob = self.blob()
             h = lib.asep_aru_load(blob, len(blob), C.byref(cfg))
             if not h:

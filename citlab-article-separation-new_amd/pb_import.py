@@ -287,26 +287,32 @@ def aru_from_constants(nodes, num_scales_att=None, apply_softmax=None):
     constants only).  What the constants cannot tell -- the number of pyramid scales and whether ``output`` is behind a
     class softmax -- must be passed in or be readable from the op list; it is never defaulted."""
     consts = const_tensors(nodes)
-    if _find(consts, "aru_net/featMapG/unet_down_0/conv1/weights") is None:
-        raise IOError("no ARU-Net variables (aru_net/featMapG/...) among the graph constants; "
+    root = "ru_net" if _find(consts, "ru_net/featMapG/unet_down_0/conv1/weights") is not None else "aru_net"    # RU_v2.py:48 / ARU_v1.py
+    if _find(consts, f"{root}/featMapG/unet_down_0/conv1/weights") is None:
+        raise IOError("no ARU-Net variables (aru_net/featMapG/... or, graph RU_v2, ru_net/featMapG/...) among the graph constants; "
                       "constants found: " + ", ".join(list(consts)[:8]) + " ...")
     levels = 0
-    while _find(consts, f"aru_net/featMapG/unet_down_{levels}/conv1/weights") is not None:
+    while _find(consts, f"{root}/featMapG/unet_down_{levels}/conv1/weights") is not None:
         levels += 1
     res_depth = 0
-    while _find(consts, f"aru_net/featMapG/unet_down_0/convR_{res_depth}/weights") is not None:
+    while _find(consts, f"{root}/featMapG/unet_down_0/convR_{res_depth}/weights") is not None:
         res_depth += 1
-    plain_u = res_depth == 0 and _find(consts, "aru_net/featMapG/unet_down_0/conv2/weights") is not None   # graph 'U'
+    plain_u = res_depth == 0 and _find(consts, f"{root}/featMapG/unet_down_0/conv2/weights") is not None   # graph 'U'
     act = _find(consts, "asep_meta/activation")             # written by weights_to_graphdef(meta={"activation": code}); absent: relu,
     try:                                                    # ARU_v1.py:43's default (the constants cannot tell)
         activation_name = ("relu", "elu", "leaky")[int(np.asarray(act).reshape(-1)[0])] if act is not None else "relu"
     except IndexError:
         raise IOError("asep_meta/activation must be 0 (relu), 1 (elu) or 2 (leaky)")
-    w0 = _find(consts, "aru_net/featMapG/unet_down_0/conv1/weights")
-    wl = _find(consts, "aru_net/logit/class/weights")
+    w0 = _find(consts, f"{root}/featMapG/unet_down_0/conv1/weights")
+    wl = _find(consts, f"{root}/logit/class/weights")
     if wl is None:
-        raise IOError("aru_net/logit/class/weights missing")
+        raise IOError(f"{root}/logit/class/weights missing")
     use_att = _find(consts, "aru_net/attMapG/attPart/conv1/weights") is not None
+    ru_v2, inp4up = root == "ru_net", True
+    if ru_v2:                                               # RU_v2.py:143-144: with inp4up conv1 of an up block has `channels` more input rows
+        wu = _find(consts, "ru_net/featMapG/unet_up_0/conv1/weights")
+        inp4up = wu is None or int(wu.shape[2]) != 2 * int(wu.shape[3])
+        num_scales_att = 1 if num_scales_att is None else num_scales_att       # (its AvgPool ops are the input pyramid, not attention scales)
     if num_scales_att is None:
         num_scales_att = _hint_num_scales(nodes, use_att)
         if num_scales_att is None:
@@ -316,10 +322,11 @@ def aru_from_constants(nodes, num_scales_att=None, apply_softmax=None):
         apply_softmax = _hint_softmax(nodes)
         if apply_softmax is None:
             raise IOError("the graph has no 'output' node: pass apply_softmax explicitly")
-    cfg = AruConfig(graph="ARU" if use_att else ("U" if plain_u else "RU"), channels=int(w0.shape[2]), n_classes=int(wl.shape[3]),
+    cfg = AruConfig(graph="RU_v2" if ru_v2 else ("ARU" if use_att else ("U" if plain_u else "RU")), channels=int(w0.shape[2]),
+                    n_classes=int(wl.shape[3]),
                     feat_root=int(w0.shape[3]), scale_space_num=levels, res_depth=3 if plain_u else res_depth, activation_name=activation_name,
-                    num_scales_att=int(num_scales_att), filter_size=int(w0.shape[0]),
-                    mvn=any("aru_net/mvn" in n["name"] for n in nodes), apply_softmax=bool(apply_softmax))
+                    num_scales_att=int(num_scales_att), filter_size=int(w0.shape[0]), inp4up=inp4up,
+                    mvn=any(f"{root}/mvn" in n["name"] for n in nodes), apply_softmax=bool(apply_softmax))
     _check_channels(cfg)
     tensors = OrderedDict()
     for name, shape in aru_tensor_shapes(cfg).items():
@@ -613,6 +620,36 @@ def _path_nodes(graph, start, end):
     return order
 
 
+def _check_input_pyramid(graph, det, cfg):
+    """graph 'RU_v2': conv1 of every down block l >= 1 and, with inp4up, of every up block reads a ConcatV2 whose LAST operand is the page
+    average-pooled l times (RU_v2.py:92-101,142-144; the up concat nested, as the reference writes it, or flat).  The engine adds that
+    operand's term from the last `channels` input rows of conv1/weights, so any other wiring is refused with the reason."""
+    R, n = cfg.res_depth, cfg.scale_space_num
+    root = graph.skip_pass(graph.src(det[0].ops[0]["input"][0]))     # the page as the first convolution reads it (standardised with mvn)
+
+    def level_of(ref):
+        node, hops = graph.skip_pass(graph.src(ref)), 0
+        while node["op"] == "AvgPool":
+            node, hops = graph.skip_pass(graph.src(node["input"][0])), hops + 1
+        return hops if node is root else None
+
+    tapped = [(det[l * (1 + R)], l, f"unet_down_{l}") for l in range(1, n)]
+    if cfg.inp4up:
+        tapped += [(det[n * (1 + R) + i * (2 + R) + 1], l, f"unet_up_{l}") for i, l in enumerate(range(n - 2, -1, -1))]
+    for lay, l, block in tapped:
+        cat = graph.skip_pass(graph.src(lay.ops[0]["input"][0]))
+        if cat["op"] != "ConcatV2":
+            raise IOError(f"{block}/conv1 ({lay.filter_name}) has {cfg.channels} input channels more than ARU_v1's but reads {cat['op']} "
+                          f"{cat['name']}, not the concat with the pooled page (RU_v2.py:101,144)")
+        levels = [level_of(r) for r in graph.data_inputs(cat)]
+        if levels[-1] != l:
+            if l in levels[:-1]:
+                raise IOError(f"{cat['name']}: the pooled page is operand {levels.index(l)} of the concat in front of {block}/conv1; RU_v2 puts it "
+                              "LAST (RU_v2.py:101,144), and the engine reads the image rows of conv1/weights behind all others")
+            raise IOError(f"{cat['name']}: the last operand of the concat in front of {block}/conv1 is not the page average-pooled {l} time(s) "
+                          f"(2x2, stride 2, SAME; RU_v2.py:94-96)")
+
+
 def aru_from_topology(nodes, input_name="inImg", output_name="output"):
     """ARU_v1 weights + hyper-parameters from the op graph between ``inImg`` and ``output``, whatever the scopes are
     called (module docstring).  Returns (tensors under the engine's names, AruConfig)."""
@@ -634,7 +671,8 @@ def aru_from_topology(nodes, input_name="inImg", output_name="output"):
         if n["op"] in ("MaxPool", "AvgPool"):
             if _attr_list(n, "ksize", [1, 2, 2, 1]) != [1, 2, 2, 1] or _attr_list(n, "strides", [1, 2, 2, 1]) != [1, 2, 2, 1] \
                     or (n["attr"].get("padding") or "SAME") != "SAME":
-                raise IOError(f"{n['name']}: only 2x2 / stride 2 / SAME pooling is supported")
+                raise IOError(f"{n['name']}: only 2x2 / stride 2 / SAME pooling is supported (the max pools between the levels and the "
+                              "average pools of the attention scales / of RU_v2's input pyramid)")
     layers, op_layer = _collect_layers(graph, path)
     if not layers:
         raise IOError("no convolution with a constant filter between inImg and output")
@@ -713,7 +751,13 @@ def aru_from_topology(nodes, input_name="inImg", output_name="output"):
     if res_depth == 1 and not att and len(det) > 1:
         nxt = det[2] if len(det) > 2 else last               # the layer that consumes the first block's output
         plain_u = nxt.preds == {det[1].filter_name}
-    cfg = AruConfig(graph="ARU" if att else ("U" if plain_u else "RU"), channels=channels, n_classes=last.cout, feat_root=feat_root,
+    # graph 'RU_v2' (RU_v2.py:101,144): conv1 of the down blocks l >= 1 has `channels` more input rows than ARU_v1's, with inp4up conv1 of the
+    # up blocks too; the shapes below and _check_input_pyramid hold the graph to it
+    ru_v2 = not att and not plain_u and n_levels > 1 and int(det[1 + res_depth].w.shape[2]) == feat_root + channels
+    up1 = det[n_levels * (1 + res_depth) + 1] if ru_v2 else None
+    inp4up = ru_v2 and int(up1.w.shape[2]) == 2 * up1.cout + channels
+    cfg = AruConfig(graph="RU_v2" if ru_v2 else ("ARU" if att else ("U" if plain_u else "RU")), channels=channels, n_classes=last.cout,
+                    feat_root=feat_root, inp4up=inp4up or not ru_v2,
                     scale_space_num=n_levels, res_depth=3 if plain_u else res_depth, num_scales_att=n_scales, filter_size=k, mvn=mvn,
                     apply_softmax=softmax, activation_name=activation_name)
     _check_channels(cfg)
@@ -755,6 +799,8 @@ def aru_from_topology(nodes, input_name="inImg", output_name="output"):
         tensors[bname] = np.ascontiguousarray(b, dtype=np.float32)
     tensors = OrderedDict((n, tensors[n]) for n in names)
     _check_wiring(cfg, ordered, name_of)
+    if ru_v2:
+        _check_input_pyramid(graph, det, cfg)
     return tensors, cfg
 
 
@@ -764,7 +810,7 @@ def _check_wiring(cfg, ordered, name_of):
     n, R = cfg.scale_space_num, cfg.res_depth
     want = {}
     block_out = None                                        # layers whose sum is the previous block's output
-    det = "aru_net/featMapG/"
+    det = f"{cfg.root_scope}/featMapG/"
     plain_u = not cfg.use_residual                          # ARU_v1.py:228-233,283-288: conv1 -> conv2, the block's output is conv2
     for l in range(n):
         s = f"{det}unet_down_{l}"
@@ -795,7 +841,7 @@ def _check_wiring(cfg, ordered, name_of):
         for i in (2, 3, 4):
             want[a + str(i)] = {a + str(i - 1)}
         logit_in.add(a + "4")
-    want["aru_net/logit/class"] = logit_in
+    want[f"{cfg.root_scope}/logit/class"] = logit_in
     for scope, preds in want.items():
         if got.get(scope) != preds:
             raise IOError(f"{scope} is fed by {sorted(got.get(scope, ()))} in the graph, ARU_v1 ('{cfg.graph}') wires it to {sorted(preds)}")
@@ -805,7 +851,8 @@ def aru_from_nodes(nodes, num_scales_att=None, apply_softmax=None):
     """Frozen ARU-Net -> (tensors, AruConfig).  A graph with its op structure is mapped by topology; when it also
     carries ARU_v1's variable names both mappings must agree.  A constants-only container is mapped by name."""
     has_ops = any(n["op"] == "Conv2D" for n in nodes)
-    named = any(n["op"] == "Const" and n["name"].endswith("aru_net/featMapG/unet_down_0/conv1/weights") for n in nodes)
+    named = any(n["op"] == "Const" and ("/" + n["name"]).endswith(("/aru_net/featMapG/unet_down_0/conv1/weights",
+                                                                    "/ru_net/featMapG/unet_down_0/conv1/weights")) for n in nodes)
     if not has_ops:
         return aru_from_constants(nodes, num_scales_att, apply_softmax)
     tensors, cfg = aru_from_topology(nodes)

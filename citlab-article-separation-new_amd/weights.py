@@ -36,11 +36,15 @@ def aru_tensor_shapes(cfg: AruConfig) -> "OrderedDict[str, tuple]":
             shapes[p + "/weights"] = (4, 4, cin, f)
             shapes[p + "/biases"] = (f,)
             cin = f
+    root = cfg.root_scope
+    # graph 'RU_v2': the pooled page (cfg.channels channels) is the LAST operand of the concat in front of conv1 (RU_v2.py:101,144)
+    pyr_down = cfg.channels if cfg.input_pyramid else 0
+    pyr_up = cfg.channels if cfg.input_pyramid and cfg.inp4up else 0
     last = cfg.channels
     for l in range(cfg.scale_space_num):                           # ARU_v1.py:208-245
         f = cfg.feat(l)
-        p = f"aru_net/featMapG/unet_down_{l}"
-        shapes[p + "/conv1/weights"] = (k, k, last, f)
+        p = f"{root}/featMapG/unet_down_{l}"
+        shapes[p + "/conv1/weights"] = (k, k, last + (pyr_down if l > 0 else 0), f)
         shapes[p + "/conv1/biases"] = (f,)
         if cfg.use_residual:
             for r in range(cfg.res_depth):
@@ -52,10 +56,10 @@ def aru_tensor_shapes(cfg: AruConfig) -> "OrderedDict[str, tuple]":
         last = f
     for l in range(cfg.scale_space_num - 2, -1, -1):                # ARU_v1.py:251-292
         f = cfg.feat(l)
-        p = f"aru_net/featMapG/unet_up_{l}"
+        p = f"{root}/featMapG/unet_up_{l}"
         shapes[p + "/deconv/weights"] = (k, k, f, last)             # [kh,kw,Cout,Cin]
         shapes[p + "/deconv/bias"] = (f,)
-        shapes[p + "/conv1/weights"] = (k, k, 2 * f, f)
+        shapes[p + "/conv1/weights"] = (k, k, 2 * f + pyr_up, f)
         shapes[p + "/conv1/biases"] = (f,)
         if cfg.use_residual:
             for r in range(cfg.res_depth):
@@ -65,8 +69,8 @@ def aru_tensor_shapes(cfg: AruConfig) -> "OrderedDict[str, tuple]":
             shapes[p + "/conv2/weights"] = (k, k, f, f)
             shapes[p + "/conv2/biases"] = (f,)
         last = f
-    shapes["aru_net/logit/class/weights"] = (4, 4, cfg.feat_root, cfg.n_classes)   # ARU_v1.py:158
-    shapes["aru_net/logit/class/biases"] = (cfg.n_classes,)
+    shapes[f"{root}/logit/class/weights"] = (4, 4, cfg.feat_root, cfg.n_classes)   # ARU_v1.py:158
+    shapes[f"{root}/logit/class/biases"] = (cfg.n_classes,)
     return shapes
 
 
@@ -166,7 +170,8 @@ def init_aru_weights(cfg: AruConfig, seed: int = 1234, bias_jitter: float = 0.0,
     at 0/1 (used by the parity tests to keep the probability comparison sensitive)."""
     w = _init_from_shapes(aru_tensor_shapes(cfg), seed)
     if logit_scale != 1.0:
-        w["aru_net/logit/class/weights"] = (w["aru_net/logit/class/weights"] * logit_scale).astype(np.float32)
+        lw = f"{cfg.root_scope}/logit/class/weights"
+        w[lw] = (w[lw] * logit_scale).astype(np.float32)
     if bias_jitter:
         # optional: non-constant biases make parity tests sensitive to bias indexing errors
         rng = np.random.default_rng(seed + 1)

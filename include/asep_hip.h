@@ -47,7 +47,7 @@ const char* asep_version(void);
  * functions refuse a struct whose size is not the one the library was built with -- a caller written against an older or newer
  * header gets ASEP_ERR_ARG + a message instead of fields read from whatever follows its struct on the stack.
  * An added function moves the version too: a binding resolves every name it declares when it loads the library. */
-#define ASEP_ABI_VERSION 9
+#define ASEP_ABI_VERSION 10
 int asep_abi_version(void);
 /* ABI 6: the environment switches this build of the library reads when a model is loaded (one name per line).
  * Anything else in the environment is not a switch: a caller that records the switches a measurement ran under (bench.py) filters
@@ -83,6 +83,11 @@ typedef struct asep_aru_cfg {
                                   ReLU between conv1 and convR_0 of a residual block is a ReLU in every variant (ARU_v1.py:214,268) */
     int32_t plain_u;           /* 1 = graph 'U' (ARU_v1.py:228-233,283-288): every block is conv1 + conv2 with the activation, no
                                   residual add, tensors <block>/conv2/{weights,biases} instead of convR_<i>; 0 = residual blocks (RU / ARU) */
+    int32_t input_pyramid;     /* ABI 10: 1 = graph RU_v2 (RU_v2.py): the residual U-Net whose down blocks l >= 1 read concat[pool(d_{l-1}), I_l],
+                                  I_l = the page average-pooled l times (2x2, stride 2, SAME).  The tensors carry the reference's names
+                                  ru_net/featMapG/..., ru_net/logit/class/...; conv1 of those blocks is [3,3,f_{l-1} + channels,f_l], the image
+                                  rows last.  Needs use_attention 0, plain_u 0 and compute_dtype 0 or 2; publishes the end point "logits" */
+    int32_t inp4up;            /* with input_pyramid (RU_v2.py:13,143): 1 = the up blocks read concat[skip, deconv, I_l], conv1 [3,3,2 f_l + channels,f_l] */
 } asep_aru_cfg;
 
 typedef struct asep_aru asep_aru;
