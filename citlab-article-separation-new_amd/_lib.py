@@ -16,7 +16,7 @@ class AsepError(RuntimeError):
 
 
 MLP_MAX_HIDDEN = 4       # GNN_MLP_MAX (csrc/gnn_kernels.h): hidden layers of the interaction / attention / classifier MLPs
-ABI_VERSION = 10         # ASEP_ABI_VERSION of include/asep_hip.h this table was written against
+ABI_VERSION = 11         # ASEP_ABI_VERSION of include/asep_hip.h this table was written against
 
 
 class _SizedCfg(C.Structure):
@@ -46,6 +46,8 @@ class ClusterSetting(C.Structure):
 
 
 RESIZE_MODES = {"keep": 0, "luma": 1}                                # ASEP_RESIZE_* of include/asep_hip.h
+EDGE_RULES = {"bb": 0, "line": 1}                                   # ASEP_EDGE_RULE_* of include/asep_hip.h
+SEP_ORIENTATIONS = {None: 0, "horizontal": 1, "vertical": 2}        # ASEP_SEP_*; any other tag is ASEP_SEP_OTHER (3)
 CLUSTER_METHODS = {"dbscan": 0, "dbscan_std": 1, "greedy": 2}       # ASEP_CLUSTER_* of include/asep_hip.h
 
 
@@ -149,6 +151,9 @@ SIGNATURES = {
     "asep_cluster_grid_last_kernel_us": (C.c_double, []),
     "asep_cluster_grid_max_nodes": (C.c_int, []),
     "asep_cluster_grid_run_methods": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "asep_edge_features_run": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_longlong, _P]),
+    "asep_edge_features_last_kernel_us": (C.c_double, []),
+    "asep_edge_features_last_launches": (C.c_long, [C.c_char_p, C.c_size_t]),
     "asep_releval_create": (_P, []),
     "asep_releval_free": (None, [_P]),
     "asep_releval_reset": (C.c_int, [_P, _P]),

@@ -298,9 +298,9 @@ def is_aligned_heading_separated(text_region_a, text_region_b):
     return True
 
 
-def mask_horizontally_separated_confs(confs, page_path, mask_heading=True, mask_horizontal=True):
+def mask_horizontally_separated_confs(confs, page_path, mask_heading=True, mask_horizontal=True, device_edges=False, device=0):
     """run_gnn_clustering.py:151-187: zero the confidences of region pairs of one column that are split by a heading
-    or by a horizontal separator."""
+    or by a horizontal separator.  ``device_edges``: the pair rules run on the GPU (edge_features.py), the result is the same."""
     regions = Page(page_path).get_regions()
     if mask_horizontal and 'SeparatorRegion' not in regions:
         logging.warning("No separators found for confidence masking.")
@@ -308,6 +308,11 @@ def mask_horizontally_separated_confs(confs, page_path, mask_heading=True, mask_
     text_regions = regions['TextRegion']
     separator_regions = regions.get('SeparatorRegion', [])
     n = len(text_regions)
+    if device_edges:
+        from . import edge_features
+        bits = edge_features.edge_features_device([edge_features.EdgePage(text_regions, separator_regions, [])], pair_bits=True,
+                                                  device=device)[0]["pair_bits"]
+        return edge_features.mask_from_pair_bits(bits, np.shape(confs), mask_heading, mask_horizontal) * confs
     masked = np.ones_like(confs, dtype=np.int32)
     for i in range(n):
         for j in range(i + 1, n):
@@ -366,8 +371,27 @@ _NONE11 = (None,) * 11
 
 
 def build_input_and_target(page_path, interaction='delaunay', visual_regions=False, external_data=None,
-                           sim_feat_extractor=None, separators='bb', swt_img=None, device=0):
-    """:593-813."""
+                           sim_feat_extractor=None, separators='bb', swt_img=None, device=0, device_edges=False):
+    """:593-813.  ``device_edges``: the separator flags and the hulls of the edges come from one engine call (edge_features.py)
+    in place of the two loops over the edges; every array is the same."""
+    graph = _page_graph(page_path, interaction, external_data, sim_feat_extractor, swt_img, device)
+    if graph is None:
+        return _NONE11
+    edge_results = None
+    if device_edges:
+        from . import edge_features
+        edge_results = edge_features.edge_features_device([_edge_page(graph)], rule=separators, hulls=visual_regions,
+                                                          device=device)[0]
+    return _input_and_target(graph, page_path, visual_regions, external_data, separators, edge_results)
+
+
+def _edge_page(graph):
+    from . import edge_features
+    return edge_features.EdgePage(graph["text_regions"], graph["separator_regions"], graph["interacting_nodes"])
+
+
+def _page_graph(page_path, interaction, external_data, sim_feat_extractor, swt_img, device):
+    """the page's regions, node features and edge set (:593-700), or None for a page without two text regions"""
     assert interaction in ('fully', 'delaunay'), \
         f"Interaction setup {interaction} is not supported. Choose from ('fully', 'delaunay') instead."
     if sim_feat_extractor is not None:
@@ -379,12 +403,12 @@ def build_input_and_target(page_path, interaction='delaunay', visual_regions=Fal
     norm_x, norm_y = float(resolution[0]), float(resolution[1])
     if 'TextRegion' not in regions:
         logging.warning(f'No TextRegions found in {page_path}. Returning None.')
-        return _NONE11
+        return None
     text_regions = regions['TextRegion']
     num_nodes = len(text_regions)
     if num_nodes <= 1:
         logging.warning(f'Less than two nodes found in {page_path}. Returning None.')
-        return _NONE11
+        return None
 
     stroke_widths, heights = get_textline_stroke_widths_heights_dist_trafo(page_path, text_lines, swt_img=swt_img,
                                                                            device=device)
@@ -420,14 +444,25 @@ def build_input_and_target(page_path, interaction='delaunay', visual_regions=Fal
     else:
         node_centers = np.array(node_features, dtype=np.float32)[:, 2:4] * [norm_x, norm_y]
         interacting_nodes = delaunay_edges(num_nodes, node_centers)
+    return {"text_regions": text_regions, "separator_regions": regions.get('SeparatorRegion'), "node_features": node_features,
+            "interacting_nodes": interacting_nodes}
+
+
+def _input_and_target(graph, page_path, visual_regions, external_data, separators, edge_results=None):
+    """edge features, visual regions and ground truth of a page (:700-813); ``edge_results``: the page's dict of
+    ``edge_features.edge_features_device`` in place of the loops over the edges"""
+    text_regions, separator_regions = graph["text_regions"], graph["separator_regions"]
+    node_features, interacting_nodes = graph["node_features"], graph["interacting_nodes"]
+    num_nodes = len(text_regions)
     num_interacting_nodes = interacting_nodes.shape[0]
 
-    separator_regions = regions.get('SeparatorRegion')
     edge_features = []
     for i in range(num_interacting_nodes):
         a, b = text_regions[interacting_nodes[i, 0]], text_regions[interacting_nodes[i, 1]]
         ef = []
-        if separator_regions:
+        if edge_results is not None:
+            ef.extend(edge_results["flags"][i].astype(np.float64).tolist())
+        elif separator_regions:
             if separators == 'line':
                 ef.extend(get_edge_separator_feature_line(a, b, separator_regions))
             else:
@@ -452,14 +487,18 @@ def build_input_and_target(page_path, interaction='delaunay', visual_regions=Fal
             vr = get_node_visual_region(text_region)
             vr_nodes.append(vr)
             np_nodes.append(len(vr))
-        vr_edges = []
-        for i in range(num_interacting_nodes):
-            vr = get_edge_visual_region(text_regions[interacting_nodes[i, 0]], text_regions[interacting_nodes[i, 1]])
-            vr_edges.append(vr)
-            np_edges.append(len(vr))
-        vr_edges_array = np.zeros((num_interacting_nodes, np.max(np_edges), 2))
-        for i, vr in enumerate(vr_edges):
-            vr_edges_array[i, :len(vr), :] = vr
+        if edge_results is not None:
+            np_edges = edge_results["hull_n"].tolist()
+            vr_edges_array = edge_results["hull"].astype(np.float64)
+        else:
+            vr_edges = []
+            for i in range(num_interacting_nodes):
+                vr = get_edge_visual_region(text_regions[interacting_nodes[i, 0]], text_regions[interacting_nodes[i, 1]])
+                vr_edges.append(vr)
+                np_edges.append(len(vr))
+            vr_edges_array = np.zeros((num_interacting_nodes, np.max(np_edges), 2))
+            for i, vr in enumerate(vr_edges):
+                vr_edges_array[i, :len(vr), :] = vr
 
     # ground truth: majority article id per region (:762-790); ties -> first of list(set(...)) like the reference
     tr_ids = []
@@ -480,10 +519,14 @@ def build_input_and_target(page_path, interaction='delaunay', visual_regions=Fal
             np.array(gt_relations, dtype=np.int32), np.array(len(gt_relations), dtype=np.int32))
 
 
+EDGE_PAGE_GROUP = 16      # pages of one engine call of generate_feature_jsons(..., device_edges=True)
+
+
 def generate_feature_jsons(page_paths, out_path=None, interaction="delaunay", visual_regions=True, json_list=None,
-                           tb_similarity_setup=(None, None), separators='line', device=0):
+                           tb_similarity_setup=(None, None), separators='line', device=0, device_edges=False):
     """:816-911: one ``<name>.json`` per PAGE-XML; default folder ``json<nodeDim><i><edgeDim>[v]<separators>`` next to
-    the ``page`` folder."""
+    the ``page`` folder.  ``device_edges``: the host part runs page by page, the edge features and edge hulls of every
+    ``EDGE_PAGE_GROUP`` pages come from one engine call (edge_features.py); the files are the same bytes."""
     json_data = []
     for json_path in json_list or []:
         with open(json_path) as f:
@@ -493,15 +536,14 @@ def generate_feature_jsons(page_paths, out_path=None, interaction="delaunay", vi
     create_default_dir = not out_path
     skipped, written = [], []
     t0 = time.time()
-    for page_path in page_paths:
-        logging.info(f"Processing... {page_path}")
+
+    def write(page_path, arrays):
+        nonlocal out_path
         (num_nodes, interacting_nodes, num_interacting_nodes, node_features, edge_features, vr_nodes, np_nodes,
-         vr_edges, np_edges, gt_relations, gt_num_relations) = build_input_and_target(
-            page_path=page_path, interaction=interaction, visual_regions=visual_regions, external_data=json_data,
-            separators=separators, device=device)
+         vr_edges, np_edges, gt_relations, gt_num_relations) = arrays
         if num_nodes is None:
             skipped.append(page_path)
-            continue
+            return
         out = {"num_nodes": num_nodes.tolist(), "interacting_nodes": interacting_nodes.tolist(),
                "num_interacting_nodes": num_interacting_nodes.tolist(), "node_features": node_features.tolist(),
                "edge_features": edge_features.tolist()}
@@ -522,6 +564,27 @@ def generate_feature_jsons(page_paths, out_path=None, interaction="delaunay", vi
         with open(target, "w") as f:
             json.dump(out, f)
         written.append(target)
+
+    if not device_edges:
+        for page_path in page_paths:
+            logging.info(f"Processing... {page_path}")
+            write(page_path, build_input_and_target(
+                page_path=page_path, interaction=interaction, visual_regions=visual_regions, external_data=json_data,
+                separators=separators, device=device))
+    else:
+        from . import edge_features
+        for g0 in range(0, len(page_paths), EDGE_PAGE_GROUP):
+            group = page_paths[g0:g0 + EDGE_PAGE_GROUP]
+            graphs = []
+            for page_path in group:
+                logging.info(f"Processing... {page_path}")
+                graphs.append(_page_graph(page_path, interaction, json_data, None, None, device))
+            good = [g for g in graphs if g is not None]
+            results = iter(edge_features.edge_features_device([_edge_page(g) for g in good], rule=separators,
+                                                              hulls=visual_regions, device=device) if good else [])
+            for page_path, g in zip(group, graphs):
+                write(page_path, _NONE11 if g is None else
+                      _input_and_target(g, page_path, visual_regions, json_data, separators, next(results)))
     logging.info(f"Time (feature generation): {time.time() - t0:.2f} seconds")
     logging.info(f"Wrote {len(written)}/{len(page_paths)} files; skipped {len(skipped)}.")
     return written

@@ -2,7 +2,7 @@
 
     python -m citlab_article_separation_new_amd.run_feature_generation --pagexml_list pages.lst \\
         [--out_dir DIR] [--interaction delaunay|fully] [--visual_regions True] [--separators bb|line] \\
-        [--external_jsons a.json b.json] [--num_workers N]
+        [--external_jsons a.json b.json] [--num_workers N] [--device_edges True]
 
 ``--wv_language/--wv_path`` (word-vector similarities) are accepted for flag compatibility and rejected when set.
 Workers are spawned processes, worker k computing its distance transforms on GPU ``k % n_gpus``.
@@ -27,13 +27,17 @@ def build_parser():
     p.add_argument("--wv_language", type=str, default=None)
     p.add_argument("--wv_path", type=str, default=None)
     p.add_argument("--num_workers", type=int, default=1)
+    # extension: True = the separator flags and the hulls of the edges are computed on the device, 16 pages per engine call
+    # (edge_features.py); the json files are the same bytes.  The default stays the host loops
+    p.add_argument("--device_edges", type=cli_flags.str2bool, default=False)
     return p
 
 
 def _worker(sublist, flags, device):
     from .feature_generation import generate_feature_jsons
     generate_feature_jsons(sublist, flags.out_dir, flags.interaction, flags.visual_regions, flags.external_jsons,
-                           (flags.wv_language, flags.wv_path), flags.separators, device=device)
+                           (flags.wv_language, flags.wv_path), flags.separators, device=device,
+                           device_edges=flags.device_edges)
 
 
 def main(argv=None):

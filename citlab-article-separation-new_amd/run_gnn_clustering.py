@@ -54,6 +54,8 @@ def build_parser():
     p.add_argument("--clustering_method", type=str, default="dbscan", choices=["dbscan", "linkage", "greedy", "dbscan_std"])
     p.add_argument("--mask_horizontally_separated_confs", type=cli_flags.str2bool, default=False)
     p.add_argument("--mask_heading_separated_confs", type=cli_flags.str2bool, default=False)
+    # extension: True = the pair rules of the two masks run on the device (edge_features.py); the masked confidences are the same
+    p.add_argument("--device_edges", type=cli_flags.str2bool, default=False)
     cli_flags.define_dict(p, "clustering_params", {})
     p.add_argument("--out_dir", type=str, default="")
     p.add_argument("--save_conf", type=str, default="no_conf", choices=["no_conf", "with_conf", "only_conf"])
@@ -114,16 +116,19 @@ def _prepare_feed(input_fn, flags, json_path, targets=None, image_later=False, d
     return feed, n
 
 
-def _finish_page(tb, flags, output, n, page_path):
+def _finish_page(tb, flags, output, n, page_path, device=None):
     """:269-300 for one page: net output -> confidences [N,N] -> (masks, json) -> clustering -> PAGE-XML with article ids;
-    -> path of the written file, or None with --save_conf only_conf"""
+    -> path of the written file, or None with --save_conf only_conf.  ``device``: the GPU of the calling owner process, where
+    --device_edges computes the masks' pair rules; None (a host worker, which owns no GPU) keeps them on the host"""
     from . import gnn_results
     confidences = gnn_results.confidences_from_output(output, n)
     if flags.mask_heading_separated_confs or flags.mask_horizontally_separated_confs:      # :279-281
         from .feature_generation import mask_horizontally_separated_confs
         confidences = mask_horizontally_separated_confs(confidences, page_path,
                                                         mask_heading=flags.mask_heading_separated_confs,
-                                                        mask_horizontal=flags.mask_horizontally_separated_confs)
+                                                        mask_horizontal=flags.mask_horizontally_separated_confs,
+                                                        device_edges=device is not None and bool(getattr(flags, "device_edges", False)),
+                                                        device=device or 0)
     if flags.save_conf != "no_conf":
         gnn_results.save_conf_to_json(confidences, page_path, flags.out_dir)
         if flags.save_conf == "only_conf":
@@ -170,7 +175,7 @@ def gnn_clustering(json_paths, flags, device="0"):
         """the collected pages through one engine call; their results leave in input order"""
         outputs = _run_group(sess, [feed for _, feed, _ in group])
         for (page_path, _, n), output in zip(group, outputs):
-            out = _finish_page(tb, flags, output, n, page_path)
+            out = _finish_page(tb, flags, output, n, page_path, device=int(device))
             if out is not None:
                 results.append(out)
         del group[:]

@@ -221,3 +221,101 @@ def write_gnn_cli_inputs(root, n_pages, visual=True, W: int = 3000, H: int = 450
     if visual:
         argv += ["--image_input", "True", "--visual_layers"] + GNN_VISUAL_LAYERS
     return argv
+
+
+class SynthRegion:
+    """a text region as the edge rules read it: ``points``, ``region_type`` (and ``id``)"""
+
+    def __init__(self, rid, points, region_type=None):
+        self.id, self.points, self.region_type = rid, [tuple(int(v) for v in p) for p in points], region_type
+
+
+class SynthSeparator:
+    def __init__(self, points, orientation=None):
+        self.points, self._orientation = [tuple(int(v) for v in p) for p in points], orientation
+
+    def get_orientation(self):
+        return self._orientation
+
+
+def synth_regions_and_separators(k: int = 0, n_regions: int = 200, n_separators: int = 100, W: int = 3000, H: int = 4500,
+                                 seed0: int = 5150):
+    """The text regions and separator regions of a newspaper-like page for the edge rules (feature_generation.py): regions in six
+    columns, 4 to 12 outline points each (boxes with jittered extra points on their upper and lower edge), about one in eight a
+    heading; separators between columns (tall) and between blocks (flat), a part of them slanted or concave polygons of 3 to 12 points,
+    two thirds tagged with their orientation.  -> ([SynthRegion], [SynthSeparator])"""
+    rng = np.random.default_rng(seed0 + k)
+    columns = 6
+    colw = (W - 120 - (columns - 1) * 40) // columns
+    rows = -(-n_regions // columns)
+    pitch = (H - 120) // max(rows, 1)
+    regions = []
+    for i in range(n_regions):
+        c, r = i % columns, i // columns
+        x0 = 60 + c * (colw + 40) + int(rng.integers(0, 9))
+        y0 = 60 + r * pitch + int(rng.integers(0, 9))
+        x1, y1 = x0 + colw - int(rng.integers(0, 17)), y0 + max(8, pitch - int(rng.integers(10, 30)))
+        extra = int(rng.integers(0, 5))
+        top = sorted(int(v) for v in rng.integers(x0 + 1, x1, extra))
+        bottom = sorted((int(v) for v in rng.integers(x0 + 1, x1, extra)), reverse=True)
+        pts = [(x0, y0)] + [(x, y0 - int(rng.integers(0, 4))) for x in top] + [(x1, y0), (x1, y1)] + \
+              [(x, y1 + int(rng.integers(0, 4))) for x in bottom] + [(x0, y1)]
+        regions.append(SynthRegion(f"r{i}", pts, "heading" if rng.random() < 0.125 else "paragraph"))
+    separators = []
+    for s in range(n_separators):
+        vertical = s % 2 == 0
+        if vertical:
+            c = int(rng.integers(1, columns))
+            cx, ya = 60 + c * (colw + 40) - 20 + int(rng.integers(-6, 7)), int(rng.integers(40, H // 2))
+            box = (cx - int(rng.integers(1, 5)), ya, cx + int(rng.integers(1, 5)), ya + int(rng.integers(H // 8, H // 2)))
+        else:
+            c, r = int(rng.integers(0, columns)), int(rng.integers(1, max(rows, 2)))
+            xa, cy = 60 + c * (colw + 40) + int(rng.integers(-10, 30)), 60 + r * pitch - 10 + int(rng.integers(-6, 7))
+            box = (xa, cy - int(rng.integers(1, 4)), xa + int(rng.integers(colw // 2, 2 * colw)), cy + int(rng.integers(1, 4)))
+        xa, ya, xb, yb = box
+        shape = int(rng.integers(0, 3))
+        if shape == 0:                                      # the box
+            pts = [(xa, ya), (xb, ya), (xb, yb), (xa, yb)]
+        elif shape == 1:                                    # slanted: a triangle or a sheared quadrilateral
+            d = int(rng.integers(3, 40))
+            pts = [(xa, ya), (xb, ya + d), (xb, yb + d)] if rng.random() < 0.3 else [(xa, ya), (xb, ya + d), (xb, yb + d), (xa, yb)]
+        else:                                               # concave: a zigzag band of up to 12 points
+            m = int(rng.integers(3, 7))
+            if vertical:
+                ys = np.linspace(ya, yb, m).astype(int)
+                pts = [(xa + (6 if j % 2 else 0), int(y)) for j, y in enumerate(ys)] + \
+                      [(xb + (6 if j % 2 else 0), int(y)) for j, y in reversed(list(enumerate(ys)))]
+            else:
+                xs = np.linspace(xa, xb, m).astype(int)
+                pts = [(int(x), ya + (5 if j % 2 else 0)) for j, x in enumerate(xs)] + \
+                      [(int(x), yb + (5 if j % 2 else 0)) for j, x in reversed(list(enumerate(xs)))]
+        tag = ("vertical" if vertical else "horizontal") if rng.random() < 2 / 3 else None
+        separators.append(SynthSeparator(pts, tag))
+    return regions, separators
+
+
+def synth_region_page_xml(path, k: int = 0, n_regions: int = 12, n_separators: int = 6, W: int = 600, H: int = 900,
+                          image_filename: str = "x.png"):
+    """``synth_regions_and_separators`` as a PAGE-XML for the feature generation: every text region with two text lines (outline,
+    baseline, text, article id), the separators with their orientation in the custom attribute.  -> (regions, separators)"""
+    regions, separators = synth_regions_and_separators(k, n_regions, n_separators, W, H)
+    fmt = lambda pts: " ".join(f"{x},{y}" for x, y in pts)       # noqa: E731
+    out = []
+    for i, r in enumerate(regions):
+        xs, ys = [p[0] for p in r.points], [p[1] for p in r.points]
+        x0, x1, y0, y1 = min(xs), max(xs), min(ys), max(ys)
+        ym = (y0 + y1) // 2
+        lines = "".join(
+            f'<TextLine id="{r.id}l{j}" custom="readingOrder {{index:{j};}} structure {{id:a{i % 5}; type:article;}}">'
+            f'<Coords points="{x0},{ya} {x1},{ya} {x1},{yb} {x0},{yb}"/><Baseline points="{x0},{yb - 2} {x1},{yb - 2}"/>'
+            f'<TextEquiv><Unicode>t{j}</Unicode></TextEquiv></TextLine>' for j, (ya, yb) in enumerate(((y0, ym), (ym + 1, y1))))
+        out.append(f'<TextRegion id="{r.id}" type="{r.region_type}"><Coords points="{fmt(r.points)}"/>{lines}</TextRegion>')
+    for i, s in enumerate(separators):
+        custom = f' custom="structure {{orientation:{s.get_orientation()};}}"' if s.get_orientation() else ""
+        out.append(f'<SeparatorRegion id="s{i}"{custom}><Coords points="{fmt(s.points)}"/></SeparatorRegion>')
+    with open(path, "w") as f:
+        f.write('<?xml version="1.0" encoding="UTF-8"?>\n<PcGts xmlns="http://schema.primaresearch.org/PAGE/gts/'
+                'pagecontent/2013-07-15"><Metadata><Creator>t</Creator><Created>2020-01-01T00:00:00</Created>'
+                '<LastChange>2020-01-01T00:00:00</LastChange></Metadata>'
+                f'<Page imageFilename="{image_filename}" imageWidth="{W}" imageHeight="{H}">' + "".join(out) + '</Page></PcGts>')
+    return regions, separators

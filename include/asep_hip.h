@@ -47,7 +47,7 @@ const char* asep_version(void);
  * functions refuse a struct whose size is not the one the library was built with -- a caller written against an older or newer
  * header gets ASEP_ERR_ARG + a message instead of fields read from whatever follows its struct on the stack.
  * An added function moves the version too: a binding resolves every name it declares when it loads the library. */
-#define ASEP_ABI_VERSION 10
+#define ASEP_ABI_VERSION 11
 int asep_abi_version(void);
 /* ABI 6: the environment switches this build of the library reads when a model is loaded (one name per line).
  * Anything else in the environment is not a switch: a caller that records the switches a measurement ran under (bench.py) filters
@@ -597,6 +597,52 @@ int asep_cluster_grid_run_methods(asep_post* p, int n_pages, const int32_t* node
                                   const asep_cluster_method_setting* settings, const int32_t* line_off, const int32_t* line_node,
                                   const int32_t* line_gt, const int32_t* gtblk_off, const int32_t* gtblk_line_off,
                                   const int32_t* gtblk_lines, int32_t* out_labels, int32_t* out_counts, double* out_llh);
+
+/* ---- edge features (article_separation/gnn/input/feature_generation.py, the per-edge and per-pair part) ------------------------
+ * For all pages of a call at once, on the asep_post handle: the separator flags of every edge, the convex hull of every edge's two
+ * regions, and the pair bits the confidence masking reads.  Everything is integer geometry, so the results equal the host
+ * functions' bit for bit.  No floating point is used.
+ * Tables (offsets over pages; every *_off starts at 0 and never decreases):
+ *   page k has the text regions node_off[k] .. node_off[k+1]-1; region r has the points node_pts[node_pt_off[r] .. node_pt_off[r+1]-1]
+ *   ([x, y] int32, as np.asarray(points, dtype=np.int32) gives them) and node_heading[r] = 1 for a heading, else 0;
+ *   page k has the separator regions sep_off[k] .. sep_off[k+1]-1 with sep_pt_off / sep_pts in the same form and sep_orient[s] =
+ *   SeparatorRegion.get_orientation(): ASEP_SEP_NONE (no tag), ASEP_SEP_HORIZONTAL, ASEP_SEP_VERTICAL, ASEP_SEP_OTHER (any other text);
+ *   page k has the edges edge_off[k] .. edge_off[k+1]-1, edges[e] = {a, b} as region indices WITHIN the page.
+ * Every coordinate lies in [-ASEP_EDGE_COORD_MAX, ASEP_EDGE_COORD_MAX] = [-2^20, 2^20]: the centre of a box is a half-integer, so the
+ * kernels work in doubled coordinates, and with this bound every cross product fits an int64 (and is exact in the host's doubles,
+ * which is why the two agree).  Every region and every separator has at least one point.
+ * Outputs, each optional (NULL = not computed):
+ *   out_flags [E][2] uint8 = (horizontally_separated, vertically_separated) of get_edge_separator_feature_bb (rule ASEP_EDGE_RULE_BB;
+ *     a separator without tag is horizontal when height < 5 * width, both clamped to >= 1) or of get_edge_separator_feature_line
+ *     (ASEP_EDGE_RULE_LINE: the segment between the two box centres against the separator's box corners in the order (min,min),
+ *     (max,min), (min,max), (max,max), closed on the fly, or line_in_bounding_box; then against the separator's own polygon; a
+ *     separator tagged horizontal, or one with height < 5 * width, sets the first flag, any other the second).
+ *   out_hull [E][hull_cap][2] int32 and out_hull_n [E] (both or none): convex_hull(points of a + points of b) as the host returns it:
+ *     lexicographically smallest point first, strict left turns, collinear points dropped; all points collinear give [first, last],
+ *     all points equal give [p, p].  Entries behind out_hull_n[e] are 0.  hull_cap must hold the points of the two regions of every
+ *     edge, and E * hull_cap * 8 bytes must not exceed hull_budget_bytes (> 0; the device holds twice that as scratch): the caller
+ *     splits its edges over several calls.  An edge whose own row exceeds the budget cannot be computed and is refused as such.
+ *   out_pairs: one N_k x N_k uint8 matrix per page, one after the other: bit 0 = is_aligned_heading_separated(i, j), bit 1 =
+ *     is_aligned_horizontally_separated(i, j, separators) is true, computed for i < j and mirrored; the diagonal is 0.
+ * Bad or decreasing offsets, an edge index outside its page, a region or separator without points, a coordinate outside the bound,
+ * an unknown rule, a hull_cap or budget that does not fit: ASEP_ERR_ARG (asep_last_error), nothing is launched.  Zero pages, edges
+ * or separators are valid.  Host pointers in and out; returns after the results have arrived. */
+#define ASEP_EDGE_COORD_MAX (1 << 20)
+#define ASEP_EDGE_RULE_BB 0
+#define ASEP_EDGE_RULE_LINE 1
+#define ASEP_SEP_NONE 0
+#define ASEP_SEP_HORIZONTAL 1
+#define ASEP_SEP_VERTICAL 2
+#define ASEP_SEP_OTHER 3
+int asep_edge_features_run(asep_post* p, int n_pages, const int32_t* node_off, const int32_t* node_pt_off, const int32_t* node_pts,
+                           const uint8_t* node_heading, const int32_t* sep_off, const int32_t* sep_pt_off, const int32_t* sep_pts,
+                           const uint8_t* sep_orient, const int32_t* edge_off, const int32_t* edges, int rule, uint8_t* out_flags,
+                           int32_t* out_hull, int32_t* out_hull_n, int hull_cap, long long hull_budget_bytes, uint8_t* out_pairs);
+/* Device time in microseconds of the kernels of the calling thread's last asep_edge_features_run (0 if nothing ran). */
+double asep_edge_features_last_kernel_us(void);
+/* The kernels the calling thread's last asep_edge_features_run launched, as JSON text [{"kernel": name, "blocks": grid size}, ...]
+ * in launch order ("[]" if nothing ran).  Returns the text's length, or ASEP_ERR_ARG if buf is too small. */
+long asep_edge_features_last_launches(char* buf, size_t buflen);
 
 /* ---- relation net evaluation (article_separation/gnn/trainer/lav_rel.py) ----------------------------------------------
  * An accumulator of (score, label) pairs in HBM and sklearn's _binary_clf_curve over them: what precision_recall_curve,
