@@ -16,7 +16,7 @@ class AsepError(RuntimeError):
 
 
 MLP_MAX_HIDDEN = 4       # GNN_MLP_MAX (csrc/gnn_kernels.h): hidden layers of the interaction / attention / classifier MLPs
-ABI_VERSION = 11         # ASEP_ABI_VERSION of include/asep_hip.h this table was written against
+ABI_VERSION = 12         # ASEP_ABI_VERSION of include/asep_hip.h this table was written against
 
 
 class _SizedCfg(C.Structure):
@@ -113,6 +113,13 @@ SIGNATURES = {
     "asep_gnn_get_page_node_features": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     "asep_gnn_get_page_feature_map": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_int32)]),
     "asep_gnn_get_page_image": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_int32)]),
+    "asep_gnn_forward_batch": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, _P, _P, _P,
+                                         C.c_size_t]),
+    "asep_gnn_forward_batch_dev": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, _P, _P, _P,
+                                             C.c_size_t, _P]),
+    "asep_gnn_get_page_hidden": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
+    "asep_gnn_get_page_edges": (C.c_int, [_P, C.c_int, _P, _P, C.c_int]),
+    "asep_gnn_batch_launches": (C.c_long, [_P]),
     "asep_gnn_step_mode": (C.c_int, [_P]),
     "asep_gnn_get_node_features": (C.c_int, [_P, _P, C.c_size_t]),
     "asep_post_create": (_P, []),

@@ -14,6 +14,7 @@
 
 #include "asep_common.h"
 #include "fmap_kernels.h"
+#include "gnn_batch_kernels.h"
 #include "gnn_kernels.h"
 
 using namespace asep;
@@ -104,6 +105,15 @@ struct asep_gnn {
     size_t ef_cat_cap = 0;
     float* d_u_cat = nullptr;                        // concatenated node features of the last visual forward (own buffer)
     size_t u_cat_cap = 0;
+    // asep_gnn_forward_batch[_dev] (the graph part of the pages of one call; the section at the end of this file): its own buffers, so that
+    // the single-page forwards keep theirs; the page rows and the corrected lists of the last call for asep_gnn_get_page_hidden / _edges
+    BufferPool batch_pool;
+    std::vector<GnnPageRow> graph_pages;
+    unsigned long long graph_serial = ~0ull;         // fwd_serial right after the last batched graph call
+    const int32_t* gb_sorted = nullptr;
+    const int* gb_sfirst = nullptr;
+    const int* gb_rowptr = nullptr;
+    long batch_launches = 0;                         // kernels the last asep_gnn_forward_batch[_dev] launched (0: it was refused)
     void free_visual() {
         for (void* p : vis_owned)
             if (p) (void)hipFree(p);
@@ -1589,5 +1599,366 @@ double asep_gnn_flops(const asep_gnn* g, int N, int E_corrected, int R) {
     mac += (double)R * ((double)2 * g->H * c.cls_hidden1 + mlp_mac(g->cls_rest));
     return 2.0 * mac;
 }
+
+}  // extern "C"
+
+// ---- ABI 12: the graph part of the relation net for the pages of ONE call (gnn_batch_kernels.h) -----------------------------------------------
+// asep_gnn_forward_batch[_dev]: edge correction, T x (message, aggregation / attention soft-max, LSTM update) and the pair classifier each as one
+// launch over all pages.  The correction, the attention pairing's chunk ranks and the classifier go through the page table; every stage between
+// them is the single-page kernel over the nodes of the call (one CSR-by-target over all pages).  forward_impl above is the schedule this mirrors.
+namespace {
+
+const char* table_error_text(GnnTableError e) {
+    switch (e) {
+        case GNN_TABLE_BAD_N: return "N < 1";
+        case GNN_TABLE_BAD_E: return "E < 0";
+        case GNN_TABLE_BAD_R: return "R < 0";
+        case GNN_TABLE_PAGE_TOO_LARGE: return "N too large for the dense edge table (N^2 > 2^30)";
+        case GNN_TABLE_SUM_TABLES: return "the edge tables of the pages up to this one do not fit one allocation (sum of N^2 > 2^30): split the call";
+        case GNN_TABLE_SUM_INDEX: return "the nodes, edges or relations of the pages up to this one do not fit a 31-bit index: split the call";
+        default: return "";
+    }
+}
+
+// every check of a batched graph call that needs no device: the handle, the arrays, the page sizes and sums, the output buffer
+int batch_graph_checks(asep_gnn* g, const char* fn, int n_pages, const int32_t* N, const int32_t* E, const int32_t* R, const void* node_feat,
+                       const void* edges, const void* edge_feat, const void* probs_out, size_t max_floats, GnnPageTable& tab, GnnUnitTables& units) {
+    if (!g) { set_error("%s: null handle", fn); return ASEP_ERR_ARG; }
+    g->batch_launches = 0;
+    if (g->backbone || g->vis_total > 0 || g->cfg.visual_edge_dims > 0) {
+        set_error("%s: this graph has visual %s features: its pages go through asep_gnn_forward_visual_batch_dev2", fn,
+                  g->cfg.visual_edge_dims > 0 ? "edge" : "node");
+        return ASEP_ERR_ARG;
+    }
+    if (n_pages < 1) { set_error("%s: n_pages = %d, at least one page is needed", fn, n_pages); return ASEP_ERR_ARG; }
+    if (!N || !E || !R) { set_error("%s: the size array %s is NULL", fn, !N ? "N" : (!E ? "E" : "R")); return ASEP_ERR_ARG; }
+    if (!node_feat) { set_error("%s: node_feat is NULL", fn); return ASEP_ERR_ARG; }
+    if (g->cfg.num_classes < 2) { set_error("%s: the output is the class-1 probability, this model has %d class", fn, g->cfg.num_classes); return ASEP_ERR_ARG; }
+    const asep_gnn_cfg& c = g->cfg;
+    const int width = std::max({g->Uin, g->U, g->Upad, 64, g->H, g->H + g->Uin, g->I, g->Iout, std::max(c.attention_heads, 1) * std::max(g->att_xd, 1),
+                                (int)c.cls_hidden1, (int)c.num_classes});
+    int bad = -1;
+    const GnnTableError te = gnn_page_table(N, E, R, n_pages, c.undirected_graph != 0, width, tab, &bad);
+    if (te != GNN_TABLE_OK) {
+        set_error("%s: %s in page %d (N=%d E=%d R=%d)", fn, table_error_text(te), bad, N[bad], E[bad], R[bad]);
+        return te == GNN_TABLE_BAD_N || te == GNN_TABLE_BAD_E || te == GNN_TABLE_BAD_R ? ASEP_ERR_ARG : ASEP_ERR_UNSUPPORTED;
+    }
+    if (tab.edges > 0 && !edges) {
+        const int b = (int)(std::find_if(E, E + n_pages, [](int32_t e) { return e > 0; }) - E);
+        set_error("%s: edges is NULL, E = %d in page %d", fn, E[b], b);
+        return ASEP_ERR_ARG;
+    }
+    if (tab.edges > 0 && c.edge_feature_dim > 0 && !edge_feat) { set_error("%s: edge features required", fn); return ASEP_ERR_ARG; }
+    if (tab.rels > 0 && !probs_out) { set_error("%s: probs_out is NULL", fn); return ASEP_ERR_ARG; }
+    if (max_floats < tab.rels) {
+        set_error("%s: the output buffer holds %zu floats, the %d pages have %llu relations", fn, max_floats, n_pages, (unsigned long long)tab.rels);
+        return ASEP_ERR_ARG;
+    }
+    if (!gnn_unit_tables(tab, c.undirected_graph != 0, c.cls_hidden1, g->cls_fast ? 256 : PAIRG_P, units)) {
+        set_error("%s: the blocks of the %d pages do not fit one launch: split the call", fn, n_pages);
+        return ASEP_ERR_UNSUPPORTED;
+    }
+    return ASEP_OK;
+}
+
+#define BATCH_LAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); ++g->batch_launches; } while (0)
+
+int forward_batch_impl(asep_gnn* g, const char* fn, const GnnPageTable& tab, const GnnUnitTables& units, const int32_t* d_edges, const float* d_u,
+                       const float* d_ef, const int32_t* d_rel, float* d_out, hipStream_t s) {
+    const asep_gnn_cfg& c = g->cfg;
+    const int n = (int)tab.rows.size();
+    const int NN = (int)tab.nodes, EE = (int)tab.edges, RR = (int)tab.rels;
+    const int und = c.undirected_graph ? 1 : 0;
+    const size_t maxE = (size_t)tab.max_corrected;
+    BufferPool& pool = g->batch_pool;
+    g->stream = s;
+    g->N = NN;
+    ++g->fwd_serial;
+    pool.begin();
+    // the page table and the launches' unit tables: one blob, one copy
+    TableBlob blob;
+    const size_t o_rows = blob.add(tab.rows.data(), tab.rows.size());
+    const size_t o_node = blob.add(tab.node_begin.data(), tab.node_begin.size());
+    const size_t o_fill = blob.add(units.fill.data(), units.fill.size());
+    const size_t o_chunk = blob.add(units.chunk.data(), units.chunk.size());
+    const size_t o_pre = blob.add(units.pre.data(), units.pre.size());
+    const size_t o_cls = blob.add(units.cls.data(), units.cls.size());
+    asep_gnn::TableSlot* slot = nullptr;
+    if (int rc = put_tables(g, blob, s, &slot)) return rc;
+    auto pages = [&](size_t off) { return GnnPagesArgs{(const GnnPageRow*)(slot->d + o_rows), (const int32_t*)(slot->d + off), n}; };
+
+    // ---- edge correction (misc.py:7-151), every page's own table ----
+    EdgeBufs eb{};
+    eb.table = (int*)pool.get((size_t)tab.cells * sizeof(int));
+    eb.rowcnt = (int*)pool.get((size_t)NN * sizeof(int));
+    eb.colcnt = (int*)pool.get((size_t)NN * sizeof(int));
+    eb.rowptr = (int*)pool.get((size_t)(NN + 1) * sizeof(int));
+    eb.colptr = (int*)pool.get((size_t)(NN + 1) * sizeof(int));
+    eb.sorted = (int32_t*)pool.get(maxE * 2 * sizeof(int32_t));
+    eb.sfirst = (int*)pool.get(maxE * sizeof(int));
+    eb.tsrc = (int*)pool.get(maxE * sizeof(int));
+    eb.tfirst = (int*)pool.get(maxE * sizeof(int));
+    ASEP_HIP_CHECK(hipMemsetAsync(eb.table, 0x7f, (size_t)tab.cells * sizeof(int), s));
+    if (units.fill[n] > 0) BATCH_LAUNCH(edge_table_pages_kernel, dim3(units.fill[n]), dim3(256), 0, s, pages(o_fill), d_edges, und, eb.table);
+    BATCH_LAUNCH(edge_count_pages_kernel, dim3(NN), dim3(64), 0, s, pages(o_node), eb.table, eb.rowcnt, eb.colcnt);
+    BATCH_LAUNCH(edge_scan_kernel, dim3(1), dim3(1024), 0, s, eb.rowcnt, eb.colcnt, NN, eb.rowptr, eb.colptr);   // (integer sums: one scan over the call)
+    BATCH_LAUNCH(edge_emit_pages_kernel, dim3(NN), dim3(64), 0, s, pages(o_node), eb.table, eb.rowptr, eb.colptr, eb.sorted, eb.sfirst, eb.tsrc, eb.tfirst);
+    g->d_rowptr = eb.rowptr;
+    g->gb_sorted = eb.sorted; g->gb_sfirst = eb.sfirst; g->gb_rowptr = eb.rowptr;
+
+    const int H = g->H, I = g->I;
+    const size_t nh = (size_t)NN * H;
+    float* h[2] = {(float*)pool.get(nh * 4), (float*)pool.get(nh * 4)};
+    float* cs[2] = {(float*)pool.get(nh * 4), (float*)pool.get(nh * 4)};
+    float* x = (float*)pool.get((size_t)NN * std::max(I, g->Iout) * 4);
+    float* Pt = (float*)pool.get((size_t)NN * c.cls_hidden1 * 4);
+    float* Qt = (float*)pool.get((size_t)NN * c.cls_hidden1 * 4);
+    float* probs = (float*)pool.get((size_t)std::max(RR, 1) * c.num_classes * 4);
+    const float* d_fed = d_u;
+    const int Eall = std::max(EE, 1);                        // tfirst holds rows of the call's edge features: `tfirst % Eall` is the row itself
+    if (g->Wc) {
+        float* uc = (float*)pool.get((size_t)NN * g->U * 4);
+        BATCH_LAUNCH(gnn_compress_kernel, dim3(cdiv(NN * g->U, 256)), dim3(256), 0, s, d_u, NN, g->Uin, g->Wc, g->bc, g->U, uc);
+        d_u = uc;
+    }
+    int* att_eidx = nullptr;
+    int* att_widx = nullptr;
+    float *att_M = nullptr, *att_A = nullptr, *att_S = nullptr;
+    if (c.attention_heads > 0) {
+        att_eidx = (int*)pool.get(maxE * sizeof(int));
+        att_M = (float*)pool.get(maxE * c.attention_heads * g->att_xd * sizeof(float));
+        att_A = (float*)pool.get(maxE * c.attention_heads * sizeof(float));
+        att_S = (float*)pool.get(maxE * c.attention_heads * sizeof(float));
+        att_widx = (int*)pool.get(maxE * sizeof(int));
+        BATCH_LAUNCH(edge_rank_kernel, dim3(NN), dim3(64), 0, s, eb.colptr, eb.tsrc, eb.rowptr, eb.sorted, NN, att_eidx);
+        BATCH_LAUNCH(edge_chunk_rank_pages_kernel, dim3(units.chunk[n]), dim3(256), 0, s, pages(o_chunk), eb.sorted, eb.rowptr, eb.colptr, att_widx);
+    }
+    float* upad = nullptr;
+    const int mode = step_mode_of(g);
+    if (mode == STEP_BIG) {
+        upad = (float*)pool.get((size_t)NN * g->Upad * 4);
+        BATCH_LAUNCH(gnn_pad_rows_kernel, dim3(cdiv(NN * g->Upad, 256)), dim3(256), 0, s, d_u, NN, g->U, upad, g->Upad);
+    }
+    float *fPu = nullptr, *fP[2] = {nullptr, nullptr}, *fC = nullptr;
+    if (mode == STEP_FACT && c.num_transition_steps > 0) {
+        fPu = (float*)pool.get((size_t)NN * 64 * 4);
+        fP[0] = (float*)pool.get((size_t)NN * 64 * 4);
+        fP[1] = (float*)pool.get((size_t)NN * 64 * 4);
+        fC = (float*)pool.get(maxE * 32 * 4);
+        FactPreArgs fa{};
+        fa.u = d_u; fa.ef = d_ef; fa.tptr = eb.colptr; fa.tsrc = eb.tsrc; fa.tfirst = eb.tfirst;
+        fa.Wuu = g->Wuu; fa.Wde = g->Wde; fa.b1 = g->b1; fa.Pu = fPu; fa.C = fC;
+        fa.N = NN; fa.U = g->U; fa.Ed = g->Ed; fa.E = Eall;
+        BATCH_LAUNCH(gnn_fact_pre_kernel, dim3(NN), dim3(256), g->fact_pre_lds, s, fa);
+    }
+    if (mode != STEP_FACT || c.num_transition_steps == 0) {
+        ASEP_HIP_CHECK(hipMemsetAsync(h[0], 0, nh * 4, s));
+        ASEP_HIP_CHECK(hipMemsetAsync(cs[0], 0, nh * 4, s));
+    }
+    int cur = 0;
+    for (int t = 0; t < c.num_transition_steps; ++t) {
+        if (mode == STEP_FACT) {
+            StepFactArgs sa{};
+            sa.u = d_u; sa.h_in = h[cur]; sa.c_in = cs[cur]; sa.tptr = eb.colptr; sa.tsrc = eb.tsrc;
+            sa.P_in = t == 0 ? fPu : fP[t & 1];
+            sa.Pu = fPu; sa.C = fC;
+            sa.A1 = (const gf32x4*)g->A1f; sa.A2 = (const gf32x4*)g->A2; sa.b2 = g->b2; sa.Whh = g->Whh;
+            for (int q = 0; q < 4; ++q) { sa.Wg[q] = g->Wg[q]; sa.bg[q] = g->bg[q]; }
+            sa.h_out = h[cur ^ 1]; sa.c_out = cs[cur ^ 1];
+            sa.P_out = t + 1 < c.num_transition_steps ? fP[(t + 1) & 1] : nullptr;
+            sa.N = NN; sa.U = g->U; sa.first = t == 0;
+            BATCH_LAUNCH(gnn_step_fact_kernel, dim3(NN), dim3(256), g->fact_lds, s, sa);
+        } else if (mode == STEP_SMALL) {
+            StepArgs sa{};
+            sa.u = d_u; sa.h_in = h[cur]; sa.c_in = cs[cur]; sa.ef = d_ef;
+            sa.tptr = eb.colptr; sa.tsrc = eb.tsrc; sa.tfirst = eb.tfirst;
+            sa.A1 = (const gf32x4*)g->A1; sa.A2 = (const gf32x4*)g->A2; sa.b1 = g->b1; sa.b2 = g->b2;
+            for (int q = 0; q < 4; ++q) { sa.Wg[q] = g->Wg[q]; sa.bg[q] = g->bg[q]; }
+            sa.h_out = h[cur ^ 1]; sa.c_out = cs[cur ^ 1];
+            sa.N = NN; sa.U = g->U; sa.Ed = g->Ed; sa.E = Eall; sa.nch = g->nch;
+            sa.qdesc = g->qdesc;
+            BATCH_LAUNCH(gnn_step_kernel, dim3(NN), dim3(256), 0, s, sa);
+        } else if (mode == STEP_BIG) {
+            StepBigArgs sa{};
+            sa.u = upad; sa.h_in = h[cur]; sa.c_in = cs[cur]; sa.ef = d_ef;
+            sa.tptr = eb.colptr; sa.tsrc = eb.tsrc; sa.tfirst = eb.tfirst;
+            sa.A1 = (const gf32x4*)g->A1; sa.A2 = (const gf32x4*)g->A2; sa.b1 = g->b1; sa.b2 = g->b2;
+            for (int q = 0; q < 4; ++q) { sa.Wg[q] = g->Wg[q]; sa.bg[q] = g->bg[q]; }
+            sa.h_out = h[cur ^ 1]; sa.c_out = cs[cur ^ 1];
+            sa.N = NN; sa.U = g->U; sa.Upad = g->Upad; sa.Ed = g->Ed; sa.E = Eall; sa.nch = g->nch;
+            sa.qdesc = g->qdesc;
+            BATCH_LAUNCH(gnn_step_big_kernel, dim3(NN), dim3(256), g->big_lds, s, sa);
+        } else if (c.attention_heads > 0) {
+            MsgAttArgs aa{};
+            aa.u = d_u; aa.h = h[cur]; aa.ef = d_ef; aa.tptr = eb.colptr; aa.tsrc = eb.tsrc; aa.tfirst = eb.tfirst; aa.eidx = att_eidx;
+            aa.hd = g->d_att_w;
+            aa.M = att_M; aa.A = att_A;
+            aa.N = NN; aa.U = g->U; aa.Ed = g->Ed; aa.E = Eall; aa.H = H;
+            aa.xd = g->att_xd; aa.heads = c.attention_heads; aa.Etot = (int)maxE; aa.maxh = g->msg_maxh;
+            const size_t lds = ((size_t)g->K + 2 * (size_t)g->msg_maxh) * sizeof(float);
+            BATCH_LAUNCH(gnn_msg_att_kernel, dim3(NN), dim3(256), lds, s, aa);
+            BATCH_LAUNCH(gnn_att_softmax_kernel, dim3(NN), dim3(64), 0, s, eb.colptr, att_eidx, att_A, c.attention_heads, (int)maxE, att_S);
+            BATCH_LAUNCH(gnn_att_aggregate_kernel, dim3(NN), dim3(64), 0, s, eb.colptr, att_eidx, att_widx, att_S, att_M, c.attention_heads,
+                         g->att_xd, (int)maxE, c.attention_merge, c.aggregation_type, x);
+        } else {
+            MsgGenArgs ma{};
+            ma.u = d_u; ma.h = h[cur]; ma.ef = d_ef; ma.tptr = eb.colptr; ma.tsrc = eb.tsrc; ma.tfirst = eb.tfirst;
+            ma.mlp = g->msg; ma.x = x;
+            ma.N = NN; ma.U = g->U; ma.Ed = g->Ed; ma.E = Eall; ma.H = H; ma.I = I; ma.maxh = g->msg_maxh;
+            ma.agg_max = c.aggregation_type;
+            const size_t lds = ((size_t)g->K + 2 * (size_t)g->msg_maxh + I) * sizeof(float);
+            BATCH_LAUNCH(gnn_message_generic_kernel, dim3(NN), dim3(256), lds, s, ma);
+        }
+        if (mode == STEP_GENERIC) {
+            LstmGenArgs la{};
+            la.x = x; la.h_in = h[cur]; la.c_in = cs[cur]; la.u = d_u;
+            for (int q = 0; q < 4; ++q) { la.Wg[q] = g->Wg[q]; la.bg[q] = g->bg[q]; }
+            la.h_out = h[cur ^ 1]; la.c_out = cs[cur ^ 1]; la.N = NN; la.U = g->U; la.H = H; la.I = g->Iout;
+            la.use_h = c.lstm_use_hidden; la.use_u = c.lstm_use_input;
+            BATCH_LAUNCH(gnn_lstm_generic_kernel, dim3(cdiv(NN * H, 256)), dim3(256), 0, s, la);
+        }
+        cur ^= 1;
+    }
+    g->d_h = h[cur];
+    const float* hcls = h[cur];
+    int Hc = H;
+    if (c.output_type != 0) {
+        Hc = c.output_type == 2 ? H + g->Uin : H;
+        float* y = (float*)pool.get((size_t)NN * Hc * 4);
+        BATCH_LAUNCH(gnn_output_type_kernel, dim3(cdiv(NN * Hc, 256)), dim3(256), 0, s, h[cur], d_fed, NN, H, g->Uin, g->Wout, c.output_type, y);
+        hcls = y;
+    }
+    if (RR > 0) {
+        BATCH_LAUNCH(gnn_pair_pre_pages_kernel, dim3(units.pre[n]), dim3(256), 0, s, pages(o_pre), hcls, Hc, g->C1, c.cls_hidden1, Pt, Qt);
+        if (g->cls_fast) {
+            PairArgs pa{};
+            pa.Pt = Pt; pa.Qt = Qt; pa.b1 = g->cb1; pa.W2 = g->C2; pa.b2 = g->cb2; pa.W3 = g->C3; pa.b3 = g->cb3;
+            pa.rel = d_rel; pa.out = probs;
+            BATCH_LAUNCH((gnn_pair_cls_pages_kernel<64, 32, 2>), dim3(units.cls[n]), dim3(256), 0, s, pages(o_cls), pa);
+        } else {
+            PairGenArgs pg{};
+            pg.Pt = Pt; pg.Qt = Qt; pg.b1 = g->cb1; pg.rest = g->cls_rest; pg.rel = d_rel; pg.out = probs;
+            pg.maxw = g->cls_maxw;
+            BATCH_LAUNCH(gnn_pair_cls_generic_pages_kernel, dim3(units.cls[n]), dim3(256), 2 * (size_t)PAIRG_P * g->cls_maxw * sizeof(float), s,
+                         pages(o_cls), pg);
+        }
+        BATCH_LAUNCH(gnn_take_class_kernel, dim3(cdiv(RR, 256)), dim3(256), 0, s, probs, RR, c.num_classes, 1, d_out);
+    }
+    if (int rc = tables_read(slot, s)) return rc;
+    ASEP_HIP_CHECK(hipGetLastError());
+    g->graph_pages = tab.rows;
+    g->graph_serial = g->fwd_serial;
+    (void)fn;
+    return ASEP_OK;
+}
+#undef BATCH_LAUNCH
+
+// "names a node outside" per page, as check_indices says it for one page
+int check_page_indices(const char* fn, const char* what, const int32_t* idx, const GnnPageTable& tab, bool relations) {
+    for (size_t b = 0; b < tab.rows.size(); ++b) {
+        const GnnPageRow& r = tab.rows[b];
+        const int32_t* p = idx + 2 * (size_t)(relations ? r.rel_off : r.edge_off);
+        const size_t cnt = (size_t)(relations ? r.R : r.E);
+        for (size_t i = 0; i < 2 * cnt; ++i)
+            if (p[i] < 0 || p[i] >= r.N) {
+                set_error("%s: %s[%zu] = (%d, %d) names a node outside 0..%d in page %d", fn, what, i / 2, p[i & ~(size_t)1], p[i | 1], r.N - 1, (int)b);
+                return ASEP_ERR_ARG;
+            }
+    }
+    return ASEP_OK;
+}
+
+const GnnPageRow* graph_batch_page(asep_gnn* g, const char* fn, int page) {
+    if (!g || g->graph_serial != g->fwd_serial || g->graph_pages.empty()) {
+        set_error("%s: the handle's last forward was not asep_gnn_forward_batch[_dev]", fn);
+        return nullptr;
+    }
+    if (page < 0 || page >= (int)g->graph_pages.size()) {
+        set_error("%s: page %d, the last call had %zu pages", fn, page, g->graph_pages.size());
+        return nullptr;
+    }
+    return &g->graph_pages[(size_t)page];
+}
+
+}  // namespace
+
+extern "C" {
+
+int asep_gnn_forward_batch_dev(asep_gnn* g, int n_pages, const int32_t* N, const int32_t* E, const int32_t* R, const float* d_node_feat,
+                               const int32_t* d_edges, const float* d_edge_feat, const int32_t* d_relations, float* d_probs_out,
+                               size_t max_floats, void* stream) {
+    ASEP_GUARD_BEGIN
+    const char* fn = "asep_gnn_forward_batch_dev";
+    GnnPageTable tab;
+    GnnUnitTables units;
+    if (int rc = batch_graph_checks(g, fn, n_pages, N, E, R, d_node_feat, d_edges, d_edge_feat, d_probs_out, max_floats, tab, units)) return rc;
+    return forward_batch_impl(g, fn, tab, units, d_edges, d_node_feat, d_edge_feat, d_relations, d_probs_out, (hipStream_t)stream);
+    ASEP_GUARD_END
+}
+
+int asep_gnn_forward_batch(asep_gnn* g, int n_pages, const int32_t* N, const int32_t* E, const int32_t* R, const float* node_feat,
+                           const int32_t* edges, const float* edge_feat, const int32_t* relations, float* probs_out, size_t max_floats) {
+    ASEP_GUARD_BEGIN
+    const char* fn = "asep_gnn_forward_batch";
+    GnnPageTable tab;
+    GnnUnitTables units;
+    int rc = batch_graph_checks(g, fn, n_pages, N, E, R, node_feat, edges, edge_feat, probs_out, max_floats, tab, units);
+    if (rc) return rc;
+    if (tab.edges > 0 && (rc = check_page_indices(fn, "interacting_nodes", edges, tab, false))) return rc;
+    if (relations && tab.rels > 0 && (rc = check_page_indices(fn, "relations", relations, tab, true))) return rc;
+    const size_t ne = (size_t)tab.edges * 2, nu = (size_t)tab.nodes * g->Uin, nf = (size_t)tab.edges * g->Ed;
+    const size_t nr = relations ? (size_t)tab.rels * 2 : 0, no = (size_t)tab.rels;
+    g->host_stage.begin();
+    int32_t* d_e = (int32_t*)g->host_stage.get(std::max<size_t>(ne, 1) * sizeof(int32_t));
+    float* d_u = (float*)g->host_stage.get(std::max<size_t>(nu, 1) * sizeof(float));
+    float* d_f = (float*)g->host_stage.get(std::max<size_t>(nf, 1) * sizeof(float));
+    int32_t* d_r = (int32_t*)g->host_stage.get(std::max<size_t>(nr, 1) * sizeof(int32_t));
+    float* d_o = (float*)g->host_stage.get(std::max<size_t>(no, 1) * sizeof(float));
+    if (ne) ASEP_HIP_CHECK(hipMemcpyAsync(d_e, edges, ne * sizeof(int32_t), hipMemcpyHostToDevice, nullptr));
+    ASEP_HIP_CHECK(hipMemcpyAsync(d_u, node_feat, nu * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    if (nf && edge_feat) ASEP_HIP_CHECK(hipMemcpyAsync(d_f, edge_feat, nf * sizeof(float), hipMemcpyHostToDevice, nullptr));
+    if (nr) ASEP_HIP_CHECK(hipMemcpyAsync(d_r, relations, nr * sizeof(int32_t), hipMemcpyHostToDevice, nullptr));
+    rc = forward_batch_impl(g, fn, tab, units, ne ? d_e : nullptr, d_u, (nf && edge_feat) ? d_f : nullptr, nr ? d_r : nullptr, d_o, nullptr);
+    if (rc) return rc;
+    if (no) ASEP_HIP_CHECK(hipMemcpyAsync(probs_out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    ASEP_HIP_CHECK(hipStreamSynchronize(nullptr));
+    return ASEP_OK;
+    ASEP_GUARD_END
+}
+
+int asep_gnn_get_page_hidden(asep_gnn* g, int page, float* out, size_t max_floats) {
+    ASEP_GUARD_BEGIN
+    const char* fn = "asep_gnn_get_page_hidden";
+    const GnnPageRow* r = graph_batch_page(g, fn, page);
+    if (!r) return ASEP_ERR_ARG;
+    const size_t cnt = (size_t)r->N * g->H;
+    if (!out || max_floats < cnt) { set_error("%s: buffer too small (%zu floats needed)", fn, cnt); return ASEP_ERR_ARG; }
+    ASEP_HIP_CHECK(hipStreamSynchronize(g->stream));
+    ASEP_HIP_CHECK(hipMemcpy(out, g->d_h + (size_t)r->node_off * g->H, cnt * sizeof(float), hipMemcpyDeviceToHost));
+    return ASEP_OK;
+    ASEP_GUARD_END
+}
+
+int asep_gnn_get_page_edges(asep_gnn* g, int page, int32_t* out_edges, int32_t* out_first, int max_edges) {
+    ASEP_GUARD_BEGIN
+    const char* fn = "asep_gnn_get_page_edges";
+    const GnnPageRow* r = graph_batch_page(g, fn, page);
+    if (!r) return ASEP_ERR_ARG;
+    ASEP_HIP_CHECK(hipStreamSynchronize(g->stream));
+    int ends[2] = {0, 0};
+    ASEP_HIP_CHECK(hipMemcpy(&ends[0], g->gb_rowptr + r->node_off, sizeof(int), hipMemcpyDeviceToHost));
+    ASEP_HIP_CHECK(hipMemcpy(&ends[1], g->gb_rowptr + r->node_off + r->N, sizeof(int), hipMemcpyDeviceToHost));
+    const int cnt = ends[1] - ends[0];
+    if (cnt < 0 || (cnt > 0 && (!out_edges || max_edges < cnt))) { set_error("%s: page %d has %d corrected edges, the buffer holds %d", fn, page, cnt, max_edges); return ASEP_ERR_ARG; }
+    if (cnt > 0) {
+        ASEP_HIP_CHECK(hipMemcpy(out_edges, g->gb_sorted + 2 * (size_t)ends[0], (size_t)cnt * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int i = 0; i < 2 * cnt; ++i) out_edges[i] -= r->node_off;       // node numbers of the call -> of the page
+        if (out_first) ASEP_HIP_CHECK(hipMemcpy(out_first, g->gb_sfirst + ends[0], (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    return cnt;
+    ASEP_GUARD_END
+}
+
+long asep_gnn_batch_launches(const asep_gnn* g) { return g ? g->batch_launches : ASEP_ERR_ARG; }
 
 }  // extern "C"

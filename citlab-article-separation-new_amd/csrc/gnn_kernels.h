@@ -21,10 +21,11 @@ constexpr int GNN_H = 32;            // hidden / interaction width handled by th
 constexpr int EMPTY_SLOT = 0x7f7f7f7f;
 
 // table[from*N+to] = first index of that directed edge in the (symmetrised) list  (misc.py:47-88)
-__global__ __launch_bounds__(256) void edge_table_kernel(const int32_t* __restrict__ edges, int E, int N,
-                                                         int undirected, int* __restrict__ table) {
+// (the bodies of the edge kernels take their block and grid: gnn_batch_kernels.h runs them per page of a page table)
+__device__ __forceinline__ void edge_table_body(const int32_t* __restrict__ edges, int E, int N, int undirected, int* __restrict__ table,
+                                                const int bx, const int gx) {
     const int total = undirected ? 2 * E : E;
-    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+    for (int idx = bx * 256 + threadIdx.x; idx < total; idx += gx * 256) {
         int f, t;
         if (idx < E) { f = edges[2 * idx]; t = edges[2 * idx + 1]; }
         else { f = edges[2 * (idx - E) + 1]; t = edges[2 * (idx - E)]; }
@@ -32,11 +33,15 @@ __global__ __launch_bounds__(256) void edge_table_kernel(const int32_t* __restri
         atomicMin(&table[(size_t)f * N + t], idx);
     }
 }
+__global__ __launch_bounds__(256) void edge_table_kernel(const int32_t* __restrict__ edges, int E, int N,
+                                                         int undirected, int* __restrict__ table) {
+    edge_table_body(edges, E, N, undirected, table, (int)blockIdx.x, (int)gridDim.x);
+}
 
 // per-row (from) and per-column (to) counts of occupied table cells; one wave per row / column
-__global__ __launch_bounds__(64) void edge_count_kernel(const int* __restrict__ table, int N,
-                                                        int* __restrict__ rowcnt, int* __restrict__ colcnt) {
-    const int r = blockIdx.x, lane = threadIdx.x;
+__device__ __forceinline__ void edge_count_body(const int* __restrict__ table, int N, int* __restrict__ rowcnt, int* __restrict__ colcnt,
+                                                const int r) {
+    const int lane = threadIdx.x;
     int rc = 0, cc = 0;
     for (int k = lane; k < N; k += 64) {
         rc += table[(size_t)r * N + k] != EMPTY_SLOT;
@@ -44,6 +49,10 @@ __global__ __launch_bounds__(64) void edge_count_kernel(const int* __restrict__ 
     }
     for (int o = 32; o > 0; o >>= 1) { rc += __shfl_down(rc, o); cc += __shfl_down(cc, o); }
     if (lane == 0) { rowcnt[r] = rc; colcnt[r] = cc; }
+}
+__global__ __launch_bounds__(64) void edge_count_kernel(const int* __restrict__ table, int N,
+                                                        int* __restrict__ rowcnt, int* __restrict__ colcnt) {
+    edge_count_body(table, N, rowcnt, colcnt, (int)blockIdx.x);
 }
 
 // exclusive scans of rowcnt / colcnt (N is a few hundred: one workgroup)
@@ -72,11 +81,14 @@ __global__ __launch_bounds__(1024) void edge_scan_kernel(const int* __restrict__
 
 // emit (a) the corrected edge list sorted by from*N+to with first-occurrence indices (misc.py:91-104)
 //      (b) the same edges grouped by target (CSR over column 1) for the aggregation
-__global__ __launch_bounds__(64) void edge_emit_kernel(const int* __restrict__ table, int N,
-                                                       const int* __restrict__ rowptr, const int* __restrict__ colptr,
-                                                       int32_t* __restrict__ sorted_edges, int* __restrict__ sorted_first,
-                                                       int* __restrict__ tsrc, int* __restrict__ tfirst) {
-    const int r = blockIdx.x, lane = threadIdx.x;
+// PAGES (gnn_batch_kernels.h): row r of one page of a call.  rowptr / colptr are the page's part of the call's scans, so the write positions are
+// those of the call; node numbers leave as numbers of the call (+ node_off), and tfirst as the row of the call's edge features
+// (first % E + edge_off: what the message kernels' `tfirst % E` selects on the page alone); sorted_first stays the page's own index.
+template <bool PAGES>
+__device__ __forceinline__ void edge_emit_body(const int* __restrict__ table, int N, const int* __restrict__ rowptr, const int* __restrict__ colptr,
+                                               int32_t* __restrict__ sorted_edges, int* __restrict__ sorted_first, int* __restrict__ tsrc,
+                                               int* __restrict__ tfirst, const int r, const int node_off, const int edge_off, const int E) {
+    const int lane = threadIdx.x;
     int wr = rowptr[r], wc = colptr[r];
     for (int k0 = 0; k0 < N; k0 += 64) {
         const int k = k0 + lane;
@@ -86,14 +98,23 @@ __global__ __launch_bounds__(64) void edge_emit_kernel(const int* __restrict__ t
         const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
         if (vr != EMPTY_SLOT) {
             const int p = wr + __popcll(mr & below);
-            sorted_edges[2 * p] = r; sorted_edges[2 * p + 1] = k; sorted_first[p] = vr;
+            if constexpr (PAGES) { sorted_edges[2 * p] = r + node_off; sorted_edges[2 * p + 1] = k + node_off; }
+            else { sorted_edges[2 * p] = r; sorted_edges[2 * p + 1] = k; }
+            sorted_first[p] = vr;
         }
         if (vc != EMPTY_SLOT) {
             const int p = wc + __popcll(mc & below);
-            tsrc[p] = k; tfirst[p] = vc;
+            if constexpr (PAGES) { tsrc[p] = k + node_off; tfirst[p] = vc % E + edge_off; }
+            else { tsrc[p] = k; tfirst[p] = vc; }
         }
         wr += __popcll(mr); wc += __popcll(mc);
     }
+}
+__global__ __launch_bounds__(64) void edge_emit_kernel(const int* __restrict__ table, int N,
+                                                       const int* __restrict__ rowptr, const int* __restrict__ colptr,
+                                                       int32_t* __restrict__ sorted_edges, int* __restrict__ sorted_first,
+                                                       int* __restrict__ tsrc, int* __restrict__ tfirst) {
+    edge_emit_body<false>(table, N, rowptr, colptr, sorted_edges, sorted_first, tsrc, tfirst, (int)blockIdx.x, 0, 0, 1);
 }
 
 __global__ __launch_bounds__(256) void edge_feat_gather_kernel(const float* __restrict__ ef, int E, int Ed,
@@ -847,15 +868,15 @@ __global__ __launch_bounds__(64) void edge_rank_kernel(const int* __restrict__ c
 // (to, from)-sorted list -- csr positions tptr[c S] ... -- and its (from, to)-sorted list -- the chunk's edges in edge-index order.
 // widx[e] = tptr[c S] + (number of edges e' < e that end in chunk c): the csr position whose soft-max value edge e is multiplied
 // with (one chunk: widx[e] = e).  One workgroup per chunk scans the edge list.
-__global__ __launch_bounds__(256) void edge_chunk_rank_kernel(const int32_t* __restrict__ sorted_edges, const int* __restrict__ rowptr,
-                                                            const int* __restrict__ colptr, int N, int S, int* __restrict__ widx) {
+// body: the chunk of the target nodes lo .. hi - 1, over the edges ebeg .. Etot - 1 (a page of a call: its part of the call's list)
+__device__ __forceinline__ void edge_chunk_rank_body(const int32_t* __restrict__ sorted_edges, const int* __restrict__ colptr, const int ebeg,
+                                                     const int Etot, const int lo, const int hi, int* __restrict__ widx) {
     __shared__ int wsum[4];
     __shared__ int carry;
-    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int Etot = rowptr[N], lo = c * S, hi = min(N, lo + S);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) carry = colptr[lo];
     __syncthreads();
-    for (int e0 = 0; e0 < Etot; e0 += 256) {
+    for (int e0 = ebeg; e0 < Etot; e0 += 256) {
         const int e = e0 + tid;
         const int t = e < Etot ? sorted_edges[2 * e + 1] : -1;
         const bool in = t >= lo && t < hi;
@@ -870,6 +891,11 @@ __global__ __launch_bounds__(256) void edge_chunk_rank_kernel(const int32_t* __r
         if (tid == 0) carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
         __syncthreads();
     }
+}
+__global__ __launch_bounds__(256) void edge_chunk_rank_kernel(const int32_t* __restrict__ sorted_edges, const int* __restrict__ rowptr,
+                                                            const int* __restrict__ colptr, int N, int S, int* __restrict__ widx) {
+    const int lo = (int)blockIdx.x * S;
+    edge_chunk_rank_body(sorted_edges, colptr, 0, rowptr[N], lo, min(N, lo + S), widx);
 }
 
 constexpr int GNN_MAX_HEADS = 8;
@@ -1055,9 +1081,9 @@ __global__ __launch_bounds__(256) void gnn_lstm_kernel(const LstmArgs a) {
 // the concatenation, so it is evaluated once per node:  P[a] = h_a . W1[0:32],  Q[b] = h_b . W1[32:64]
 // (stored transposed [H1][N] for coalesced per-pair reads); per pair: relu(P+Q+b1) -> H2 -> classes.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gnn_pair_pre_kernel(const float* __restrict__ h, int N, int H, const float* __restrict__ W1,
-                                                           int H1, float* __restrict__ Pt, float* __restrict__ Qt) {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < N * H1; i += gridDim.x * 256) {
+__device__ __forceinline__ void gnn_pair_pre_body(const float* __restrict__ h, int N, int H, const float* __restrict__ W1, int H1,
+                                                  float* __restrict__ Pt, float* __restrict__ Qt, const int bx, const int gx) {
+    for (int i = bx * 256 + threadIdx.x; i < N * H1; i += gx * 256) {
         const int n = i % N, k = i / N;
         float p = 0.f, q = 0.f;
         for (int d = 0; d < H; ++d) {
@@ -1068,6 +1094,10 @@ __global__ __launch_bounds__(256) void gnn_pair_pre_kernel(const float* __restri
         Pt[(size_t)k * N + n] = p;
         Qt[(size_t)k * N + n] = q;
     }
+}
+__global__ __launch_bounds__(256) void gnn_pair_pre_kernel(const float* __restrict__ h, int N, int H, const float* __restrict__ W1,
+                                                           int H1, float* __restrict__ Pt, float* __restrict__ Qt) {
+    gnn_pair_pre_body(h, N, H, W1, H1, Pt, Qt, (int)blockIdx.x, (int)gridDim.x);
 }
 
 struct PairArgs {
@@ -1146,22 +1176,26 @@ constexpr int PAIRG_P = 32;             // pairs per block; 8 threads per pair
 
 // any number of hidden layers of any width (graph_relation.py:196 num_hidden_units is a free list): 32 pairs per block, the
 // activations of a layer in an LDS tile [pair][unit], 8 threads of a pair share the units of the next layer -- a fallback
-__global__ __launch_bounds__(256) void gnn_pair_cls_generic_kernel(const PairGenArgs a) {
+// (Pt, Qt, rel, out, N, R: the page's, apart from `a` -- the batched form passes a page of a call, and a changed copy of `a` would move the
+// layer table, which is indexed by a loop counter, from the kernel arguments into scratch)
+__device__ __forceinline__ void gnn_pair_cls_generic_body(const PairGenArgs& a, const float* __restrict__ Pt, const float* __restrict__ Qt,
+                                                          const int32_t* __restrict__ rel, float* __restrict__ out, const int N, const int R,
+                                                          const int bx) {
     extern __shared__ float spg[];
     float* cur = spg;                                   // [PAIRG_P][maxw]
     float* nxt = spg + PAIRG_P * a.maxw;
     const int tid = threadIdx.x, pl = tid >> 3, sub = tid & 7;
-    const int r = blockIdx.x * PAIRG_P + pl;
+    const int r = bx * PAIRG_P + pl;
     const int NC = a.rest.dims[a.rest.nl];
     int na = -1, nb = -1;
-    if (r < a.R) {
-        if (a.rel) { na = a.rel[2 * r]; nb = a.rel[2 * r + 1]; }
-        else { na = r / a.N; nb = r - na * a.N; }
+    if (r < R) {
+        if (rel) { na = rel[2 * r]; nb = rel[2 * r + 1]; }
+        else { na = r / N; nb = r - na * N; }
     }
-    const bool valid = r < a.R && (unsigned)na < (unsigned)a.N && (unsigned)nb < (unsigned)a.N;
+    const bool valid = r < R && (unsigned)na < (unsigned)N && (unsigned)nb < (unsigned)N;
     const int h1 = a.rest.dims[0];
     for (int d = sub; d < h1; d += 8)
-        cur[pl * a.maxw + d] = valid ? fmaxf(a.Pt[(size_t)d * a.N + na] + a.Qt[(size_t)d * a.N + nb] + a.b1[d], 0.f) : 0.f;
+        cur[pl * a.maxw + d] = valid ? fmaxf(Pt[(size_t)d * N + na] + Qt[(size_t)d * N + nb] + a.b1[d], 0.f) : 0.f;
     __syncthreads();
     for (int l = 0; l < a.rest.nl; ++l) {
         const int din = a.rest.dims[l], dout = a.rest.dims[l + 1];
@@ -1174,9 +1208,9 @@ __global__ __launch_bounds__(256) void gnn_pair_cls_generic_kernel(const PairGen
         __syncthreads();
         float* t = cur; cur = nxt; nxt = t;
     }
-    if (sub == 0 && r < a.R) {
+    if (sub == 0 && r < R) {
         if (!valid) {                                   // a pair that names no node: visible, not UB
-            for (int c = 0; c < NC; ++c) a.out[(size_t)r * NC + c] = __builtin_nanf("");
+            for (int c = 0; c < NC; ++c) out[(size_t)r * NC + c] = __builtin_nanf("");
             return;
         }
         const float* lg = cur + pl * a.maxw;
@@ -1184,8 +1218,11 @@ __global__ __launch_bounds__(256) void gnn_pair_cls_generic_kernel(const PairGen
         for (int c = 1; c < NC; ++c) mx = fmaxf(mx, lg[c]);
         float den = 0.f;
         for (int c = 0; c < NC; ++c) den += expf(lg[c] - mx);
-        for (int c = 0; c < NC; ++c) a.out[(size_t)r * NC + c] = expf(lg[c] - mx) / den;
+        for (int c = 0; c < NC; ++c) out[(size_t)r * NC + c] = expf(lg[c] - mx) / den;
     }
+}
+__global__ __launch_bounds__(256) void gnn_pair_cls_generic_kernel(const PairGenArgs a) {
+    gnn_pair_cls_generic_body(a, a.Pt, a.Qt, a.rel, a.out, a.N, a.R, (int)blockIdx.x);
 }
 
 

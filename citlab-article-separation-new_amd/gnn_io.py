@@ -230,6 +230,11 @@ class GnnSession:
                 a["enpts"] = np.ascontiguousarray(np.asarray(feed["num_points_visual_regions_edges:0"], dtype=np.int32)[0][:E]).reshape(E)
         return a
 
+    def run_confidences(self, feed_dicts):
+        """the confidence matrices [N_b, N_b] of several pages of a graph without visual features from ONE engine call
+        (asep_gnn_forward_batch); per page ``confidences_from_output(self.run(...))`` bit for bit"""
+        return page_confidences(self, list(feed_dicts))
+
     def run(self, fetches, feed_dict):
         name = _key(fetches)
         if name != OUTPUT_NODE:
@@ -247,6 +252,99 @@ class GnnSession:
         else:
             probs = gnn_forward(self.graph, N, edges, u, ef, rel, self.device)
         return probs[None]
+
+
+def pack_graph_pages(pages, node_dim, edge_dim):
+    """the pages of one asep_gnn_forward_batch call one behind the other: ``pages`` = dicts with N, edges [E, 2] (page-local node numbers),
+    u [N, node_dim], ef [E, edge_dim] or None, rel [R, 2] or None (all N * N ordered pairs) -> (N, E, R int32 arrays, u, edges, ef, rel);
+    rel is None when no page lists relations (a call lists them for all of its pages or for none)"""
+    N = np.array([int(p["N"]) for p in pages], np.int32)
+    edges = [np.ascontiguousarray(p["edges"], dtype=np.int32).reshape(-1, 2) for p in pages]
+    E = np.array([e.shape[0] for e in edges], np.int32)
+    listed = [p.get("rel") is not None for p in pages]
+    if any(listed) and not all(listed):
+        raise ValueError("the pages of one call list their relations all or none")
+    rels = [np.ascontiguousarray(p["rel"], dtype=np.int32).reshape(-1, 2) for p in pages] if all(listed) else None
+    R = np.array([r.shape[0] for r in rels] if rels is not None else [int(n) * int(n) for n in N], np.int32)
+    u = np.concatenate([np.ascontiguousarray(p["u"], dtype=np.float32).reshape(int(p["N"]), node_dim) for p in pages], axis=0)
+    ef = None
+    if edge_dim:
+        ef = np.concatenate([np.ascontiguousarray(p["ef"], dtype=np.float32).reshape(e.shape[0], edge_dim) if e.shape[0]
+                             else np.zeros((0, edge_dim), np.float32) for p, e in zip(pages, edges)], axis=0)
+    return (N, E, R, np.ascontiguousarray(u), np.ascontiguousarray(np.concatenate(edges, axis=0)), ef,
+            np.ascontiguousarray(np.concatenate(rels, axis=0)) if rels is not None else None)
+
+
+def _i32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def gnn_forward_batch(graph: GnnGraph, pages, device=0):
+    """The graph part of several pages in ONE engine call (asep_gnn_forward_batch: every stage one launch over all pages), for a graph
+    without visual features -> per page the class-1 probabilities of its relations [R_b] (R_b = N_b * N_b ordered pairs row major when
+    the pages list no relations): the values of :func:`gnn_forward` ``[:, 1]`` on the page alone, bit for bit.  ``pages``:
+    :func:`pack_graph_pages`."""
+    lib = _lib.init_device(device)
+    cfg = graph.cfg
+    N, E, R, u, edges, ef, rel = pack_graph_pages(pages, cfg.node_feature_dim, cfg.edge_feature_dim)
+    out = np.empty(max(int(R.sum(dtype=np.int64)), 1), dtype=np.float32)
+    rc = lib.asep_gnn_forward_batch(graph.handle(device), len(N), _i32p(N), _i32p(E), _i32p(R), u.ctypes.data,
+                                    edges.ctypes.data if edges.size else None, ef.ctypes.data if ef is not None and ef.size else None,
+                                    rel.ctypes.data if rel is not None and rel.size else None, out.ctypes.data, int(R.sum(dtype=np.int64)))
+    _lib.check(rc, "asep_gnn_forward_batch")
+    ends = np.cumsum(R.astype(np.int64))
+    return [out[int(e - r):int(e)].copy() for e, r in zip(ends, R)]
+
+
+def gnn_forward_batch_dev(graph: GnnGraph, N, E, R, d_node_feat, d_edges, d_edge_feat, d_relations, d_probs_out, max_floats, stream=None,
+                          device=0):
+    """asep_gnn_forward_batch_dev: the same call on device addresses (N, E, R: host int32 arrays), queued on ``stream``"""
+    lib = _lib.init_device(device)
+    N, E, R = (np.ascontiguousarray(a, dtype=np.int32) for a in (N, E, R))
+    rc = lib.asep_gnn_forward_batch_dev(graph.handle(device), len(N), _i32p(N), _i32p(E), _i32p(R), d_node_feat, d_edges, d_edge_feat,
+                                        d_relations, d_probs_out, int(max_floats), stream)
+    _lib.check(rc, "asep_gnn_forward_batch_dev")
+
+
+def graph_batch_serves(cfg) -> bool:
+    """whether --pages_per_call N > 1 groups this graph's pages into asep_gnn_forward_batch calls: no visual features (those pages go
+    through the visual batch call), and two classes (the call returns the class-1 probability, which is then every consumer's score)"""
+    return not cfg.visual_dims and not cfg.visual_edges and cfg.num_classes == 2
+
+
+def page_confidences(sess, feed_dicts):
+    """feed dicts of several pages -> their confidence matrices [N_b, R_b / N_b] (``gnn_results.confidences_from_output`` of ``sess.run``,
+    bit for bit) from ONE batched graph call"""
+    arrays = [sess.page_arrays(f) for f in feed_dicts]
+    for a in arrays:
+        _check_node_indices("interacting_nodes", a["edges"], a["N"])
+        _check_node_indices("relations", a["rel"], a["N"])
+    probs = gnn_forward_batch(sess.graph, arrays, sess.device)
+    return [np.reshape(p, [a["N"], -1]) for p, a in zip(probs, arrays)]
+
+
+def gnn_page_hidden(graph: GnnGraph, page, num_nodes, device=0):
+    """hidden states [N_b, hidden_dim] of page ``page`` of the last batched graph call"""
+    lib = _lib.init_device(device)
+    out = np.empty((int(num_nodes), graph.cfg.hidden_dim), dtype=np.float32)
+    _lib.check(lib.asep_gnn_get_page_hidden(graph.handle(device), int(page), out.ctypes.data, out.size), "asep_gnn_get_page_hidden")
+    return out
+
+
+def gnn_page_edges(graph: GnnGraph, page, num_edges, device=0):
+    """corrected edge list of page ``page`` of the last batched graph call -> (edges [E', 2], first occurrence [E']), as
+    :func:`correct_edges` orders them; ``num_edges``: the page's fed edges"""
+    lib = _lib.init_device(device)
+    cap = max((2 if graph.cfg.undirected_graph else 1) * int(num_edges), 1)
+    out_e, out_f = np.empty((cap, 2), np.int32), np.empty(cap, np.int32)
+    n = lib.asep_gnn_get_page_edges(graph.handle(device), int(page), out_e.ctypes.data, out_f.ctypes.data, cap)
+    _lib.check(n, "asep_gnn_get_page_edges")
+    return out_e[:n].copy(), out_f[:n].copy()
+
+
+def gnn_batch_launches(graph: GnnGraph, device=0) -> int:
+    """kernels the handle's last batched graph call launched (0: it was refused before any launch)"""
+    return int(_lib.init_device(device).asep_gnn_batch_launches(graph.handle(device)))
 
 
 def run_pages(sess: GnnSession, feed_dicts):

@@ -407,7 +407,8 @@ class LavGNN(object):
     def _launch_pages(self, graph, recs, keep):
         """the uploaded pages of one call (``_upload_page``) -> their output buffers, in order.  One page of a visual model goes through
         asep_gnn_forward_visual_batch_dev as ever, several -- of whatever image sizes -- through ONE asep_gnn_forward_visual_batch_dev2
-        call; a model without the visual branch runs page by page (its graph part shares nothing between pages)."""
+        call; a model without the visual branch runs page by page, or with --pages_per_call > 1 through ONE asep_gnn_forward_batch_dev call
+        (``_launch_graph_batch``: every stage of the graph part one launch over the pages)."""
         from . import gnn_io
         stream = _stream(self.device)
         cfg = graph.cfg
@@ -422,6 +423,8 @@ class LavGNN(object):
                 gnn_io.gnn_forward_visual_batch_u8_dev(graph, fed[0], [r["scan"] for r in recs], fed[1], fed[2], recs[0]["P"], stream, self.device)
             else:
                 gnn_io.gnn_forward_visual_batch_dev2(graph, *fed, recs[0]["P"], stream, self.device)
+        elif "a" in recs[0]:                                 # --pages_per_call > 1 without the visual branch (a tail of one page included)
+            return self._launch_graph_batch(graph, recs, keep)
         else:
             lib = _lib.init_device(self.device)
             for r in recs:
@@ -431,10 +434,34 @@ class LavGNN(object):
         keep.extend(r["t"] for r in recs)
         return [r["out"] for r in recs]
 
-    def _upload_page(self, graph, a, scan_to_call=False):
+    def _launch_graph_batch(self, graph, recs, keep):
+        """the pages of a model without the visual branch (``_upload_page`` with ``to_call``: their host arrays) in ONE
+        asep_gnn_forward_batch_dev call: one upload per input, every stage of the graph one launch over all pages -> per page its slice
+        [N * N] of the call's class-1 probabilities in HBM (the score column the accumulator reads)"""
+        import torch
+        from . import gnn_io
+        cfg = graph.cfg
+        arrays = [r["a"] for r in recs]
+        for a in arrays:
+            gnn_io._check_node_indices("interacting_nodes", a["edges"], a["N"])
+        N, E, R, u, edges, ef, _ = gnn_io.pack_graph_pages(arrays, cfg.node_feature_dim, cfg.edge_feature_dim)
+        dev = f"cuda:{self.device}"
+        t = [torch.from_numpy(x).to(dev) if x is not None and x.size else None for x in (u, edges, ef)]
+        ptr = lambda x: x.data_ptr() if x is not None else None                                    # noqa: E731
+        total = int(R.sum(dtype=np.int64))
+        out = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+        gnn_io.gnn_forward_batch_dev(graph, N, E, R, ptr(t[0]), ptr(t[1]), ptr(t[2]), None, out.data_ptr(), total, _stream(self.device),
+                                     self.device)
+        keep.append(t)
+        ends = np.cumsum(R.astype(np.int64))
+        return [out[int(e - r):int(e)] for e, r in zip(ends, R)]
+
+    def _upload_page(self, graph, a, scan_to_call=False, to_call=False):
         """the arrays of one page into HBM (+ the device resize of a scan) -> what ``_launch_pages`` takes.  ``scan_to_call``: a scan is
         left as uploaded, for a call that resizes all its scans in one launch (asep_gnn_forward_visual_batch_u8_dev)"""
         import torch
+        if to_call:                                          # no visual branch, several pages per call: the call uploads them together
+            return {"a": a, "scan": None}
         dev = f"cuda:{self.device}"
         up = lambda x: torch.from_numpy(x).to(dev) if x is not None and x.size else None            # noqa: E731
         ptr = lambda t: t.data_ptr() if t is not None else None                                    # noqa: E731
@@ -580,7 +607,8 @@ class LavGNN(object):
                 batch_counter += 1
                 feed, n, gt_relations = page
                 t0 = time.perf_counter()
-                group.append((self._upload_page(graph, _feed_arrays(feed, graph.cfg), scan_to_call=per_call > 1), n, gt_relations))
+                group.append((self._upload_page(graph, _feed_arrays(feed, graph.cfg), scan_to_call=per_call > 1,
+                                                to_call=per_call > 1 and gnn_io.graph_batch_serves(graph.cfg)), n, gt_relations))
                 feed = page = None                                    # (a scan fed from a decode slot: no view outlives its slot)
                 tm["net_s"] += time.perf_counter() - t0
                 if len(group) >= per_call:

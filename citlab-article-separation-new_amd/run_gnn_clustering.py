@@ -45,7 +45,8 @@ def build_parser():
     # until the device path is no slower on every leg: with host workers it loses on colour scans
     p.add_argument("--device_resize", type=cli_flags.str2bool, default=False)
     # extension: up to N prepared pages, of whatever image sizes, go through the engine in ONE call (gnn_io.run_pages ->
-    # asep_gnn_forward_visual_batch_dev2); 1 = page by page.  The files written are the same bytes for every N
+    # asep_gnn_forward_visual_batch_dev2; a graph without the visual branch: GnnSession.run_confidences -> asep_gnn_forward_batch);
+    # 1 = page by page.  The files written are the same bytes for every N
     p.add_argument("--pages_per_call", type=cli_flags.pages_per_call, default=1)
     p.add_argument("--assign_visual_features_to_nodes", type=cli_flags.str2bool, default=True)
     p.add_argument("--assign_visual_features_to_edges", type=cli_flags.str2bool, default=False)
@@ -121,7 +122,8 @@ def _finish_page(tb, flags, output, n, page_path, device=None):
     -> path of the written file, or None with --save_conf only_conf.  ``device``: the GPU of the calling owner process, where
     --device_edges computes the masks' pair rules; None (a host worker, which owns no GPU) keeps them on the host"""
     from . import gnn_results
-    confidences = gnn_results.confidences_from_output(output, n)
+    # (a page of a batched graph call arrives as its confidence matrix [N, N]: the class-1 column is all that call returns)
+    confidences = output if np.ndim(output) == 2 else gnn_results.confidences_from_output(output, n)
     if flags.mask_heading_separated_confs or flags.mask_horizontally_separated_confs:      # :279-281
         from .feature_generation import mask_horizontally_separated_confs
         confidences = mask_horizontally_separated_confs(confidences, page_path,
@@ -158,6 +160,8 @@ def _run_group(sess, feeds):
     if len(feeds) == 1:
         return [sess.run("output_belong_to_same_instance:0", feed_dict=feeds[0])]
     from . import gnn_io
+    if gnn_io.graph_batch_serves(sess.graph.cfg):            # no visual branch: the graph part of the pages in one set of launches ->
+        return sess.run_confidences(feeds)                   # the confidence matrices themselves (``_finish_page`` takes either)
     return gnn_io.run_pages(sess, feeds)
 
 

@@ -47,7 +47,7 @@ const char* asep_version(void);
  * functions refuse a struct whose size is not the one the library was built with -- a caller written against an older or newer
  * header gets ASEP_ERR_ARG + a message instead of fields read from whatever follows its struct on the stack.
  * An added function moves the version too: a binding resolves every name it declares when it loads the library. */
-#define ASEP_ABI_VERSION 11
+#define ASEP_ABI_VERSION 12
 int asep_abi_version(void);
 /* ABI 6: the environment switches this build of the library reads when a model is loaded (one name per line).
  * Anything else in the environment is not a switch: a caller that records the switches a measurement ran under (bench.py) filters
@@ -329,6 +329,29 @@ int asep_gnn_forward_visual_batch_u8_dev(asep_gnn* g, int n_pages, const asep_gn
 int asep_gnn_get_page_node_features(asep_gnn* g, int page, float* out, size_t max_floats);
 int asep_gnn_get_page_feature_map(asep_gnn* g, int page, int index, float* out, size_t max_floats, int32_t dims[3]);
 int asep_gnn_get_page_image(asep_gnn* g, int page, float* out, size_t max_floats, int32_t dims[3]);
+
+/* ABI 12: the GRAPH part (edge correction, message passing, LSTM update, pair classifier) of n_pages pages in one call, each stage one launch
+ * over all pages, for graphs WITHOUT visual features (a handle with a backbone attached or with visual_edge_dims is refused with a message
+ * that names asep_gnn_forward_visual_batch_dev2).  N / E / R [n_pages] are host arrays; the other inputs hold the pages one behind the other:
+ * node features [sum N, node_feature_dim], edges [sum E, 2] with PAGE-LOCAL node numbers, edge features [sum E, edge_feature_dim],
+ * relations [sum R, 2] page-local (NULL: R_b <= N_b^2 ordered pairs of page b row major).  probs_out receives the class-1 probability of
+ * every relation, sum R floats in page order (max_floats: what the buffer holds); per page the values are those of asep_gnn_forward[_dev] on
+ * the page alone bit for bit, whatever else shares the call.  Refused before anything is uploaded or launched, with "... in page %d" where a
+ * page is at fault: NULL arrays, N_b < 1, E_b / R_b < 0, N_b^2 > 2^30 and a sum of N_b^2 over the call > 2^30 (ASEP_ERR_UNSUPPORTED: split
+ * the call), a too-small output buffer, and in the host entry an edge or relation that names a node outside 0..N_b-1 (the device entry does
+ * with those what asep_gnn_forward_dev does: the edge is ignored, the relation is NaN).  The calls of a handle go to one stream, or the
+ * caller orders them.  Afterwards asep_gnn_get_hidden returns the hidden states of all pages [sum N, hidden_dim] in page order,
+ * asep_gnn_get_page_hidden those of one page, asep_gnn_get_page_edges one page's corrected edge list as asep_gnn_correct_edges returns it
+ * (out_first, optional: the index into the page's symmetrised list of every edge's first occurrence; returns the count), until the
+ * handle's next forward.  asep_gnn_batch_launches: the kernels the handle's last batched call launched (0: it was refused). */
+int asep_gnn_forward_batch(asep_gnn* g, int n_pages, const int32_t* N, const int32_t* E, const int32_t* R, const float* node_feat,
+                           const int32_t* edges, const float* edge_feat, const int32_t* relations, float* probs_out, size_t max_floats);
+int asep_gnn_forward_batch_dev(asep_gnn* g, int n_pages, const int32_t* N, const int32_t* E, const int32_t* R, const float* d_node_feat,
+                               const int32_t* d_edges, const float* d_edge_feat, const int32_t* d_relations, float* d_probs_out,
+                               size_t max_floats, void* stream);
+int asep_gnn_get_page_hidden(asep_gnn* g, int page, float* out, size_t max_floats);
+int asep_gnn_get_page_edges(asep_gnn* g, int page, int32_t* out_edges, int32_t* out_first, int max_edges);
+long asep_gnn_batch_launches(const asep_gnn* g);
 
 /* Which message-passing kernel the handle uses: 0 = generic FMA kernels (any widths), 1 = fused MFMA step with the
  * edge-MLP filter in registers (widths 32, node_feature_dim <= 8), 2 = fused MFMA step with the filter in LDS (widths 32,

@@ -1,0 +1,285 @@
+"""asep_gnn_forward_batch: the graph part of the relation net (edge correction, message passing, LSTM update, pair classifier) for the pages of one
+call, each stage one launch over all pages.  Per page the results are those of asep_gnn_forward on the page alone BIT FOR BIT, whatever else
+shares the call and in whatever order: compared on the float32 bit patterns, no tolerance.  Refusals come from the host checks, before a launch."""
+import json
+import logging
+import os
+import re
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+SIZES = [1, 2, 3, 7, 64, 65, 130]         # one node, the two-node case, fewer edges than a wave, both sides of a 64 boundary, > 2 x 64
+
+
+def _setup(seed=99, **cfg_kw):
+    from citlab_article_separation_new_amd.config import GnnConfig
+    from citlab_article_separation_new_amd.weights import init_gnn_weights
+    from citlab_article_separation_new_amd.gnn_io import GnnGraph
+    cfg = GnnConfig(**cfg_kw)
+    w = init_gnn_weights(cfg, seed, bias_jitter=0.05)
+    return cfg, w, GnnGraph(w, cfg)
+
+
+def _page(rng, N, E, cfg):
+    edges = rng.integers(0, N, size=(E, 2)).astype(np.int32)       # duplicates, reversed duplicates and self loops among them
+    if E > 4:
+        edges[1] = edges[0]
+        edges[2] = edges[0][::-1]
+        edges[3] = [min(3, N - 1), min(3, N - 1)]
+    return dict(N=N, edges=edges, u=rng.random((N, cfg.node_feature_dim), dtype=np.float32),
+                ef=rng.random((E, cfg.edge_feature_dim), dtype=np.float32) if cfg.edge_feature_dim else None, rel=None)
+
+
+def _single(graph, p):
+    from citlab_article_separation_new_amd import gnn_io
+    probs = gnn_io.gnn_forward(graph, p["N"], p["edges"], p["u"], p["ef"] if len(p["edges"]) else None, p["rel"])
+    return probs[:, 1].copy(), gnn_io.gnn_hidden(graph, p["N"])
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+@pytest.mark.parametrize("kw", [
+    dict(),
+    dict(aggregation_type="max"),
+    dict(use_attention=True, num_attention_heads=2, multihead_attention_merge_type="concat"),
+    dict(output_type="concat_final_hidden_and_input"),
+], ids=["default", "max", "attention2_concat", "output_concat"])
+def test_batch_equals_single_bit_for_bit_in_two_orders(kw):
+    from citlab_article_separation_new_amd import gnn_io
+    cfg, w, graph = _setup(seed=17, **kw)
+    rng = np.random.default_rng(11)
+    pages = [_page(rng, N, {1: 0, 2: 1, 3: 5, 7: 12}.get(N, 5 * N), cfg) for N in SIZES]
+    want = [_single(graph, p) for p in pages]
+    orders = [list(range(len(pages))), [6, 0, 4, 2, 5, 1, 3]]
+    for order in orders:
+        got = gnn_io.gnn_forward_batch(graph, [pages[k] for k in order])
+        assert gnn_io.gnn_batch_launches(graph) > 0
+        h_all = gnn_io.gnn_hidden(graph, sum(SIZES))                       # asep_gnn_get_hidden: all pages, in the call's order
+        off = 0
+        for slot, k in enumerate(order):
+            N = pages[k]["N"]
+            assert got[slot].shape == (N * N,)
+            assert np.array_equal(_bits(got[slot]), _bits(want[k][0])), (kw, order, k)
+            assert np.array_equal(_bits(gnn_io.gnn_page_hidden(graph, slot, N)), _bits(want[k][1])), (kw, order, k)
+            assert np.array_equal(_bits(h_all[off:off + N]), _bits(want[k][1]))
+            off += N
+    graph.close()
+
+
+def test_listed_relations_and_a_single_page_call():
+    """relations listed per page (page-local node numbers), a page without any, and a call of one page"""
+    from citlab_article_separation_new_amd import gnn_io
+    cfg, w, graph = _setup()
+    rng = np.random.default_rng(3)
+    pages = [_page(rng, N, 4 * N, cfg) for N in (9, 70, 5)]
+    for p, R in zip(pages, (20, 300, 0)):
+        p["rel"] = rng.integers(0, p["N"], size=(R, 2)).astype(np.int32)
+    want = [_single(graph, p)[0] if p["rel"].shape[0] else np.zeros(0, np.float32) for p in pages]
+    got = gnn_io.gnn_forward_batch(graph, pages)
+    for g, wnt in zip(got, want):
+        assert np.array_equal(_bits(g), _bits(wnt))
+    one = gnn_io.gnn_forward_batch(graph, pages[1:2])
+    assert np.array_equal(_bits(one[0]), _bits(want[1]))
+    graph.close()
+
+
+def test_edge_correction_per_page():
+    """a page without edges, a page with duplicates, self loops and both directions of one edge, a fully connected page: the results and the
+    corrected edge lists of the page alone"""
+    from citlab_article_separation_new_amd import gnn_io
+    cfg, w, graph = _setup()
+    rng = np.random.default_rng(8)
+    empty = _page(rng, 6, 0, cfg)
+    messy = _page(rng, 9, 0, cfg)
+    messy["edges"] = np.array([[0, 1], [1, 0], [0, 1], [4, 4], [2, 7], [2, 7], [7, 2], [8, 8], [3, 5], [0, 1]], np.int32)
+    messy["ef"] = rng.random((10, cfg.edge_feature_dim), dtype=np.float32)
+    full = _page(rng, 12, 0, cfg)
+    full["edges"] = np.array([[i, j] for i in range(12) for j in range(12) if i != j], np.int32)
+    full["ef"] = rng.random((132, cfg.edge_feature_dim), dtype=np.float32)
+    pages = [empty, messy, full]
+    want = [_single(graph, p) for p in pages]
+    want_edges = [gnn_io.correct_edges(graph, p["N"], p["edges"], p["ef"] if len(p["edges"]) else None) for p in pages]
+    assert [len(e) for e, _ in want_edges] == [0, 6, 132]
+    got = gnn_io.gnn_forward_batch(graph, pages)
+    for k, p in enumerate(pages):
+        assert np.array_equal(_bits(got[k]), _bits(want[k][0])), k
+        edges, first = gnn_io.gnn_page_edges(graph, k, p["edges"].shape[0])
+        assert np.array_equal(edges, want_edges[k][0]), k
+        if len(edges):                                                     # the features of the first occurrences, as correct_edges gathers them
+            assert np.array_equal(p["ef"][first % p["edges"].shape[0]], want_edges[k][1]), k
+    graph.close()
+
+
+def test_parity_with_the_oracle():
+    """the bound of tests/test_gnn_gpu.py::test_probabilities_match_oracle (PROB_TOL = 1e-5 against the float64 oracle)"""
+    from citlab_article_separation_new_amd import gnn_io
+    from oracle import gnn_oracle
+    PROB_TOL = 1e-5
+    cfg, w, graph = _setup()
+    rng = np.random.default_rng(21)
+    pages = [_page(rng, N, E, cfg) for N, E in ((12, 30), (77, 150), (50, 400))]
+    got = gnn_io.gnn_forward_batch(graph, pages)
+    for k, p in enumerate(pages):
+        want, want_h = gnn_oracle.forward(p["N"], p["edges"], p["u"], p["ef"], None, w, cfg, dtype=np.float64, return_hidden=True)
+        err, err_h = float(np.abs(got[k] - want[:, 1]).max()), float(np.abs(gnn_io.gnn_page_hidden(graph, k, p["N"]) - want_h).max())
+        print(f"page {k}: N={p['N']} max|p - oracle| = {err:.3e}, max|h - oracle| = {err_h:.3e}")
+        assert err <= PROB_TOL and err_h <= PROB_TOL
+    graph.close()
+
+
+def test_refusals_launch_nothing_and_leave_the_handle_usable():
+    from citlab_article_separation_new_amd import _lib, gnn_io
+    cfg, w, graph = _setup()
+    rng = np.random.default_rng(2)
+    pages = [_page(rng, N, 3 * N, cfg) for N in (5, 8, 6)]
+    want = [_single(graph, p)[0] for p in pages]
+    lib = _lib.init_device(0)
+
+    def refused(match, call):
+        with pytest.raises(_lib.AsepError, match=match):
+            call()
+        assert gnn_io.gnn_batch_launches(graph) == 0                       # the engine's launch record of the call
+        got = gnn_io.gnn_forward_batch(graph, pages)                       # a following good call
+        assert gnn_io.gnn_batch_launches(graph) > 0
+        assert all(np.array_equal(_bits(g), _bits(wnt)) for g, wnt in zip(got, want))
+
+    # an edge index equal to N_b
+    bad = [dict(p) for p in pages]
+    bad[1]["edges"] = pages[1]["edges"].copy()
+    bad[1]["edges"][7, 1] = 8
+    refused(r"interacting_nodes\[7\] = \(\d+, 8\) names a node outside 0\.\.7 in page 1", lambda: gnn_io.gnn_forward_batch(graph, bad))
+    # N_b = 0
+    N, E, R, u, edges, ef, _ = gnn_io.pack_graph_pages(pages, cfg.node_feature_dim, cfg.edge_feature_dim)
+    out = np.empty(int(R.sum()), np.float32)
+    i32p = gnn_io._i32p
+
+    def raw(N=N, E=E, R=R, max_floats=out.size):
+        rc = lib.asep_gnn_forward_batch(graph.handle(0), len(N), i32p(N), i32p(E), i32p(R), u.ctypes.data, edges.ctypes.data, ef.ctypes.data, None,
+                                        out.ctypes.data, max_floats)
+        _lib.check(rc, "asep_gnn_forward_batch")
+    N0 = N.copy()
+    N0[2] = 0
+    refused(r"N < 1 in page 2", lambda: raw(N=N0))
+    # an output buffer one float short
+    refused(r"output buffer holds %d floats" % (out.size - 1), lambda: raw(max_floats=out.size - 1))
+    # a NULL size array
+    with pytest.raises(_lib.AsepError, match="size array E is NULL"):
+        _lib.check(lib.asep_gnn_forward_batch(graph.handle(0), len(N), i32p(N), None, i32p(R), u.ctypes.data, edges.ctypes.data, ef.ctypes.data,
+                                              None, out.ctypes.data, out.size), "asep_gnn_forward_batch")
+    assert gnn_io.gnn_batch_launches(graph) == 0
+    graph.close()
+
+
+def test_a_graph_with_visual_dims_is_refused():
+    from citlab_article_separation_new_amd import _lib, gnn_io, synth
+    from citlab_article_separation_new_amd.config import GnnConfig
+    from citlab_article_separation_new_amd.weights import init_gnn_weights
+    cfg = GnnConfig(node_feature_dim=7, visual_dims=[16, 16, 16], visual_layers=synth.GNN_VISUAL_LAYERS)
+    graph = gnn_io.GnnGraph(init_gnn_weights(cfg, 3, bias_jitter=0.05), cfg)
+    lib = _lib.init_device(0)
+    N, E, R = (np.array([4], np.int32) for _ in range(3))
+    u, edges, ef = np.zeros((4, 7), np.float32), np.zeros((4, 2), np.int32), np.zeros((4, cfg.edge_feature_dim), np.float32)
+    out = np.full(4, -1, np.float32)
+    rc = lib.asep_gnn_forward_batch(graph.handle(0), 1, gnn_io._i32p(N), gnn_io._i32p(E), gnn_io._i32p(R), u.ctypes.data, edges.ctypes.data,
+                                    ef.ctypes.data, None, out.ctypes.data, out.size)
+    assert rc < 0 and "asep_gnn_forward_visual_batch_dev2" in _lib.last_error()
+    assert gnn_io.gnn_batch_launches(graph) == 0 and (out == -1).all()
+    graph.close()
+
+
+# ---- the command lines: --pages_per_call 3 writes the bytes of --pages_per_call 1 ------------------------------------------------------------
+
+N_CLI = 14
+_NOT_RESULTS = ("Time:", "Using pb_path", "Saved", "No json")
+
+
+def _inputs(root, n_pages=5):
+    """synth.write_gnn_cli_inputs for the geometric net (no visual branch), with planted ground truth relations for lav_rel"""
+    from citlab_article_separation_new_amd import synth
+    argv = synth.write_gnn_cli_inputs(str(root), n_pages, visual=False, N=N_CLI)
+    rng = np.random.default_rng(4)
+    for k in range(n_pages):
+        jp = root / "data" / "json15d2bb" / f"p{k:03d}.json"
+        d = json.loads(jp.read_text())
+        if jp.is_symlink():
+            jp.unlink()
+        member = rng.integers(-1, 3, size=N_CLI)
+        gt = [[0, int(i), int(j)] for i in range(N_CLI) for j in range(N_CLI) if member[i] >= 0 and member[i] == member[j]]
+        d["gt_relations"], d["gt_num_relations"] = gt, len(gt)
+        jp.write_text(json.dumps(d))
+    return argv + ["--gpu_devices", "0"]
+
+
+def _files(root, out_dir):
+    found = {}
+    for top in (root / out_dir, root / "data" / "confidences"):
+        for dirpath, _, names in os.walk(top):
+            for n in names:
+                p = os.path.join(dirpath, n)
+                with open(p, "rb") as f:
+                    raw = f.read()
+                if n.endswith(".xml"):                                     # the only clock-dependent bytes of a PAGE-XML
+                    raw = re.sub(rb"(<(?:\w+:)?LastChange>)[^<]*(</)", rb"\1\2", raw)
+                found[os.path.relpath(p, top)] = raw
+    return found
+
+
+def test_run_gnn_clustering_three_pages_per_call_writes_the_bytes_of_page_by_page(tmp_path):
+    from citlab_article_separation_new_amd import run_gnn_clustering
+    argv = _inputs(tmp_path) + ["--save_conf", "with_conf"]
+    cwd = os.getcwd()
+    os.chdir(tmp_path)
+    got = {}
+    try:
+        for n in ("1", "3"):
+            conf = tmp_path / "data" / "confidences"
+            for f in conf.glob("*.json") if conf.is_dir() else ():
+                f.unlink()
+            outs = run_gnn_clustering.main(argv + ["--out_dir", "out_" + n, "--pages_per_call", n])
+            assert len(outs) == 5
+            got[n] = _files(tmp_path, "out_" + n)
+    finally:
+        os.chdir(cwd)
+    assert sorted(got["1"]) == sorted(got["3"])
+    assert sum(k.endswith("_clustering.xml") for k in got["3"]) == 5 and sum(k.endswith("_confidences.json") for k in got["3"]) == 5
+    for k in got["1"]:
+        assert got["1"][k] == got["3"][k], k
+
+
+class _Capture(logging.Handler):
+    def __init__(self):
+        super().__init__()
+        self.lines = []
+
+    def emit(self, record):
+        self.lines.append(record.getMessage())
+
+
+def _evaluate(argv):
+    from citlab_article_separation_new_amd import lav_rel
+    cap = _Capture()
+    root = logging.getLogger()
+    level = root.level
+    root.addHandler(cap)
+    root.setLevel(logging.INFO)
+    try:
+        curve = lav_rel.LavGNN(argv=argv).evaluate()
+    finally:
+        root.removeHandler(cap)
+        root.setLevel(level)
+    return curve, [ln for ln in cap.lines if not ln.startswith(_NOT_RESULTS)]
+
+
+def test_lav_rel_three_pages_per_call_gives_the_tables_of_page_by_page(tmp_path):
+    argv = _inputs(tmp_path)
+    (one, one_lines), (three, three_lines) = (_evaluate(argv + ["--pages_per_call", n]) for n in ("1", "3"))
+    assert one.n == 5 * N_CLI * N_CLI and three.n == one.n and three.n_correct == one.n_correct and three.a2 == one.a2
+    assert np.array_equal(three.thresholds.view(np.uint32), one.thresholds.view(np.uint32))
+    assert np.array_equal(three.tps, one.tps) and np.array_equal(three.fps, one.fps)
+    assert three.auc_roc == one.auc_roc and np.isfinite(one.auc_roc)
+    assert three_lines == one_lines and "Evaluation finished." in three_lines
