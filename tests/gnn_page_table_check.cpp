@@ -84,6 +84,29 @@ int main(int argc, char** argv) {
             CHECK(t.node_begin[(size_t)n] == nodes);
         }
     }
+    // ---- pinned numbers: the first page size of two interaction chunks, and the sizes at which the fill and the per-node launches are capped ----
+    {
+        const std::vector<int32_t> N = {316, 317, 400, 800, 4200, 4096, 4097}, E = {0, 900, 2500, 300000, 8000, 262144, 262145},
+                                   R = {0, 0, 0, 200, 500, 0, 0};
+        const int chunk_nodes[] = {316, 315, 250, 125, 23, 24, 24}, chunks[] = {1, 2, 2, 7, 183, 171, 171};
+        const int pre[] = {79, 80, 100, 200, 1024, 1024, 1024};                 // N * 64 / 256 blocks up to N = 4096, 1024 beyond
+        const int fill_und[] = {0, 8, 20, 2048, 63, 2048, 2048}, fill_dir[] = {0, 4, 10, 1172, 32, 1024, 1025};
+        for (int und = 0; und < 2; ++und) {
+            GnnPageTable t;
+            int bad = -2;
+            CHECK(gnn_page_table(N.data(), E.data(), R.data(), (int)N.size(), und != 0, 64, t, &bad) == GNN_TABLE_OK && bad == -1);
+            GnnUnitTables u;
+            CHECK(gnn_unit_tables(t, und != 0, 64, 256, u));
+            for (size_t b = 0; b < N.size(); ++b) {
+                CHECK(t.rows[b].chunk_nodes == chunk_nodes[b] && u.chunk[b + 1] - u.chunk[b] == chunks[b]);
+                CHECK(u.pre[b + 1] - u.pre[b] == pre[b]);
+                CHECK(u.fill[b + 1] - u.fill[b] == (und ? fill_und[b] : fill_dir[b]));
+            }
+            // what a capped page's blocks stride over: 600 000 fed entries in 2048 x 256, 4200 x 64 first-layer terms in 1024 x 256
+            CHECK(!und || 2ll * E[3] > 2048ll * 256);
+            CHECK((long long)N[4] * 64 > 1024ll * 256);
+        }
+    }
     // ---- refusals: the page at fault is named, nothing past the arrays is read ----
     {
         GnnPageTable t;

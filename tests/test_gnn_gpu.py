@@ -29,11 +29,15 @@ def _random_graph(rng, N, E, node_dim=7, edge_dim=2, dup=True):
     return edges, u, ef
 
 
-@pytest.mark.parametrize("N,E", [(4, 5), (12, 30), (50, 400), (200, 10000), (333, 2000), (3, 0)])
+FILL_GRID_CAP, PRE_GRID_CAP = 2048, 1024       # blocks of 256 threads: edge_table_kernel / gnn_pair_pre_kernel stride over what lies beyond
+
+
+@pytest.mark.parametrize("N,E", [(4, 5), (12, 30), (50, 400), (200, 10000), (333, 2000), (3, 0), (800, 300000)])
 def test_edge_correction_bit_exact(N, E):
     from citlab_article_separation_new_amd import gnn_io
     from oracle import gnn_oracle
     cfg, w, graph = _setup()
+    assert (2 * E > FILL_GRID_CAP * 256) == (E == 300000)          # the last case alone has fed entries beyond the fill launch's grid
     rng = np.random.default_rng(N * 7 + E)
     edges, u, ef = _random_graph(rng, N, E)
     want_e, want_f = gnn_oracle.correct_edges(edges, ef, N, True)
@@ -69,6 +73,28 @@ def test_probabilities_match_oracle(N, E):
     assert got.shape == (N * N, 2)
     assert float(np.abs(got_h - want_h).max()) <= PROB_TOL
     assert float(np.abs(got - want).max()) <= PROB_TOL
+    graph.close()
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(use_attention=True, num_attention_heads=2)], ids=["default", "attention2"])
+def test_probabilities_match_oracle_beyond_the_per_node_grid(kw):
+    """N = 4200: the classifier's per-node first layer (gnn_pair_pre_kernel) has N x 64 > 1024 x 256 terms and strides over its capped grid; with
+    attention the page has 183 interaction chunks of 23 target nodes.  500 listed relations keep the pair part small."""
+    from citlab_article_separation_new_amd import gnn_io
+    from oracle import gnn_oracle
+    cfg, w, graph = _setup(**kw)
+    N, E = 4200, 8000
+    assert N * cfg.classifier_hidden[0] > PRE_GRID_CAP * 256
+    assert 100000 // N == 23 and -(-N // 23) == 183
+    rng = np.random.default_rng(N + E)
+    edges, u, ef = _random_graph(rng, N, E)
+    rel = rng.integers(0, N, size=(500, 2)).astype(np.int32)
+    want, want_h = gnn_oracle.forward(N, edges, u, ef, rel, w, cfg, dtype=np.float64, return_hidden=True)
+    got = gnn_io.gnn_forward(graph, N, edges, u, ef, rel)
+    got_h = gnn_io.gnn_hidden(graph, N)
+    err, err_h = float(np.abs(got - want).max()), float(np.abs(got_h - want_h).max())
+    print(f"{kw}: max|p - oracle| = {err:.3e}, max|h - oracle| = {err_h:.3e}")
+    assert got.shape == (500, 2) and err_h <= PROB_TOL and err <= PROB_TOL
     graph.close()
 
 
