@@ -305,20 +305,25 @@ struct EdgeBufs {
     int32_t* sorted; int* sfirst; int* tsrc; int* tfirst;
 };
 
-// misc.py:7-151 on the device; fills the CSR-by-target used by the message kernel
-int correct_edges_dev(asep_gnn* g, BufferPool& pool, int N, int E, const int32_t* d_edges, EdgeBufs& eb, hipStream_t s) {
-    const int und = g->cfg.undirected_graph ? 1 : 0;
-    const size_t maxE = (size_t)(und ? 2 : 1) * std::max(E, 1);
-    eb.table = (int*)pool.get((size_t)N * N * sizeof(int));
-    eb.rowcnt = (int*)pool.get((size_t)N * sizeof(int));
-    eb.colcnt = (int*)pool.get((size_t)N * sizeof(int));
-    eb.rowptr = (int*)pool.get((size_t)(N + 1) * sizeof(int));
-    eb.colptr = (int*)pool.get((size_t)(N + 1) * sizeof(int));
+// the buffers of an edge correction over `nodes` nodes: dense tables of `cells` cells in all (queued here: every cell "no edge"), lists of maxE
+int edge_bufs(BufferPool& pool, size_t cells, size_t nodes, size_t maxE, EdgeBufs& eb, hipStream_t s) {
+    eb.table = (int*)pool.get(cells * sizeof(int));
+    eb.rowcnt = (int*)pool.get(nodes * sizeof(int));
+    eb.colcnt = (int*)pool.get(nodes * sizeof(int));
+    eb.rowptr = (int*)pool.get((nodes + 1) * sizeof(int));
+    eb.colptr = (int*)pool.get((nodes + 1) * sizeof(int));
     eb.sorted = (int32_t*)pool.get(maxE * 2 * sizeof(int32_t));
     eb.sfirst = (int*)pool.get(maxE * sizeof(int));
     eb.tsrc = (int*)pool.get(maxE * sizeof(int));
     eb.tfirst = (int*)pool.get(maxE * sizeof(int));
-    ASEP_HIP_CHECK(hipMemsetAsync(eb.table, 0x7f, (size_t)N * N * sizeof(int), s));
+    ASEP_HIP_CHECK(hipMemsetAsync(eb.table, 0x7f, cells * sizeof(int), s));
+    return ASEP_OK;
+}
+
+// misc.py:7-151 on the device; fills the CSR-by-target used by the message kernel
+int correct_edges_dev(asep_gnn* g, BufferPool& pool, int N, int E, const int32_t* d_edges, EdgeBufs& eb, hipStream_t s) {
+    const int und = g->cfg.undirected_graph ? 1 : 0;
+    if (int rc = edge_bufs(pool, (size_t)N * N, (size_t)N, (size_t)(und ? 2 : 1) * std::max(E, 1), eb, s)) return rc;
     if (E > 0) {
         const int total = und ? 2 * E : E;
         hipLaunchKernelGGL(edge_table_kernel, dim3(std::min(cdiv(total, 256), 2048)), dim3(256), 0, s, d_edges, E, N, und,
@@ -339,64 +344,62 @@ inline int step_mode_of(const asep_gnn* g) {
     return g->use_fact && g->A1f ? STEP_FACT : g->mode;
 }
 
-int forward_impl(asep_gnn* g, BufferPool& pool, int N, int E, const int32_t* d_edges, const float* d_u, const float* d_ef, int R,
-                 const int32_t* d_rel, float* d_out, hipStream_t s) {
+// a launch that its caller counts (asep_gnn_batch_launches)
+#define COUNTED_LAUNCH(count, ...) do { hipLaunchKernelGGL(__VA_ARGS__); ++(count); } while (0)
+
+struct GraphOut { const float* hcls = nullptr; int Hc = 0; long launches = 0; };   // what the pair classifier reads, its width; kernels launched
+
+// The ONE step schedule of the relation net, from the compress_node_feature_dim layer to the output_type layer: T x (message, aggregation /
+// attention soft-max, LSTM update) over the N nodes of a launch -- a page (forward_impl) or all pages of a call (forward_batch_impl; one
+// CSR-by-target over them: no kernel in here knows of pages).  Erows = rows of the fed edge features (`tfirst % Erows` is the row), maxE = the
+// capacity of the corrected lists.  The one page-dependent launch of the span, the attention pairing's chunk rank, is the caller's:
+// chunk_rank(widx, launches) queues it.  Sets g->d_h.  Buffers come from `pool` in an order that depends on the handle alone.
+template <class ChunkRank>
+int graph_steps(asep_gnn* g, BufferPool& pool, int N, int Erows, size_t maxE, const EdgeBufs& eb, const float* d_u, const float* d_ef,
+                hipStream_t s, ChunkRank chunk_rank, GraphOut& out) {
     const asep_gnn_cfg& c = g->cfg;
-    if (N < 1 || E < 0 || R < 0) { set_error("asep_gnn_forward: bad sizes N=%d E=%d R=%d", N, E, R); return ASEP_ERR_ARG; }
-    if ((size_t)N * N > (size_t)1 << 30) { set_error("asep_gnn_forward: N=%d too large for the dense edge table", N); return ASEP_ERR_UNSUPPORTED; }
-    g->stream = s;
-    g->N = N;
-    ++g->fwd_serial;
-    pool.begin();
-    EdgeBufs eb{};
-    int rc = correct_edges_dev(g, pool, N, E, d_edges, eb, s);
-    if (rc) return rc;
+    long& nl = out.launches;
     const int H = g->H, I = g->I;
     const size_t nh = (size_t)N * H;
     float* h[2] = {(float*)pool.get(nh * 4), (float*)pool.get(nh * 4)};
     float* cs[2] = {(float*)pool.get(nh * 4), (float*)pool.get(nh * 4)};
     float* x = (float*)pool.get((size_t)N * std::max(I, g->Iout) * 4);
-    float* Pt = (float*)pool.get((size_t)N * c.cls_hidden1 * 4);
-    float* Qt = (float*)pool.get((size_t)N * c.cls_hidden1 * 4);
     const float* d_fed = d_u;                                // node features as fed (output_type add / concat read these)
     if (g->Wc) {                                             // compress_node_feature_dim: the fed features -> tanh(Wc x + bc)
         float* uc = (float*)pool.get((size_t)N * g->U * 4);
-        hipLaunchKernelGGL(gnn_compress_kernel, dim3(cdiv(N * g->U, 256)), dim3(256), 0, s, d_u, N, g->Uin, g->Wc, g->bc, g->U, uc);
+        COUNTED_LAUNCH(nl, gnn_compress_kernel, dim3(cdiv(N * g->U, 256)), dim3(256), 0, s, d_u, N, g->Uin, g->Wc, g->bc, g->U, uc);
         d_u = uc;
     }
     // attention-weighted aggregation: edge index of every csr entry + per-edge interaction features / attention values
     int* att_eidx = nullptr;
     int* att_widx = nullptr;
     float *att_M = nullptr, *att_A = nullptr, *att_S = nullptr;
-    const size_t att_maxE = (size_t)(c.undirected_graph ? 2 : 1) * std::max(E, 1);
     if (c.attention_heads > 0) {
-        att_eidx = (int*)pool.get(att_maxE * sizeof(int));
-        att_M = (float*)pool.get(att_maxE * c.attention_heads * g->att_xd * sizeof(float));
-        att_A = (float*)pool.get(att_maxE * c.attention_heads * sizeof(float));
-        att_S = (float*)pool.get(att_maxE * c.attention_heads * sizeof(float));
-        att_widx = (int*)pool.get(att_maxE * sizeof(int));
-        hipLaunchKernelGGL(edge_rank_kernel, dim3(N), dim3(64), 0, s, eb.colptr, eb.tsrc, eb.rowptr, eb.sorted, N, att_eidx);
-        const int chunk_nodes = std::max(1, 100000 / N);      // message_fn_chunk.py:77-78
-        hipLaunchKernelGGL(edge_chunk_rank_kernel, dim3(cdiv(N, chunk_nodes)), dim3(256), 0, s, eb.sorted, eb.rowptr, eb.colptr, N, chunk_nodes,
-                           att_widx);
+        att_eidx = (int*)pool.get(maxE * sizeof(int));
+        att_M = (float*)pool.get(maxE * c.attention_heads * g->att_xd * sizeof(float));
+        att_A = (float*)pool.get(maxE * c.attention_heads * sizeof(float));
+        att_S = (float*)pool.get(maxE * c.attention_heads * sizeof(float));
+        att_widx = (int*)pool.get(maxE * sizeof(int));
+        COUNTED_LAUNCH(nl, edge_rank_kernel, dim3(N), dim3(64), 0, s, eb.colptr, eb.tsrc, eb.rowptr, eb.sorted, N, att_eidx);
+        chunk_rank(att_widx, nl);
     }
     float* upad = nullptr;
     const int mode = step_mode_of(g);
     if (mode == STEP_BIG) {
         upad = (float*)pool.get((size_t)N * g->Upad * 4);
-        hipLaunchKernelGGL(gnn_pad_rows_kernel, dim3(cdiv(N * g->Upad, 256)), dim3(256), 0, s, d_u, N, g->U, upad, g->Upad);
+        COUNTED_LAUNCH(nl, gnn_pad_rows_kernel, dim3(cdiv(N * g->Upad, 256)), dim3(256), 0, s, d_u, N, g->U, upad, g->Upad);
     }
     float *fPu = nullptr, *fP[2] = {nullptr, nullptr}, *fC = nullptr;
-    if (mode == STEP_FACT && c.num_transition_steps > 0) {     // the step-independent parts of the edge MLP's first layer, once per page
+    if (mode == STEP_FACT && c.num_transition_steps > 0) {     // the step-independent parts of the edge MLP's first layer, once per launch
         fPu = (float*)pool.get((size_t)N * 64 * 4);
         fP[0] = (float*)pool.get((size_t)N * 64 * 4);
         fP[1] = (float*)pool.get((size_t)N * 64 * 4);
-        fC = (float*)pool.get(att_maxE * 32 * 4);
+        fC = (float*)pool.get(maxE * 32 * 4);
         FactPreArgs fa{};
         fa.u = d_u; fa.ef = d_ef; fa.tptr = eb.colptr; fa.tsrc = eb.tsrc; fa.tfirst = eb.tfirst;
         fa.Wuu = g->Wuu; fa.Wde = g->Wde; fa.b1 = g->b1; fa.Pu = fPu; fa.C = fC;
-        fa.N = N; fa.U = g->U; fa.Ed = g->Ed; fa.E = std::max(E, 1);
-        hipLaunchKernelGGL(gnn_fact_pre_kernel, dim3(N), dim3(256), g->fact_pre_lds, s, fa);
+        fa.N = N; fa.U = g->U; fa.Ed = g->Ed; fa.E = Erows;
+        COUNTED_LAUNCH(nl, gnn_fact_pre_kernel, dim3(N), dim3(256), g->fact_pre_lds, s, fa);
     }
     if (mode != STEP_FACT || c.num_transition_steps == 0) {  // (the factored step's first launch does not read h / c: no memsets)
         ASEP_HIP_CHECK(hipMemsetAsync(h[0], 0, nh * 4, s));
@@ -414,7 +417,7 @@ int forward_impl(asep_gnn* g, BufferPool& pool, int N, int E, const int32_t* d_e
             sa.h_out = h[cur ^ 1]; sa.c_out = cs[cur ^ 1];
             sa.P_out = t + 1 < c.num_transition_steps ? fP[(t + 1) & 1] : nullptr;
             sa.N = N; sa.U = g->U; sa.first = t == 0;
-            hipLaunchKernelGGL(gnn_step_fact_kernel, dim3(N), dim3(256), g->fact_lds, s, sa);
+            COUNTED_LAUNCH(nl, gnn_step_fact_kernel, dim3(N), dim3(256), g->fact_lds, s, sa);
         } else if (mode == STEP_SMALL) {
             StepArgs sa{};
             sa.u = d_u; sa.h_in = h[cur]; sa.c_in = cs[cur]; sa.ef = d_ef;
@@ -422,9 +425,9 @@ int forward_impl(asep_gnn* g, BufferPool& pool, int N, int E, const int32_t* d_e
             sa.A1 = (const gf32x4*)g->A1; sa.A2 = (const gf32x4*)g->A2; sa.b1 = g->b1; sa.b2 = g->b2;
             for (int q = 0; q < 4; ++q) { sa.Wg[q] = g->Wg[q]; sa.bg[q] = g->bg[q]; }
             sa.h_out = h[cur ^ 1]; sa.c_out = cs[cur ^ 1];
-            sa.N = N; sa.U = g->U; sa.Ed = g->Ed; sa.E = std::max(E, 1); sa.nch = g->nch;
+            sa.N = N; sa.U = g->U; sa.Ed = g->Ed; sa.E = Erows; sa.nch = g->nch;
             sa.qdesc = g->qdesc;
-            hipLaunchKernelGGL(gnn_step_kernel, dim3(N), dim3(256), 0, s, sa);
+            COUNTED_LAUNCH(nl, gnn_step_kernel, dim3(N), dim3(256), 0, s, sa);
         } else if (mode == STEP_BIG) {
             StepBigArgs sa{};
             sa.u = upad; sa.h_in = h[cur]; sa.c_in = cs[cur]; sa.ef = d_ef;
@@ -432,29 +435,29 @@ int forward_impl(asep_gnn* g, BufferPool& pool, int N, int E, const int32_t* d_e
             sa.A1 = (const gf32x4*)g->A1; sa.A2 = (const gf32x4*)g->A2; sa.b1 = g->b1; sa.b2 = g->b2;
             for (int q = 0; q < 4; ++q) { sa.Wg[q] = g->Wg[q]; sa.bg[q] = g->bg[q]; }
             sa.h_out = h[cur ^ 1]; sa.c_out = cs[cur ^ 1];
-            sa.N = N; sa.U = g->U; sa.Upad = g->Upad; sa.Ed = g->Ed; sa.E = std::max(E, 1); sa.nch = g->nch;
+            sa.N = N; sa.U = g->U; sa.Upad = g->Upad; sa.Ed = g->Ed; sa.E = Erows; sa.nch = g->nch;
             sa.qdesc = g->qdesc;
-            hipLaunchKernelGGL(gnn_step_big_kernel, dim3(N), dim3(256), g->big_lds, s, sa);
+            COUNTED_LAUNCH(nl, gnn_step_big_kernel, dim3(N), dim3(256), g->big_lds, s, sa);
         } else if (c.attention_heads > 0) {
             MsgAttArgs aa{};
             aa.u = d_u; aa.h = h[cur]; aa.ef = d_ef; aa.tptr = eb.colptr; aa.tsrc = eb.tsrc; aa.tfirst = eb.tfirst; aa.eidx = att_eidx;
             aa.hd = g->d_att_w;
             aa.M = att_M; aa.A = att_A;
-            aa.N = N; aa.U = g->U; aa.Ed = g->Ed; aa.E = std::max(E, 1); aa.H = H;
-            aa.xd = g->att_xd; aa.heads = c.attention_heads; aa.Etot = (int)att_maxE; aa.maxh = g->msg_maxh;
+            aa.N = N; aa.U = g->U; aa.Ed = g->Ed; aa.E = Erows; aa.H = H;
+            aa.xd = g->att_xd; aa.heads = c.attention_heads; aa.Etot = (int)maxE; aa.maxh = g->msg_maxh;
             const size_t lds = ((size_t)g->K + 2 * (size_t)g->msg_maxh) * sizeof(float);
-            hipLaunchKernelGGL(gnn_msg_att_kernel, dim3(N), dim3(256), lds, s, aa);
-            hipLaunchKernelGGL(gnn_att_softmax_kernel, dim3(N), dim3(64), 0, s, eb.colptr, att_eidx, att_A, c.attention_heads, (int)att_maxE, att_S);
-            hipLaunchKernelGGL(gnn_att_aggregate_kernel, dim3(N), dim3(64), 0, s, eb.colptr, att_eidx, att_widx, att_S, att_M, c.attention_heads,
-                               g->att_xd, (int)att_maxE, c.attention_merge, c.aggregation_type, x);
+            COUNTED_LAUNCH(nl, gnn_msg_att_kernel, dim3(N), dim3(256), lds, s, aa);
+            COUNTED_LAUNCH(nl, gnn_att_softmax_kernel, dim3(N), dim3(64), 0, s, eb.colptr, att_eidx, att_A, c.attention_heads, (int)maxE, att_S);
+            COUNTED_LAUNCH(nl, gnn_att_aggregate_kernel, dim3(N), dim3(64), 0, s, eb.colptr, att_eidx, att_widx, att_S, att_M, c.attention_heads,
+                           g->att_xd, (int)maxE, c.attention_merge, c.aggregation_type, x);
         } else {
             MsgGenArgs ma{};
             ma.u = d_u; ma.h = h[cur]; ma.ef = d_ef; ma.tptr = eb.colptr; ma.tsrc = eb.tsrc; ma.tfirst = eb.tfirst;
             ma.mlp = g->msg; ma.x = x;
-            ma.N = N; ma.U = g->U; ma.Ed = g->Ed; ma.E = std::max(E, 1); ma.H = H; ma.I = I; ma.maxh = g->msg_maxh;
+            ma.N = N; ma.U = g->U; ma.Ed = g->Ed; ma.E = Erows; ma.H = H; ma.I = I; ma.maxh = g->msg_maxh;
             ma.agg_max = c.aggregation_type;
             const size_t lds = ((size_t)g->K + 2 * (size_t)g->msg_maxh + I) * sizeof(float);
-            hipLaunchKernelGGL(gnn_message_generic_kernel, dim3(N), dim3(256), lds, s, ma);
+            COUNTED_LAUNCH(nl, gnn_message_generic_kernel, dim3(N), dim3(256), lds, s, ma);
         }
         if (mode == STEP_GENERIC) {                          // (the fused step kernels contain the LSTM update)
             LstmGenArgs la{};
@@ -462,37 +465,84 @@ int forward_impl(asep_gnn* g, BufferPool& pool, int N, int E, const int32_t* d_e
             for (int q = 0; q < 4; ++q) { la.Wg[q] = g->Wg[q]; la.bg[q] = g->bg[q]; }
             la.h_out = h[cur ^ 1]; la.c_out = cs[cur ^ 1]; la.N = N; la.U = g->U; la.H = H; la.I = g->Iout;
             la.use_h = c.lstm_use_hidden; la.use_u = c.lstm_use_input;
-            hipLaunchKernelGGL(gnn_lstm_generic_kernel, dim3(cdiv(N * H, 256)), dim3(256), 0, s, la);
+            COUNTED_LAUNCH(nl, gnn_lstm_generic_kernel, dim3(cdiv(N * H, 256)), dim3(256), 0, s, la);
         }
         cur ^= 1;
     }
     g->d_h = h[cur];
-    const float* hcls = h[cur];                              // what the pair classifier reads, and its width
-    int Hc = H;
+    out.hcls = h[cur];
+    out.Hc = H;
     if (c.output_type != 0) {                                // graph_gnn.py:158-166
-        Hc = c.output_type == 2 ? H + g->Uin : H;
-        float* y = (float*)pool.get((size_t)N * Hc * 4);
-        hipLaunchKernelGGL(gnn_output_type_kernel, dim3(cdiv(N * Hc, 256)), dim3(256), 0, s, h[cur], d_fed, N, H, g->Uin, g->Wout,
-                           c.output_type, y);
-        hcls = y;
+        out.Hc = c.output_type == 2 ? H + g->Uin : H;
+        float* y = (float*)pool.get((size_t)N * out.Hc * 4);
+        COUNTED_LAUNCH(nl, gnn_output_type_kernel, dim3(cdiv(N * out.Hc, 256)), dim3(256), 0, s, h[cur], d_fed, N, H, g->Uin, g->Wout,
+                       c.output_type, y);
+        out.hcls = y;
     }
+    return ASEP_OK;
+}
+
+// the pair classifier's arguments in both forms (cls_fast says which kernel runs); N and R stay 0: only the single-page kernels read them
+void pair_args(const asep_gnn* g, const float* Pt, const float* Qt, const int32_t* rel, float* out, PairArgs& pa, PairGenArgs& pg) {
+    pa.Pt = Pt; pa.Qt = Qt; pa.b1 = g->cb1; pa.W2 = g->C2; pa.b2 = g->cb2; pa.W3 = g->C3; pa.b3 = g->cb3;
+    pa.rel = rel; pa.out = out;
+    pg.Pt = Pt; pg.Qt = Qt; pg.b1 = g->cb1; pg.rest = g->cls_rest; pg.rel = rel; pg.out = out;
+    pg.maxw = g->cls_maxw;
+}
+
+int forward_impl(asep_gnn* g, BufferPool& pool, int N, int E, const int32_t* d_edges, const float* d_u, const float* d_ef, int R,
+                 const int32_t* d_rel, float* d_out, hipStream_t s) {
+    const asep_gnn_cfg& c = g->cfg;
+    if (N < 1 || E < 0 || R < 0) { set_error("asep_gnn_forward: bad sizes N=%d E=%d R=%d", N, E, R); return ASEP_ERR_ARG; }
+    if ((size_t)N * N > (size_t)1 << 30) { set_error("asep_gnn_forward: N=%d too large for the dense edge table", N); return ASEP_ERR_UNSUPPORTED; }
+    g->stream = s;
+    g->N = N;
+    ++g->fwd_serial;
+    pool.begin();
+    EdgeBufs eb{};
+    int rc = correct_edges_dev(g, pool, N, E, d_edges, eb, s);
+    if (rc) return rc;
+    GraphOut go;
+    auto chunk_rank = [&](int* widx, long& nl) {
+        const int chunk_nodes = std::max(1, 100000 / N);      // message_fn_chunk.py:77-78
+        COUNTED_LAUNCH(nl, edge_chunk_rank_kernel, dim3(cdiv(N, chunk_nodes)), dim3(256), 0, s, eb.sorted, eb.rowptr, eb.colptr, N, chunk_nodes, widx);
+    };
+    rc = graph_steps(g, pool, N, std::max(E, 1), (size_t)(c.undirected_graph ? 2 : 1) * std::max(E, 1), eb, d_u, d_ef, s, chunk_rank, go);
+    if (rc) return rc;
+    float* Pt = (float*)pool.get((size_t)N * c.cls_hidden1 * 4);
+    float* Qt = (float*)pool.get((size_t)N * c.cls_hidden1 * 4);
     if (R > 0) {
         hipLaunchKernelGGL(gnn_pair_pre_kernel, dim3(std::min(cdiv(N * c.cls_hidden1, 256), 1024)), dim3(256), 0, s,
-                           hcls, N, Hc, g->C1, c.cls_hidden1, Pt, Qt);
-        if (g->cls_fast) {
-            PairArgs pa{};
-            pa.Pt = Pt; pa.Qt = Qt; pa.b1 = g->cb1; pa.W2 = g->C2; pa.b2 = g->cb2; pa.W3 = g->C3; pa.b3 = g->cb3;
-            pa.rel = d_rel; pa.out = d_out; pa.N = N; pa.R = R;
+                           go.hcls, N, go.Hc, g->C1, c.cls_hidden1, Pt, Qt);
+        PairArgs pa{};
+        PairGenArgs pg{};
+        pair_args(g, Pt, Qt, d_rel, d_out, pa, pg);
+        pa.N = pg.N = N; pa.R = pg.R = R;
+        if (g->cls_fast)
             hipLaunchKernelGGL((gnn_pair_cls_kernel<64, 32, 2>), dim3(cdiv(R, 256)), dim3(256), 0, s, pa);
-        } else {
-            PairGenArgs pg{};
-            pg.Pt = Pt; pg.Qt = Qt; pg.b1 = g->cb1; pg.rest = g->cls_rest; pg.rel = d_rel; pg.out = d_out; pg.N = N; pg.R = R;
-            pg.maxw = g->cls_maxw;
+        else
             hipLaunchKernelGGL(gnn_pair_cls_generic_kernel, dim3(cdiv(R, PAIRG_P)), dim3(256), 2 * (size_t)PAIRG_P * g->cls_maxw * sizeof(float), s, pg);
-        }
     }
     ASEP_HIP_CHECK(hipGetLastError());
     return ASEP_OK;
+}
+
+// The inputs of a host-pointer graph entry (one page or the pages of a call; the totals) in the handle's grow-only device staging, queued for
+// upload on the null stream, and room for `outs` output floats: hipMalloc / hipFree pairs per call would cost more than the GNN.  A pointer is
+// null where its array is absent or empty.  Throws HipError.
+struct StagedGraph { int32_t* e; float* u; float* f; int32_t* r; float* o; };
+StagedGraph stage_graph(asep_gnn* g, size_t nodes, size_t edges, size_t rels, size_t outs, const int32_t* h_edges, const float* node_feat,
+                        const float* edge_feat, const int32_t* relations) {
+    BufferPool& p = g->host_stage;
+    p.begin();
+    auto up = [&p](auto* src, size_t n) { auto* d = upload(p, nullptr, src, n); return n ? d : nullptr; };   // (a slot per array, present or not)
+    StagedGraph st{};
+    st.e = up(h_edges, edges * 2);
+    st.u = upload(p, nullptr, node_feat, nodes * g->Uin);        // (features as fed: width Uin; never null)
+    st.f = up(edge_feat, edge_feat ? edges * g->Ed : 0);
+    st.r = up(relations, relations ? rels * 2 : 0);
+    st.o = (float*)p.get(std::max<size_t>(outs, 1) * sizeof(float));
+    return st;
 }
 
 // ---- the visual branch in front of the graph (graph_relation.py:84-172): what its three entries share --------------------------------------
@@ -876,23 +926,11 @@ int asep_gnn_forward(asep_gnn* g, int N, int E, const int32_t* edges, const floa
     int rc;
     if (E > 0 && (rc = check_indices("interacting_nodes", edges, (size_t)E, N))) return rc;
     if (relations && R > 0 && (rc = check_indices("relations", relations, (size_t)R, N))) return rc;
-    // grow-only device staging in the handle: seven hipMalloc / hipFree pairs per page would cost more than the GNN
-    const size_t ne = (size_t)E * 2, nu = (size_t)N * g->Uin, nf = (size_t)E * g->Ed;      // (features as fed: width Uin)
-    const size_t nr = relations ? (size_t)R * 2 : 0, no = (size_t)R * g->cfg.num_classes;
-    g->host_stage.begin();
-    int32_t* d_e = (int32_t*)g->host_stage.get(std::max<size_t>(ne, 1) * sizeof(int32_t));
-    float* d_u = (float*)g->host_stage.get(std::max<size_t>(nu, 1) * sizeof(float));
-    float* d_f = (float*)g->host_stage.get(std::max<size_t>(nf, 1) * sizeof(float));
-    int32_t* d_r = (int32_t*)g->host_stage.get(std::max<size_t>(nr, 1) * sizeof(int32_t));
-    float* d_o = (float*)g->host_stage.get(std::max<size_t>(no, 1) * sizeof(float));
-    if (ne) ASEP_HIP_CHECK(hipMemcpyAsync(d_e, edges, ne * sizeof(int32_t), hipMemcpyHostToDevice, nullptr));
-    ASEP_HIP_CHECK(hipMemcpyAsync(d_u, node_feat, nu * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    if (nf && edge_feat) ASEP_HIP_CHECK(hipMemcpyAsync(d_f, edge_feat, nf * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    if (nr) ASEP_HIP_CHECK(hipMemcpyAsync(d_r, relations, nr * sizeof(int32_t), hipMemcpyHostToDevice, nullptr));
-    rc = asep_gnn_forward_dev(g, N, E, ne ? d_e : nullptr, d_u, (nf && edge_feat) ? d_f : nullptr, R,
-                              nr ? d_r : nullptr, d_o, nullptr);
+    const size_t no = (size_t)R * g->cfg.num_classes;
+    const StagedGraph st = stage_graph(g, (size_t)N, (size_t)E, (size_t)R, no, edges, node_feat, edge_feat, relations);
+    rc = asep_gnn_forward_dev(g, N, E, st.e, st.u, st.f, R, st.r, st.o, nullptr);
     if (rc) return rc;
-    if (R > 0) ASEP_HIP_CHECK(hipMemcpyAsync(probs_out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    if (R > 0) ASEP_HIP_CHECK(hipMemcpyAsync(probs_out, st.o, no * sizeof(float), hipMemcpyDeviceToHost, nullptr));
     ASEP_HIP_CHECK(hipStreamSynchronize(nullptr));
     return ASEP_OK;
     ASEP_GUARD_END
@@ -1605,7 +1643,7 @@ double asep_gnn_flops(const asep_gnn* g, int N, int E_corrected, int R) {
 // ---- ABI 12: the graph part of the relation net for the pages of ONE call (gnn_batch_kernels.h) -----------------------------------------------
 // asep_gnn_forward_batch[_dev]: edge correction, T x (message, aggregation / attention soft-max, LSTM update) and the pair classifier each as one
 // launch over all pages.  The correction, the attention pairing's chunk ranks and the classifier go through the page table; every stage between
-// them is the single-page kernel over the nodes of the call (one CSR-by-target over all pages).  forward_impl above is the schedule this mirrors.
+// them is the single-page kernel over the nodes of the call (one CSR-by-target over all pages): graph_steps above, which forward_impl runs too.
 namespace {
 
 const char* table_error_text(GnnTableError e) {
@@ -1661,16 +1699,14 @@ int batch_graph_checks(asep_gnn* g, const char* fn, int n_pages, const int32_t* 
     return ASEP_OK;
 }
 
-#define BATCH_LAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); ++g->batch_launches; } while (0)
-
-int forward_batch_impl(asep_gnn* g, const char* fn, const GnnPageTable& tab, const GnnUnitTables& units, const int32_t* d_edges, const float* d_u,
+int forward_batch_impl(asep_gnn* g, const GnnPageTable& tab, const GnnUnitTables& units, const int32_t* d_edges, const float* d_u,
                        const float* d_ef, const int32_t* d_rel, float* d_out, hipStream_t s) {
     const asep_gnn_cfg& c = g->cfg;
     const int n = (int)tab.rows.size();
     const int NN = (int)tab.nodes, EE = (int)tab.edges, RR = (int)tab.rels;
     const int und = c.undirected_graph ? 1 : 0;
-    const size_t maxE = (size_t)tab.max_corrected;
     BufferPool& pool = g->batch_pool;
+    long& nl = g->batch_launches;                            // (0 since batch_graph_checks)
     g->stream = s;
     g->N = NN;
     ++g->fwd_serial;
@@ -1689,169 +1725,44 @@ int forward_batch_impl(asep_gnn* g, const char* fn, const GnnPageTable& tab, con
 
     // ---- edge correction (misc.py:7-151), every page's own table ----
     EdgeBufs eb{};
-    eb.table = (int*)pool.get((size_t)tab.cells * sizeof(int));
-    eb.rowcnt = (int*)pool.get((size_t)NN * sizeof(int));
-    eb.colcnt = (int*)pool.get((size_t)NN * sizeof(int));
-    eb.rowptr = (int*)pool.get((size_t)(NN + 1) * sizeof(int));
-    eb.colptr = (int*)pool.get((size_t)(NN + 1) * sizeof(int));
-    eb.sorted = (int32_t*)pool.get(maxE * 2 * sizeof(int32_t));
-    eb.sfirst = (int*)pool.get(maxE * sizeof(int));
-    eb.tsrc = (int*)pool.get(maxE * sizeof(int));
-    eb.tfirst = (int*)pool.get(maxE * sizeof(int));
-    ASEP_HIP_CHECK(hipMemsetAsync(eb.table, 0x7f, (size_t)tab.cells * sizeof(int), s));
-    if (units.fill[n] > 0) BATCH_LAUNCH(edge_table_pages_kernel, dim3(units.fill[n]), dim3(256), 0, s, pages(o_fill), d_edges, und, eb.table);
-    BATCH_LAUNCH(edge_count_pages_kernel, dim3(NN), dim3(64), 0, s, pages(o_node), eb.table, eb.rowcnt, eb.colcnt);
-    BATCH_LAUNCH(edge_scan_kernel, dim3(1), dim3(1024), 0, s, eb.rowcnt, eb.colcnt, NN, eb.rowptr, eb.colptr);   // (integer sums: one scan over the call)
-    BATCH_LAUNCH(edge_emit_pages_kernel, dim3(NN), dim3(64), 0, s, pages(o_node), eb.table, eb.rowptr, eb.colptr, eb.sorted, eb.sfirst, eb.tsrc, eb.tfirst);
+    if (int rc = edge_bufs(pool, (size_t)tab.cells, (size_t)NN, (size_t)tab.max_corrected, eb, s)) return rc;
+    if (units.fill[n] > 0) COUNTED_LAUNCH(nl, edge_table_pages_kernel, dim3(units.fill[n]), dim3(256), 0, s, pages(o_fill), d_edges, und, eb.table);
+    COUNTED_LAUNCH(nl, edge_count_pages_kernel, dim3(NN), dim3(64), 0, s, pages(o_node), eb.table, eb.rowcnt, eb.colcnt);
+    COUNTED_LAUNCH(nl, edge_scan_kernel, dim3(1), dim3(1024), 0, s, eb.rowcnt, eb.colcnt, NN, eb.rowptr, eb.colptr);   // (integer sums: one scan over the call)
+    COUNTED_LAUNCH(nl, edge_emit_pages_kernel, dim3(NN), dim3(64), 0, s, pages(o_node), eb.table, eb.rowptr, eb.colptr, eb.sorted, eb.sfirst, eb.tsrc, eb.tfirst);
     g->d_rowptr = eb.rowptr;
     g->gb_sorted = eb.sorted; g->gb_sfirst = eb.sfirst; g->gb_rowptr = eb.rowptr;
 
-    const int H = g->H, I = g->I;
-    const size_t nh = (size_t)NN * H;
-    float* h[2] = {(float*)pool.get(nh * 4), (float*)pool.get(nh * 4)};
-    float* cs[2] = {(float*)pool.get(nh * 4), (float*)pool.get(nh * 4)};
-    float* x = (float*)pool.get((size_t)NN * std::max(I, g->Iout) * 4);
+    // ---- the steps over the nodes of the call; tfirst holds rows of the call's edge features ----
+    GraphOut go;
+    auto chunk_rank = [&](int* widx, long& count) {
+        COUNTED_LAUNCH(count, edge_chunk_rank_pages_kernel, dim3(units.chunk[n]), dim3(256), 0, s, pages(o_chunk), eb.sorted, eb.rowptr, eb.colptr, widx);
+    };
+    if (int rc = graph_steps(g, pool, NN, std::max(EE, 1), (size_t)tab.max_corrected, eb, d_u, d_ef, s, chunk_rank, go)) return rc;
+    nl += go.launches;
+
+    // ---- the pair classifier, every page's own relations ----
     float* Pt = (float*)pool.get((size_t)NN * c.cls_hidden1 * 4);
     float* Qt = (float*)pool.get((size_t)NN * c.cls_hidden1 * 4);
     float* probs = (float*)pool.get((size_t)std::max(RR, 1) * c.num_classes * 4);
-    const float* d_fed = d_u;
-    const int Eall = std::max(EE, 1);                        // tfirst holds rows of the call's edge features: `tfirst % Eall` is the row itself
-    if (g->Wc) {
-        float* uc = (float*)pool.get((size_t)NN * g->U * 4);
-        BATCH_LAUNCH(gnn_compress_kernel, dim3(cdiv(NN * g->U, 256)), dim3(256), 0, s, d_u, NN, g->Uin, g->Wc, g->bc, g->U, uc);
-        d_u = uc;
-    }
-    int* att_eidx = nullptr;
-    int* att_widx = nullptr;
-    float *att_M = nullptr, *att_A = nullptr, *att_S = nullptr;
-    if (c.attention_heads > 0) {
-        att_eidx = (int*)pool.get(maxE * sizeof(int));
-        att_M = (float*)pool.get(maxE * c.attention_heads * g->att_xd * sizeof(float));
-        att_A = (float*)pool.get(maxE * c.attention_heads * sizeof(float));
-        att_S = (float*)pool.get(maxE * c.attention_heads * sizeof(float));
-        att_widx = (int*)pool.get(maxE * sizeof(int));
-        BATCH_LAUNCH(edge_rank_kernel, dim3(NN), dim3(64), 0, s, eb.colptr, eb.tsrc, eb.rowptr, eb.sorted, NN, att_eidx);
-        BATCH_LAUNCH(edge_chunk_rank_pages_kernel, dim3(units.chunk[n]), dim3(256), 0, s, pages(o_chunk), eb.sorted, eb.rowptr, eb.colptr, att_widx);
-    }
-    float* upad = nullptr;
-    const int mode = step_mode_of(g);
-    if (mode == STEP_BIG) {
-        upad = (float*)pool.get((size_t)NN * g->Upad * 4);
-        BATCH_LAUNCH(gnn_pad_rows_kernel, dim3(cdiv(NN * g->Upad, 256)), dim3(256), 0, s, d_u, NN, g->U, upad, g->Upad);
-    }
-    float *fPu = nullptr, *fP[2] = {nullptr, nullptr}, *fC = nullptr;
-    if (mode == STEP_FACT && c.num_transition_steps > 0) {
-        fPu = (float*)pool.get((size_t)NN * 64 * 4);
-        fP[0] = (float*)pool.get((size_t)NN * 64 * 4);
-        fP[1] = (float*)pool.get((size_t)NN * 64 * 4);
-        fC = (float*)pool.get(maxE * 32 * 4);
-        FactPreArgs fa{};
-        fa.u = d_u; fa.ef = d_ef; fa.tptr = eb.colptr; fa.tsrc = eb.tsrc; fa.tfirst = eb.tfirst;
-        fa.Wuu = g->Wuu; fa.Wde = g->Wde; fa.b1 = g->b1; fa.Pu = fPu; fa.C = fC;
-        fa.N = NN; fa.U = g->U; fa.Ed = g->Ed; fa.E = Eall;
-        BATCH_LAUNCH(gnn_fact_pre_kernel, dim3(NN), dim3(256), g->fact_pre_lds, s, fa);
-    }
-    if (mode != STEP_FACT || c.num_transition_steps == 0) {
-        ASEP_HIP_CHECK(hipMemsetAsync(h[0], 0, nh * 4, s));
-        ASEP_HIP_CHECK(hipMemsetAsync(cs[0], 0, nh * 4, s));
-    }
-    int cur = 0;
-    for (int t = 0; t < c.num_transition_steps; ++t) {
-        if (mode == STEP_FACT) {
-            StepFactArgs sa{};
-            sa.u = d_u; sa.h_in = h[cur]; sa.c_in = cs[cur]; sa.tptr = eb.colptr; sa.tsrc = eb.tsrc;
-            sa.P_in = t == 0 ? fPu : fP[t & 1];
-            sa.Pu = fPu; sa.C = fC;
-            sa.A1 = (const gf32x4*)g->A1f; sa.A2 = (const gf32x4*)g->A2; sa.b2 = g->b2; sa.Whh = g->Whh;
-            for (int q = 0; q < 4; ++q) { sa.Wg[q] = g->Wg[q]; sa.bg[q] = g->bg[q]; }
-            sa.h_out = h[cur ^ 1]; sa.c_out = cs[cur ^ 1];
-            sa.P_out = t + 1 < c.num_transition_steps ? fP[(t + 1) & 1] : nullptr;
-            sa.N = NN; sa.U = g->U; sa.first = t == 0;
-            BATCH_LAUNCH(gnn_step_fact_kernel, dim3(NN), dim3(256), g->fact_lds, s, sa);
-        } else if (mode == STEP_SMALL) {
-            StepArgs sa{};
-            sa.u = d_u; sa.h_in = h[cur]; sa.c_in = cs[cur]; sa.ef = d_ef;
-            sa.tptr = eb.colptr; sa.tsrc = eb.tsrc; sa.tfirst = eb.tfirst;
-            sa.A1 = (const gf32x4*)g->A1; sa.A2 = (const gf32x4*)g->A2; sa.b1 = g->b1; sa.b2 = g->b2;
-            for (int q = 0; q < 4; ++q) { sa.Wg[q] = g->Wg[q]; sa.bg[q] = g->bg[q]; }
-            sa.h_out = h[cur ^ 1]; sa.c_out = cs[cur ^ 1];
-            sa.N = NN; sa.U = g->U; sa.Ed = g->Ed; sa.E = Eall; sa.nch = g->nch;
-            sa.qdesc = g->qdesc;
-            BATCH_LAUNCH(gnn_step_kernel, dim3(NN), dim3(256), 0, s, sa);
-        } else if (mode == STEP_BIG) {
-            StepBigArgs sa{};
-            sa.u = upad; sa.h_in = h[cur]; sa.c_in = cs[cur]; sa.ef = d_ef;
-            sa.tptr = eb.colptr; sa.tsrc = eb.tsrc; sa.tfirst = eb.tfirst;
-            sa.A1 = (const gf32x4*)g->A1; sa.A2 = (const gf32x4*)g->A2; sa.b1 = g->b1; sa.b2 = g->b2;
-            for (int q = 0; q < 4; ++q) { sa.Wg[q] = g->Wg[q]; sa.bg[q] = g->bg[q]; }
-            sa.h_out = h[cur ^ 1]; sa.c_out = cs[cur ^ 1];
-            sa.N = NN; sa.U = g->U; sa.Upad = g->Upad; sa.Ed = g->Ed; sa.E = Eall; sa.nch = g->nch;
-            sa.qdesc = g->qdesc;
-            BATCH_LAUNCH(gnn_step_big_kernel, dim3(NN), dim3(256), g->big_lds, s, sa);
-        } else if (c.attention_heads > 0) {
-            MsgAttArgs aa{};
-            aa.u = d_u; aa.h = h[cur]; aa.ef = d_ef; aa.tptr = eb.colptr; aa.tsrc = eb.tsrc; aa.tfirst = eb.tfirst; aa.eidx = att_eidx;
-            aa.hd = g->d_att_w;
-            aa.M = att_M; aa.A = att_A;
-            aa.N = NN; aa.U = g->U; aa.Ed = g->Ed; aa.E = Eall; aa.H = H;
-            aa.xd = g->att_xd; aa.heads = c.attention_heads; aa.Etot = (int)maxE; aa.maxh = g->msg_maxh;
-            const size_t lds = ((size_t)g->K + 2 * (size_t)g->msg_maxh) * sizeof(float);
-            BATCH_LAUNCH(gnn_msg_att_kernel, dim3(NN), dim3(256), lds, s, aa);
-            BATCH_LAUNCH(gnn_att_softmax_kernel, dim3(NN), dim3(64), 0, s, eb.colptr, att_eidx, att_A, c.attention_heads, (int)maxE, att_S);
-            BATCH_LAUNCH(gnn_att_aggregate_kernel, dim3(NN), dim3(64), 0, s, eb.colptr, att_eidx, att_widx, att_S, att_M, c.attention_heads,
-                         g->att_xd, (int)maxE, c.attention_merge, c.aggregation_type, x);
-        } else {
-            MsgGenArgs ma{};
-            ma.u = d_u; ma.h = h[cur]; ma.ef = d_ef; ma.tptr = eb.colptr; ma.tsrc = eb.tsrc; ma.tfirst = eb.tfirst;
-            ma.mlp = g->msg; ma.x = x;
-            ma.N = NN; ma.U = g->U; ma.Ed = g->Ed; ma.E = Eall; ma.H = H; ma.I = I; ma.maxh = g->msg_maxh;
-            ma.agg_max = c.aggregation_type;
-            const size_t lds = ((size_t)g->K + 2 * (size_t)g->msg_maxh + I) * sizeof(float);
-            BATCH_LAUNCH(gnn_message_generic_kernel, dim3(NN), dim3(256), lds, s, ma);
-        }
-        if (mode == STEP_GENERIC) {
-            LstmGenArgs la{};
-            la.x = x; la.h_in = h[cur]; la.c_in = cs[cur]; la.u = d_u;
-            for (int q = 0; q < 4; ++q) { la.Wg[q] = g->Wg[q]; la.bg[q] = g->bg[q]; }
-            la.h_out = h[cur ^ 1]; la.c_out = cs[cur ^ 1]; la.N = NN; la.U = g->U; la.H = H; la.I = g->Iout;
-            la.use_h = c.lstm_use_hidden; la.use_u = c.lstm_use_input;
-            BATCH_LAUNCH(gnn_lstm_generic_kernel, dim3(cdiv(NN * H, 256)), dim3(256), 0, s, la);
-        }
-        cur ^= 1;
-    }
-    g->d_h = h[cur];
-    const float* hcls = h[cur];
-    int Hc = H;
-    if (c.output_type != 0) {
-        Hc = c.output_type == 2 ? H + g->Uin : H;
-        float* y = (float*)pool.get((size_t)NN * Hc * 4);
-        BATCH_LAUNCH(gnn_output_type_kernel, dim3(cdiv(NN * Hc, 256)), dim3(256), 0, s, h[cur], d_fed, NN, H, g->Uin, g->Wout, c.output_type, y);
-        hcls = y;
-    }
     if (RR > 0) {
-        BATCH_LAUNCH(gnn_pair_pre_pages_kernel, dim3(units.pre[n]), dim3(256), 0, s, pages(o_pre), hcls, Hc, g->C1, c.cls_hidden1, Pt, Qt);
-        if (g->cls_fast) {
-            PairArgs pa{};
-            pa.Pt = Pt; pa.Qt = Qt; pa.b1 = g->cb1; pa.W2 = g->C2; pa.b2 = g->cb2; pa.W3 = g->C3; pa.b3 = g->cb3;
-            pa.rel = d_rel; pa.out = probs;
-            BATCH_LAUNCH((gnn_pair_cls_pages_kernel<64, 32, 2>), dim3(units.cls[n]), dim3(256), 0, s, pages(o_cls), pa);
-        } else {
-            PairGenArgs pg{};
-            pg.Pt = Pt; pg.Qt = Qt; pg.b1 = g->cb1; pg.rest = g->cls_rest; pg.rel = d_rel; pg.out = probs;
-            pg.maxw = g->cls_maxw;
-            BATCH_LAUNCH(gnn_pair_cls_generic_pages_kernel, dim3(units.cls[n]), dim3(256), 2 * (size_t)PAIRG_P * g->cls_maxw * sizeof(float), s,
-                         pages(o_cls), pg);
-        }
-        BATCH_LAUNCH(gnn_take_class_kernel, dim3(cdiv(RR, 256)), dim3(256), 0, s, probs, RR, c.num_classes, 1, d_out);
+        COUNTED_LAUNCH(nl, gnn_pair_pre_pages_kernel, dim3(units.pre[n]), dim3(256), 0, s, pages(o_pre), go.hcls, go.Hc, g->C1, c.cls_hidden1, Pt, Qt);
+        PairArgs pa{};
+        PairGenArgs pg{};
+        pair_args(g, Pt, Qt, d_rel, probs, pa, pg);
+        if (g->cls_fast)
+            COUNTED_LAUNCH(nl, (gnn_pair_cls_pages_kernel<64, 32, 2>), dim3(units.cls[n]), dim3(256), 0, s, pages(o_cls), pa);
+        else
+            COUNTED_LAUNCH(nl, gnn_pair_cls_generic_pages_kernel, dim3(units.cls[n]), dim3(256), 2 * (size_t)PAIRG_P * g->cls_maxw * sizeof(float), s,
+                           pages(o_cls), pg);
+        COUNTED_LAUNCH(nl, gnn_take_class_kernel, dim3(cdiv(RR, 256)), dim3(256), 0, s, probs, RR, c.num_classes, 1, d_out);
     }
     if (int rc = tables_read(slot, s)) return rc;
     ASEP_HIP_CHECK(hipGetLastError());
     g->graph_pages = tab.rows;
     g->graph_serial = g->fwd_serial;
-    (void)fn;
     return ASEP_OK;
 }
-#undef BATCH_LAUNCH
 
 // "names a node outside" per page, as check_indices says it for one page
 int check_page_indices(const char* fn, const char* what, const int32_t* idx, const GnnPageTable& tab, bool relations) {
@@ -1892,7 +1803,7 @@ int asep_gnn_forward_batch_dev(asep_gnn* g, int n_pages, const int32_t* N, const
     GnnPageTable tab;
     GnnUnitTables units;
     if (int rc = batch_graph_checks(g, fn, n_pages, N, E, R, d_node_feat, d_edges, d_edge_feat, d_probs_out, max_floats, tab, units)) return rc;
-    return forward_batch_impl(g, fn, tab, units, d_edges, d_node_feat, d_edge_feat, d_relations, d_probs_out, (hipStream_t)stream);
+    return forward_batch_impl(g, tab, units, d_edges, d_node_feat, d_edge_feat, d_relations, d_probs_out, (hipStream_t)stream);
     ASEP_GUARD_END
 }
 
@@ -1906,21 +1817,11 @@ int asep_gnn_forward_batch(asep_gnn* g, int n_pages, const int32_t* N, const int
     if (rc) return rc;
     if (tab.edges > 0 && (rc = check_page_indices(fn, "interacting_nodes", edges, tab, false))) return rc;
     if (relations && tab.rels > 0 && (rc = check_page_indices(fn, "relations", relations, tab, true))) return rc;
-    const size_t ne = (size_t)tab.edges * 2, nu = (size_t)tab.nodes * g->Uin, nf = (size_t)tab.edges * g->Ed;
-    const size_t nr = relations ? (size_t)tab.rels * 2 : 0, no = (size_t)tab.rels;
-    g->host_stage.begin();
-    int32_t* d_e = (int32_t*)g->host_stage.get(std::max<size_t>(ne, 1) * sizeof(int32_t));
-    float* d_u = (float*)g->host_stage.get(std::max<size_t>(nu, 1) * sizeof(float));
-    float* d_f = (float*)g->host_stage.get(std::max<size_t>(nf, 1) * sizeof(float));
-    int32_t* d_r = (int32_t*)g->host_stage.get(std::max<size_t>(nr, 1) * sizeof(int32_t));
-    float* d_o = (float*)g->host_stage.get(std::max<size_t>(no, 1) * sizeof(float));
-    if (ne) ASEP_HIP_CHECK(hipMemcpyAsync(d_e, edges, ne * sizeof(int32_t), hipMemcpyHostToDevice, nullptr));
-    ASEP_HIP_CHECK(hipMemcpyAsync(d_u, node_feat, nu * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    if (nf && edge_feat) ASEP_HIP_CHECK(hipMemcpyAsync(d_f, edge_feat, nf * sizeof(float), hipMemcpyHostToDevice, nullptr));
-    if (nr) ASEP_HIP_CHECK(hipMemcpyAsync(d_r, relations, nr * sizeof(int32_t), hipMemcpyHostToDevice, nullptr));
-    rc = forward_batch_impl(g, fn, tab, units, ne ? d_e : nullptr, d_u, (nf && edge_feat) ? d_f : nullptr, nr ? d_r : nullptr, d_o, nullptr);
+    const size_t no = (size_t)tab.rels;
+    const StagedGraph st = stage_graph(g, (size_t)tab.nodes, (size_t)tab.edges, no, no, edges, node_feat, edge_feat, relations);
+    rc = forward_batch_impl(g, tab, units, st.e, st.u, st.f, st.r, st.o, nullptr);
     if (rc) return rc;
-    if (no) ASEP_HIP_CHECK(hipMemcpyAsync(probs_out, d_o, no * sizeof(float), hipMemcpyDeviceToHost, nullptr));
+    if (no) ASEP_HIP_CHECK(hipMemcpyAsync(probs_out, st.o, no * sizeof(float), hipMemcpyDeviceToHost, nullptr));
     ASEP_HIP_CHECK(hipStreamSynchronize(nullptr));
     return ASEP_OK;
     ASEP_GUARD_END

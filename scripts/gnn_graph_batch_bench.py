@@ -10,9 +10,10 @@ Two figures per form, both per page:
   device_us  the device-pointer entry on inputs that already lie in HBM: the time between two events around the queued calls of all 64 pages
              (launch gaps included: it is what the stream is busy or waiting for launches)
 
-``--parent_lib`` names a build of the PARENT commit's libasep_hip.so; its single-page entries run on the same inputs, in the same process and in
-alternation with this build's (loaded with RTLD_LOCAL | RTLD_DEEPBIND, so that each library calls its own functions).  Warm-up rounds, then
-``--rounds`` rounds that visit the forms in turn; the medians over the rounds are reported.  Nothing here asserts a speed-up.
+``--parent_lib`` names a build of the PARENT commit's libasep_hip.so; its single-page and batched entries (``parent_single``, ``parent_batch_<k>``)
+run on the same inputs, in the same process and in alternation with this build's (loaded with RTLD_LOCAL | RTLD_DEEPBIND, so that each library
+calls its own functions); its batched results and launch record are compared with this build's.  Warm-up rounds, then ``--rounds`` rounds that
+visit the forms in turn; the medians over the rounds are reported.  Nothing here asserts a speed-up.
 
     python scripts/gnn_graph_batch_bench.py --out profiles/gnn_graph_batch/gpu.json [--parent_lib PATH]
 """
@@ -44,6 +45,9 @@ def _load_parent(path):
     lib.asep_gnn_free.argtypes, lib.asep_gnn_free.restype = [P], None
     lib.asep_gnn_forward.argtypes, lib.asep_gnn_forward.restype = [P, C.c_int, C.c_int, P, P, P, C.c_int, P, P], C.c_int
     lib.asep_gnn_forward_dev.argtypes, lib.asep_gnn_forward_dev.restype = [P, C.c_int, C.c_int, P, P, P, C.c_int, P, P, P], C.c_int
+    lib.asep_gnn_forward_batch.argtypes, lib.asep_gnn_forward_batch.restype = [P, C.c_int] + [P] * 8 + [C.c_size_t], C.c_int
+    lib.asep_gnn_forward_batch_dev.argtypes, lib.asep_gnn_forward_batch_dev.restype = [P, C.c_int] + [P] * 8 + [C.c_size_t, P], C.c_int
+    lib.asep_gnn_batch_launches.argtypes, lib.asep_gnn_batch_launches.restype = [P], C.c_long
     return lib
 
 
@@ -116,23 +120,25 @@ def main(argv=None):
                 rc = L.asep_gnn_forward_dev(h, N, E, e.data_ptr(), u.data_ptr(), ef.data_ptr(), R, None, d_out1.data_ptr(), sp)
                 assert rc >= 0
 
-        def batch_wall(P):
+        def batch_wall(P, L=lib, h=h_new):
             for g in groups[P]:
-                rc = lib.asep_gnn_forward_batch(h_new, len(g["N"]), i32p(g["N"]), i32p(g["E"]), i32p(g["R"]), g["u"].ctypes.data,
-                                                g["edges"].ctypes.data, g["ef"].ctypes.data, None, g["out"].ctypes.data, g["out"].size)
-                assert rc >= 0, _lib.last_error()
+                rc = L.asep_gnn_forward_batch(h, len(g["N"]), i32p(g["N"]), i32p(g["E"]), i32p(g["R"]), g["u"].ctypes.data,
+                                              g["edges"].ctypes.data, g["ef"].ctypes.data, None, g["out"].ctypes.data, g["out"].size)
+                assert rc >= 0, L.asep_last_error()
 
-        def batch_dev(P):
+        def batch_dev(P, L=lib, h=h_new):
             for g in groups[P]:
-                rc = lib.asep_gnn_forward_batch_dev(h_new, len(g["N"]), i32p(g["N"]), i32p(g["E"]), i32p(g["R"]), g["d"][0].data_ptr(),
-                                                    g["d"][1].data_ptr(), g["d"][2].data_ptr(), None, g["d_out"].data_ptr(), g["d_out"].numel(), sp)
-                assert rc >= 0, _lib.last_error()
+                rc = L.asep_gnn_forward_batch_dev(h, len(g["N"]), i32p(g["N"]), i32p(g["E"]), i32p(g["R"]), g["d"][0].data_ptr(),
+                                                  g["d"][1].data_ptr(), g["d"][2].data_ptr(), None, g["d_out"].data_ptr(), g["d_out"].numel(), sp)
+                assert rc >= 0, L.asep_last_error()
 
         forms = {}
         if parent:
             forms["parent_single"] = (lambda: single_wall(parent, h_old), lambda: single_dev(parent, h_old))
         forms["single"] = (lambda: single_wall(lib, h_new), lambda: single_dev(lib, h_new))
         for P in PER_CALL:
+            if parent:
+                forms[f"parent_batch_{P}"] = (lambda P=P: batch_wall(P, parent, h_old), lambda P=P: batch_dev(P, parent, h_old))
             forms[f"batch_{P}"] = (lambda P=P: batch_wall(P), lambda P=P: batch_dev(P))
 
         # the forms agree on the values before anything is timed: page 5 alone (both builds) and as a member of a call of 16
@@ -141,11 +147,14 @@ def main(argv=None):
         ref = out1[:, 1].copy()
         batch_wall(16)
         same = bool(np.array_equal(groups[16][0]["out"][5 * R:6 * R].view(np.uint32), ref.view(np.uint32)))
-        same_parent = None
+        same_parent = same_parent_batch = None
         if parent:
             parent.asep_gnn_forward(h_old, N, E, pages[5]["edges"].ctypes.data, pages[5]["u"].ctypes.data, pages[5]["ef"].ctypes.data, R, None,
                                     out1.ctypes.data)
             same_parent = bool(np.array_equal(out1[:, 1].view(np.uint32), ref.view(np.uint32)))
+            groups[16][0]["out"].fill(-1.0)
+            batch_wall(16, parent, h_old)
+            same_parent_batch = bool(np.array_equal(groups[16][0]["out"][5 * R:6 * R].view(np.uint32), ref.view(np.uint32)))
 
         wall = {k: [] for k in forms}
         devt = {k: [] for k in forms}
@@ -163,14 +172,20 @@ def main(argv=None):
                 if rnd >= a.warmup:
                     wall[name].append((t1 - t0) * 1e6 / PAGES)
                     devt[name].append(e0.elapsed_time(e1) * 1e3 / PAGES)
-        res = {"N": N, "E_fed": int(E), "R": int(R), "batch_equals_single_bits": same, "parent_equals_single_bits": same_parent, "forms": {}}
+        res = {"N": N, "E_fed": int(E), "R": int(R), "batch_equals_single_bits": same, "parent_equals_single_bits": same_parent,
+               "parent_equals_batch_bits": same_parent_batch, "forms": {}}
         for name in forms:
             res["forms"][name] = {"wall_us_per_page": round(statistics.median(wall[name]), 2),
                                   "wall_us_min_max": [round(min(wall[name]), 2), round(max(wall[name]), 2)],
                                   "device_us_per_page": round(statistics.median(devt[name]), 2),
                                   "device_us_min_max": [round(min(devt[name]), 2), round(max(devt[name]), 2)]}
-        batch_dev(64)
-        res["launches_per_call"] = gnn_io.gnn_batch_launches(graph)
+        res["launches_per_call"], res["parent_launches_per_call"] = {}, {} if parent else None
+        for P in PER_CALL:                                                 # the launch record of a call at every pages-per-call
+            batch_dev(P)
+            res["launches_per_call"][str(P)] = gnn_io.gnn_batch_launches(graph)
+            if parent:
+                batch_dev(P, parent, h_old)
+                res["parent_launches_per_call"][str(P)] = parent.asep_gnn_batch_launches(h_old)
         result["sizes"][str(N)] = res
         print(json.dumps(res), flush=True)
 

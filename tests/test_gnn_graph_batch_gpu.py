@@ -88,6 +88,26 @@ def test_listed_relations_and_a_single_page_call():
     graph.close()
 
 
+def test_a_single_page_forward_between_two_batched_calls_changes_nothing():
+    """the two entries run one step schedule on one handle: a single-page forward leaves the launch record of the last batched call alone, and
+    leaves no state behind that the next batched call reads (same launch count, same bits)"""
+    from citlab_article_separation_new_amd import gnn_io
+    cfg, w, graph = _setup()
+    rng = np.random.default_rng(5)
+    pages = [_page(rng, N, {3: 5, 7: 12}.get(N, 5 * N), cfg) for N in (3, 65, 7)]
+    first = gnn_io.gnn_forward_batch(graph, pages)
+    launches = gnn_io.gnn_batch_launches(graph)
+    assert launches > 0
+    alone, _ = _single(graph, pages[1])
+    assert gnn_io.gnn_batch_launches(graph) == launches
+    assert np.array_equal(_bits(alone), _bits(first[1]))
+    again = gnn_io.gnn_forward_batch(graph, pages)
+    assert gnn_io.gnn_batch_launches(graph) == launches
+    for a, b in zip(again, first):
+        assert np.array_equal(_bits(a), _bits(b))
+    graph.close()
+
+
 def test_edge_correction_per_page():
     """a page without edges, a page with duplicates, self loops and both directions of one edge, a fully connected page: the results and the
     corrected edge lists of the page alone"""
