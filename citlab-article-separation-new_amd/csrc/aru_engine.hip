@@ -1880,7 +1880,8 @@ asep_aru* asep_aru_load(const void* weight_blob, size_t nbytes, const asep_aru_c
     std::map<std::string, std::vector<float>> taps;
     if (cfg->input_pyramid) {
         try {
-            blob = split_pyramid_blob(blob, *cfg, taps);       // ru_net/... -> the names and conv1 shapes of the packers + the taps' rows
+            // ru_net/... -> the names and conv1 shapes of the packers + the taps' rows; a conv1 wider than the tap launch's LDS bound is refused
+            blob = split_pyramid_blob(blob, *cfg, taps, PYR_MAX_COUT);
         } catch (const PackRefusal&) {
             return nullptr;
         }

@@ -521,14 +521,15 @@ inline std::vector<float> pack_logit_diff(const Layer& L) {
 // The graph's variables live under ru_net/..., and conv1 of every block that reads the pooled page I_l has `channels` more input rows, LAST in
 // the concat (RU_v2.py:101,144): down blocks l >= 1 [3,3,f_{l-1} + channels,f_l], with inp4up up blocks [3,3,2 f_l + channels,f_l].  Returns the
 // blob that the packers above read -- the same tensors under aru_net/..., those filters cut to their main rows (the layer the conv kernels run)
-// -- and leaves the image rows [9][channels][f_l] (pyr_tap_kernel's order) in taps[<aru_net scope of the conv1>].
-inline WeightBlob split_pyramid_blob(const WeightBlob& in, const asep_aru_cfg& cfg, std::map<std::string, std::vector<float>>& taps) {
+// -- and leaves the image rows [9][channels][f_l] (pyr_tap_kernel's order) in taps[<aru_net scope of the conv1>].  max_cout: the widest conv1 the
+// tap kernel serves (PYR_MAX_COUT of pyr_kernels.h, where the bound is derived); a wider one is refused here, before anything is launched.
+inline WeightBlob split_pyramid_blob(const WeightBlob& in, const asep_aru_cfg& cfg, std::map<std::string, std::vector<float>>& taps, int max_cout) {
     WeightBlob out;
     for (const auto& kv : in) out[kv.first.compare(0, 7, "ru_net/") == 0 ? "aru_" + kv.first.substr(3) : kv.first] = kv.second;
     const int n = cfg.scale_space_num, ch = cfg.channels;
     auto cut = [&](const std::string& scope, int cmain, int f) {
-        if (f % 4 != 0 || f > 256) {
-            set_error("weights: %s has %d output channels: the input-pyramid tap serves multiples of 4 up to 256", scope.c_str(), f);
+        if (f % 4 != 0 || f > max_cout) {
+            set_error("weights: %s has %d output channels: the input-pyramid tap serves multiples of 4 up to %d", scope.c_str(), f, max_cout);
             throw PackRefusal{ASEP_ERR_UNSUPPORTED};
         }
         auto wi = out.find(scope + "/weights");

@@ -5,7 +5,7 @@
 // colour) with the LAST CH input rows of conv1/weights, no bias.  conv1_main is the layer the engine's conv kernels already run, unchanged;
 // pyr_tap_kernel adds the tap to its result t in place.
 //
-//   pyr_tap_kernel<CH>:  t[h,w,cout] += tap(I[h,w,CH]); cout a run-time multiple of 4 (<= 256: the filter lies in LDS).  One block = 64 x 4
+//   pyr_tap_kernel<CH>:  t[h,w,cout] += tap(I[h,w,CH]); cout a run-time multiple of 4 (<= PYR_MAX_COUT: the filter lies in LDS).  One block = 64 x 4
 //     pixels.  The block puts its standardised 66 x 6 window (zero outside the page = SAME padding; {mean, 1/std} applied while loading like
 //     the first-layer kernels do) and the 9 CH cout filter values into LDS; a thread then takes (pixel, channel quad) items, consecutive
 //     threads consecutive quads of a pixel and then the next pixel of the row, so every load and store of t is a 16-byte access and a wave's
@@ -24,9 +24,17 @@
 namespace asep {
 
 constexpr int PYR_TW = 64, PYR_TH = 4;                         // output pixels of a block
-constexpr int PYR_MAX_COUT = 256;
 constexpr int pyr_win_floats(int ch) { return (PYR_TH + 2) * (PYR_TW + 2) * ch; }      // 396 ch: a multiple of 4 (the filter behind it is 16-byte aligned)
-inline size_t pyr_tap_lds(int ch, int cout) { return ((size_t)pyr_win_floats(ch) + (size_t)9 * ch * cout) * sizeof(float); }
+constexpr size_t pyr_tap_lds(int ch, int cout) { return ((size_t)pyr_win_floats(ch) + (size_t)9 * ch * cout) * sizeof(float); }
+// The widest tapped conv1.  A block's dynamic LDS is pyr_tap_lds(ch, cout) = (396 ch + 9 ch cout) * 4 bytes, and launch_pyr_tap asks for it
+// without hipFuncAttributeMaxDynamicSharedMemorySize, so a launch may count on 64 KiB and no more.  At cout = 256 that is 10 800 bytes gray and
+// 32 400 bytes colour: half the limit, and four blocks a CU.  The LDS alone would hold up to cout 560 in colour ((16384 - 1188) / 27, down to a
+// multiple of 4) and 1776 gray; 1024 channels in colour (feat_root 32, six levels) ask for 115 344 bytes and cannot launch.  The bound stays
+// at 256, the widest level that the engine's other layers are compared at (feat_root 16 with five levels, feat_root 8 with six): it is what
+// asep_aru_load refuses beyond (split_pyramid_blob, with the layer and this limit in the message), and the assertion below ties it to the LDS.
+constexpr int PYR_MAX_COUT = 256;
+constexpr size_t PYR_LDS_LIMIT = 64 * 1024;                    // dynamic LDS of a launch without the opt-in attribute
+static_assert(pyr_tap_lds(3, PYR_MAX_COUT) <= PYR_LDS_LIMIT && pyr_tap_lds(1, PYR_MAX_COUT) <= PYR_LDS_LIMIT, "the tap's window and filter must fit the LDS of a plain launch");
 
 struct TapProb {
     const float* img;      // pooled page of the block's level [H,W,CH], values as fed (not standardised)
