@@ -114,15 +114,15 @@ def _slow(prep, dmax):
     return pairs, recs, truth
 
 
-def _check_hist(pairs, mode):
+def _compare_hist(preps, results):
+    """the histograms of device_rel_hits(preps, want_hist=True) against _slow, exactly (shared with
+    test_measure_seams_gpu.py, which sets tolerances of its own on the prepared pairs).  Returns the number of candidate
+    pairs and _slow's three results per file pair."""
     import numpy as np
-    from citlab_article_separation_new_amd import measure
-    import measure_cases as mc
-    preps = measure.prepare(pairs, *mc.MODES[mode], 0.25, 5)
-    results = measure.device_rel_hits(preps, want_hist=True)
-    n_pairs = 0
+    n_pairs, slow = 0, []
     for prep, res in zip(preps, results):
         sp, sr, st = _slow(prep, res.dmax)
+        slow.append((sp, sr, st))
         got_p = {(int(i), int(j)): h for i, j, h in zip(res.pair_i, res.pair_j, res.pair_hist)}
         got_r = {(int(j), int(a)): h for j, a, h in zip(res.rec_j, res.rec_a, res.rec_hist)}
         assert sorted(got_p) == sorted(sp) and list(got_p) == sorted(got_p), "candidate pairs differ"
@@ -131,7 +131,14 @@ def _check_hist(pairs, mode):
         assert all(np.array_equal(got_r[k], sr[k]) for k in sr), "record histograms differ"
         assert all(np.array_equal(res.truth_hist[j][u], st[j][u]) for j in range(prep.truth.n) for u in (0, 1)), "truth histograms differ"
         n_pairs += len(sp)
-    return n_pairs
+    return n_pairs, slow
+
+
+def _check_hist(pairs, mode):
+    from citlab_article_separation_new_amd import measure
+    import measure_cases as mc
+    preps = measure.prepare(pairs, *mc.MODES[mode], 0.25, 5)
+    return _compare_hist(preps, measure.device_rel_hits(preps, want_hist=True))[0]
 
 
 def check_hist_golden():
