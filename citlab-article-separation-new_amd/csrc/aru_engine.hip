@@ -1479,7 +1479,7 @@ int forward_impl(asep_aru* m, asep_aru::Lane& L, int page0, int B, const float* 
         for (int b = 0; b < B; ++b)
             for (int s = 0; s < nsc; ++s) {
                 all.push_back(pyr[s][b]);
-                names.push_back((page0 + b ? "p" + std::to_string(page0 + b) + "/" : std::string()) + "scale_" + std::to_string(s));
+                names.push_back(page_prefix(page0 + b) + "scale_" + std::to_string(s));
                 stats.push_back(stats0[b]);
             }
         if (!cfg.mvn) stats.clear();
@@ -1501,10 +1501,7 @@ int forward_impl(asep_aru* m, asep_aru::Lane& L, int page0, int B, const float* 
                 ASEP_HIP_CHECK(hipEventRecord(L.ev_join, L.side));
                 m->stream = stream;
             }
-            for (size_t i = 0; i < att.size(); ++i) {
-                const int pg = page0 + (int)i / nsc;
-                m->endpoints[(pg ? "p" + std::to_string(pg) + "/" : std::string()) + "att_" + std::to_string(i % nsc)] = att[i];
-            }
+            for (size_t i = 0; i < att.size(); ++i) m->endpoints[page_prefix(page0 + (int)i / nsc) + "att_" + std::to_string(i % nsc)] = att[i];
         }
         TL feat = det_cnn(m, all, names, stats);
         if (forked) ASEP_HIP_CHECK(hipStreamWaitEvent(stream, L.ev_join, 0));
@@ -1576,7 +1573,7 @@ int forward_impl(asep_aru* m, asep_aru::Lane& L, int page0, int B, const float* 
                 // RU_v2: the logits as an end point of their own ("logits", "p<b>/logits"; the probabilities do not determine them): the same
                 // kernel once more without the soft-max, 4 (feat_root + n_classes) bytes per pixel
                 const Tensor lg = new_tensor(m, H, W, cfg.n_classes);
-                m->endpoints[(page0 + b ? "p" + std::to_string(page0 + b) + "/" : std::string()) + "logits"] = lg;
+                m->endpoints[page_prefix(page0 + b) + "logits"] = lg;
                 CombineArgs cl = ca;
                 cl.out = lg.p; cl.out_u8 = nullptr; cl.out_mask = nullptr; cl.softmax = 0; cl.wd = nullptr;
                 ProfScope pl(m, cname, 2.0 * H * W * 16.0 * cfg.feat_root * cfg.n_classes, "logits end point");

@@ -547,9 +547,6 @@ StagedGraph stage_graph(asep_gnn* g, size_t nodes, size_t edges, size_t rels, si
 
 // ---- the visual branch in front of the graph (graph_relation.py:84-172): what its three entries share --------------------------------------
 
-// the end points of page b of a grouped backbone forward are "<page_prefix(b)><name>"
-std::string page_prefix(int b) { return b ? "p" + std::to_string(b) + "/" : std::string(); }
-
 asep_gnn::FmapRef map_ref(const float* p, const FmapShape& m) { return asep_gnn::FmapRef{p, m.fh, m.fw, m.C, m.bf}; }
 
 // the per-page arguments of the single (b < 0: its message names no page), the uniform and the table entries
@@ -565,7 +562,21 @@ int check_visual_page(const asep_gnn* g, const char* fn, int b, const asep_gnn_p
     return ASEP_OK;
 }
 
-int reserve_floats(float** p, size_t* cap, size_t n) {          // a grow-only buffer of the handle (d_u_cat, d_ef_cat)
+// the compression layer "<scope>weights" [C, d] / "<scope>bias" [d] of a map of C channels (nodes' or interactions' side), owned through vis_owned
+int upload_compression(asep_gnn* g, const std::string& scope, int C, float** dW, float** db, int* d) {
+    auto w = g->vis_blob.find(scope + "weights"), b = g->vis_blob.find(scope + "bias");
+    if (w == g->vis_blob.end() || b == g->vis_blob.end()) { set_error("weights: missing tensor %sweights|bias", scope.c_str()); return ASEP_ERR_WEIGHTS; }
+    if (w->second.dims.size() != 2 || w->second.dims[0] != C || b->second.dims.size() != 1 || b->second.dims[0] != w->second.dims[1]) {
+        set_error("weights: %sweights must be [%d, d] with a matching bias", scope.c_str(), C);
+        return ASEP_ERR_WEIGHTS;
+    }
+    *d = w->second.dims[1];
+    int rc = upload_named(g->vis_owned, g->vis_blob, scope + "weights", w->second.dims, dW);
+    if (!rc) rc = upload_named(g->vis_owned, g->vis_blob, scope + "bias", b->second.dims, db);
+    return rc;
+}
+
+int reserve_floats(float** p, size_t* cap, size_t n) {         // a grow-only buffer of the handle (d_u_cat, d_ef_cat)
     if (*cap < n) {
         if (*p) (void)hipFree(*p);
         *p = nullptr; *cap = 0;
@@ -610,6 +621,15 @@ int page_map_plan(asep_gnn* g, const std::string& prefix, std::vector<FmapStep>&
     return ASEP_OK;
 }
 
+// One record of the backbone's launch profile (aru_prof_begin / aru_prof_end) around the launches that follow it in its block: the visual
+// stage's kernels are timed in the backbone's report.  Closed on every way out of the block.
+struct ProfiledLaunch {
+    void* scope;
+    ProfiledLaunch(asep_gnn* g, const char* name, const std::string& detail, double flops, double bytes)
+        : scope(aru_prof_begin(g->backbone, name, detail.c_str(), flops, bytes)) {}
+    ~ProfiledLaunch() { aru_prof_end(scope); }
+};
+
 // feature_map_generators.py:140-194 for the page whose backbone end points are "<prefix><name>" of the forward queued on s: every generated
 // map into the handle's arena (two launches each, fmap_kernels.h), every map's address into g->fmap_last.  A layout without generated
 // maps returns at once: it allocates and launches nothing.
@@ -638,17 +658,13 @@ int generate_maps_dev(asep_gnn* g, const std::string& prefix, hipStream_t s) {
         if (k.n1 + 255 > ((size_t)1 << 31) * 256 || k.n2 + 255 > ((size_t)1 << 31) * 256) { set_error("feature map %zu is too large for one launch", i); return ASEP_ERR_UNSUPPORTED; }
         const std::string where = "fm_" + std::to_string(i) + " " + std::to_string(k.d.ih) + "x" + std::to_string(k.d.iw);
         {
-            const std::string det = where + " " + std::to_string(k.in.C) + "->" + std::to_string(half);
-            void* ps = aru_prof_begin(g->backbone, k.in.bf ? "fmap_conv1x1_kernel<true>" : "fmap_conv1x1_kernel<false>", det.c_str(), k.fl1, k.io1 + k.w1);
+            ProfiledLaunch pl(g, k.in.bf ? "fmap_conv1x1_kernel<true>" : "fmap_conv1x1_kernel<false>", where + " " + std::to_string(k.in.C) + "->" + std::to_string(half), k.fl1, k.io1 + k.w1);
             if (k.in.bf) hipLaunchKernelGGL(fmap_conv1x1_kernel<true>, dim3((unsigned)((k.n1 + 255) / 256)), dim3(256), 0, s, a);
             else hipLaunchKernelGGL(fmap_conv1x1_kernel<false>, dim3((unsigned)((k.n1 + 255) / 256)), dim3(256), 0, s, a);
-            aru_prof_end(ps);
         }
         {
-            const std::string det = where + " " + std::to_string(half) + "->" + std::to_string(G.depth) + " s" + std::to_string(G.stride);
-            void* ps = aru_prof_begin(g->backbone, "fmap_conv3x3_kernel", det.c_str(), k.fl3, k.io3 + k.w3);
+            ProfiledLaunch pl(g, "fmap_conv3x3_kernel", where + " " + std::to_string(half) + "->" + std::to_string(G.depth) + " s" + std::to_string(G.stride), k.fl3, k.io3 + k.w3);
             hipLaunchKernelGGL(fmap_conv3x3_kernel, dim3((unsigned)((k.n2 + 255) / 256)), dim3(256), 0, s, c);
-            aru_prof_end(ps);
         }
         g->fmap_last[i] = map_ref(c.out, k.out);
     }
@@ -681,11 +697,17 @@ RoiArgs roi_entry(const asep_gnn::FmapRef& m, const float* regions, int P, const
     return a;
 }
 
+// the fed columns of a side: d_fed [rows, fed] -> the first columns of d_out [rows, stride].  The per-page schedule queues this in front of the
+// page's ROI kernels, the table schedule behind its ROI launch (disjoint columns: the results do not depend on the order)
+void copy_fed_cols(const RoiSide& sd, int rows, const float* d_fed, float* d_out, hipStream_t s) {
+    if (sd.fed > 0) hipLaunchKernelGGL(gnn_copy_cols_kernel, dim3(cdiv(rows * sd.fed, 256)), dim3(256), 0, s, d_fed, rows, sd.fed, d_out, sd.stride);
+}
+
 // one side of one page from the maps "<prefix>..." of the forward that is queued on s: d_fed [rows, fed] -> d_out [rows, stride]
 int visual_rois_dev(asep_gnn* g, const RoiSide& sd, int rows, const float* d_fed, const std::string& prefix, const float* d_reg, int P,
                     const int32_t* d_np, float* d_out, hipStream_t s) {
     if (rows < 1) return ASEP_OK;
-    if (sd.fed > 0) hipLaunchKernelGGL(gnn_copy_cols_kernel, dim3(cdiv(rows * sd.fed, 256)), dim3(256), 0, s, d_fed, rows, sd.fed, d_out, sd.stride);
+    copy_fed_cols(sd, rows, d_fed, d_out, s);
     int col = sd.fed;
     for (size_t i = 0; i < g->vis_names.size(); ++i) {
         asep_gnn::FmapRef m{};                              // (a bf16 backbone, compute_dtype 1, hands over bf16 maps)
@@ -701,6 +723,20 @@ int visual_rois_dev(asep_gnn* g, const RoiSide& sd, int rows, const float* d_fed
     return ASEP_OK;
 }
 
+// The graph of one page whose features are in place: its node rows at *d_u and, where the model has interaction visual features and the page
+// interactions, its edge rows at *d_efc (the fed edge features otherwise).  Both cursors move on to the next page's rows.
+int visual_graph_dev(asep_gnn* g, const asep_gnn_page& q, float** d_u, float** d_efc, hipStream_t s) {
+    const float* d_ef = q.d_edge_feat;
+    if (g->vise_total > 0 && q.E > 0) {
+        d_ef = *d_efc;
+        *d_efc += (size_t)q.E * g->Ed;
+    }
+    int rc = forward_impl(g, g->pool, q.N, q.E, q.d_edges, *d_u, d_ef, q.R, q.d_relations, q.d_probs_out, s);
+    if (rc) return rc;
+    *d_u += (size_t)q.N * g->Uin;
+    return ASEP_OK;
+}
+
 // Everything of one page behind its backbone forward, queued on s: generated maps, ROI max + compression of nodes and interactions, the graph.
 // The page's rows go to *d_u (and *d_efc), which move on to the next page's.
 int visual_page_dev(asep_gnn* g, const asep_gnn_page& q, const std::string& prefix, int P, float** d_u, float** d_efc, hipStream_t s) {
@@ -709,16 +745,42 @@ int visual_page_dev(asep_gnn* g, const asep_gnn_page& q, const std::string& pref
     if (rc) return rc;
     rc = visual_rois_dev(g, node_side(g), q.N, q.d_node_feat, prefix, q.d_regions, P, q.d_num_points, *d_u, s);
     if (rc) return rc;
-    const float* d_ef = q.d_edge_feat;
     if (g->vise_total > 0 && q.E > 0) {
         rc = visual_rois_dev(g, edge_side(g), q.E, q.d_edge_feat, prefix, q.d_edge_regions, P, q.d_edge_num_points, *d_efc, s);
         if (rc) return rc;
-        d_ef = *d_efc;
-        *d_efc += (size_t)q.E * g->Ed;
     }
-    rc = forward_impl(g, g->pool, q.N, q.E, q.d_edges, *d_u, d_ef, q.R, q.d_relations, q.d_probs_out, s);
+    return visual_graph_dev(g, q, d_u, d_efc, s);
+}
+
+// The body of asep_gnn_forward_visual_dev (one page; name_pages = false: its messages name no page) and asep_gnn_forward_visual_batch_dev
+// (pages of ONE size): ONE grouped backbone forward for all pages (every layer is one launch over the page list), then per page the generated
+// maps, the ROI kernels and the graph, queued back to back on the same stream.  h, w and P are checked in front of the pages, and the buffers
+// are reserved in front of the backbone forward.
+int visual_uniform_impl(asep_gnn* g, const char* fn, int n_pages, const asep_gnn_page* pages, int h, int w, int P, hipStream_t s, bool name_pages) {
+    if (!g || !g->backbone) { set_error("%s: no backbone attached", fn); return ASEP_ERR_ARG; }
+    if (n_pages < 1 || !pages || h < 1 || w < 1 || P < 1) { set_error("%s: bad argument", fn); return ASEP_ERR_ARG; }
+    size_t nu = 0, nef = 0;
+    for (int b = 0; b < n_pages; ++b) {
+        if (int rc = check_visual_page(g, fn, name_pages ? b : -1, pages[b], true)) return rc;
+        nu += (size_t)pages[b].N * g->Uin;
+        if (g->vise_total > 0) nef += (size_t)pages[b].E * g->Ed;
+    }
+    g->vis_pool.begin();
+    const int ncls = std::max(1, aru_num_classes(g->backbone));
+    std::vector<const float*> imgs(n_pages); std::vector<float*> outs(n_pages);
+    for (int b = 0; b < n_pages; ++b) {
+        imgs[b] = pages[b].d_image;
+        outs[b] = (float*)g->vis_pool.get((size_t)h * w * ncls * sizeof(float));      // backbone logits (not used by the graph)
+    }
+    int rc = reserve_floats(&g->d_u_cat, &g->u_cat_cap, nu);
+    if (!rc && nef) rc = reserve_floats(&g->d_ef_cat, &g->ef_cat_cap, nef);
     if (rc) return rc;
-    *d_u += (size_t)q.N * g->Uin;
+    // (one page through the batch entry is the single entry's forward: both hand the same one-page list to the backbone's forward_lanes)
+    rc = asep_aru_forward_batch_dev(g->backbone, n_pages, imgs.data(), h, w, outs.data(), nullptr, nullptr, 0.f, s);
+    if (rc) return rc;
+    float *d_u = g->d_u_cat, *d_efc = g->d_ef_cat;
+    for (int b = 0; b < n_pages; ++b)
+        if ((rc = visual_page_dev(g, pages[b], page_prefix(b), P, &d_u, &d_efc, s))) return rc;
     return ASEP_OK;
 }
 
@@ -989,16 +1051,16 @@ int asep_gnn_attach_backbone_maps(asep_gnn* g, asep_aru* backbone, int n_maps, c
     ASEP_GUARD_BEGIN
     if (!g || !backbone || n_maps < 1 || !endpoint_names) { set_error("asep_gnn_attach_backbone: bad argument"); return ASEP_ERR_ARG; }
     g->free_visual();                                   // a second attach replaces (and frees) the first one's uploads
+    struct Undo { asep_gnn* g; ~Undo() { if (g) g->free_visual(); } } undo{g};   // every refusal below frees what was uploaded so far
     std::string base;                                   // feature_map_generators.py:133,147: the last from_layer that had depth -1
     for (int i = 0; i < n_maps; ++i) {
-        if (!endpoint_names[i]) { set_error("asep_gnn_attach_backbone: null end-point name"); g->free_visual(); return ASEP_ERR_ARG; }
+        if (!endpoint_names[i]) { set_error("asep_gnn_attach_backbone: null end-point name"); return ASEP_ERR_ARG; }
         const int depth = layer_depths ? layer_depths[i] : -1;
         const bool named = endpoint_names[i][0] != 0;
         int C = named ? aru_endpoint_channels(backbone, endpoint_names[i]) : 0;
         if (named && (C < 1 || C > 256)) {
             set_error("asep_gnn_attach_backbone: '%s' is not a feature map of this backbone (only unet conv/deconv "
                       "end points are supported)", endpoint_names[i]);
-            g->free_visual();
             return ASEP_ERR_UNSUPPORTED;
         }
         asep_gnn::FmapGen G{};
@@ -1006,7 +1068,6 @@ int asep_gnn_attach_backbone_maps(asep_gnn* g, asep_aru* backbone, int n_maps, c
             if (!named) {
                 set_error("asep_gnn_attach_backbone_maps: map %d has an empty from_layer and layer_depth -1: an empty from_layer builds a new map "
                           "and needs its depth (feature_map_generators.py:145-155)", i);
-                g->free_visual();
                 return ASEP_ERR_ARG;
             }
             base = endpoint_names[i];
@@ -1014,13 +1075,11 @@ int asep_gnn_attach_backbone_maps(asep_gnn* g, asep_aru* backbone, int n_maps, c
             if (!named && i == 0) {
                 set_error("asep_gnn_attach_backbone_maps: map 0 has an empty from_layer: there is no previous feature map to shrink "
                           "(feature_map_generators.py:154)");
-                g->free_visual();
                 return ASEP_ERR_ARG;
             }
             if (depth < 2 || depth % 2 != 0 || depth > 256) {
                 set_error("asep_gnn_attach_backbone_maps: map %d has layer_depth %d: an even depth from 2 to 256 is served (layer_depth / 2 is the "
                           "width of the 1x1 convolution, feature_map_generators.py:159-160)", i, depth);
-                g->free_visual();
                 return depth > 256 ? ASEP_ERR_UNSUPPORTED : ASEP_ERR_ARG;
             }
             G.depth = depth;
@@ -1033,57 +1092,36 @@ int asep_gnn_attach_backbone_maps(asep_gnn* g, asep_aru* backbone, int n_maps, c
             if (!rc) rc = upload_named(g->vis_owned, g->vis_blob, n1 + "biases", {depth / 2}, &G.b1);
             if (!rc) rc = upload_named(g->vis_owned, g->vis_blob, n2 + "weights", {3, 3, depth / 2, depth}, &G.W2);
             if (!rc) rc = upload_named(g->vis_owned, g->vis_blob, n2 + "biases", {depth}, &G.b2);
-            if (rc) { g->free_visual(); return rc; }
+            if (rc) { return rc; }
             C = depth;
             ++g->n_generated;
         }
         g->vis_gen.push_back(G);
-        const std::string scope = "visual_node_feature_compression_fm_" + std::to_string(i) + "/dense/";
-        auto w = g->vis_blob.find(scope + "weights"), b = g->vis_blob.find(scope + "bias");
-        if (w == g->vis_blob.end() || b == g->vis_blob.end()) { set_error("weights: missing tensor %sweights|bias", scope.c_str()); g->free_visual(); return ASEP_ERR_WEIGHTS; }
-        if (w->second.dims.size() != 2 || w->second.dims[0] != C || b->second.dims.size() != 1 || b->second.dims[0] != w->second.dims[1]) {
-            set_error("weights: %sweights must be [%d, d] with a matching bias", scope.c_str(), C);
-            g->free_visual();
-            return ASEP_ERR_WEIGHTS;
-        }
-        float *dW = nullptr, *db = nullptr;
-        int rc = upload_named(g->vis_owned, g->vis_blob, scope + "weights", w->second.dims, &dW);
-        if (!rc) rc = upload_named(g->vis_owned, g->vis_blob, scope + "bias", b->second.dims, &db);
-        if (rc) { g->free_visual(); return rc; }
+        float *dW = nullptr, *db = nullptr; int d = 0;
+        if (int rc = upload_compression(g, "visual_node_feature_compression_fm_" + std::to_string(i) + "/dense/", C, &dW, &db, &d)) { return rc; }
         g->vis_names.push_back(endpoint_names[i]);
         g->vis_W.push_back(dW); g->vis_b.push_back(db);
-        g->vis_C.push_back(C); g->vis_d.push_back(w->second.dims[1]);
-        g->vis_total += w->second.dims[1];
+        g->vis_C.push_back(C); g->vis_d.push_back(d);
+        g->vis_total += d;
     }
     if (g->cfg.visual_edge_dims > 0) {                     // assign_visual_features_to_edges: one compression layer per feature map
         for (int i = 0; i < n_maps; ++i) {
-            const std::string scope = "visual_edge_feature_compression_fm_" + std::to_string(i) + "/dense/";
-            auto w = g->vis_blob.find(scope + "weights"), b = g->vis_blob.find(scope + "bias");
-            if (w == g->vis_blob.end() || b == g->vis_blob.end()) { set_error("weights: missing tensor %sweights|bias", scope.c_str()); g->free_visual(); return ASEP_ERR_WEIGHTS; }
-            if (w->second.dims.size() != 2 || w->second.dims[0] != g->vis_C[i] || b->second.dims.size() != 1 || b->second.dims[0] != w->second.dims[1]) {
-                set_error("weights: %sweights must be [%d, d] with a matching bias", scope.c_str(), g->vis_C[i]);
-                g->free_visual();
-                return ASEP_ERR_WEIGHTS;
-            }
-            float *dW = nullptr, *db = nullptr;
-            int rc = upload_named(g->vis_owned, g->vis_blob, scope + "weights", w->second.dims, &dW);
-            if (!rc) rc = upload_named(g->vis_owned, g->vis_blob, scope + "bias", b->second.dims, &db);
-            if (rc) { g->free_visual(); return rc; }
-            g->vise_W.push_back(dW); g->vise_b.push_back(db); g->vise_d.push_back(w->second.dims[1]);
-            g->vise_total += w->second.dims[1];
+            float *dW = nullptr, *db = nullptr; int d = 0;
+            if (int rc = upload_compression(g, "visual_edge_feature_compression_fm_" + std::to_string(i) + "/dense/", g->vis_C[i], &dW, &db, &d)) { return rc; }
+            g->vise_W.push_back(dW); g->vise_b.push_back(db); g->vise_d.push_back(d);
+            g->vise_total += d;
         }
         if (g->vise_total != g->cfg.visual_edge_dims) {
             set_error("asep_gnn_attach_backbone: the visual edge compression layers are %d wide in all, cfg.visual_edge_dims says %d", g->vise_total,
                       g->cfg.visual_edge_dims);
-            g->free_visual();
             return ASEP_ERR_ARG;
         }
     }
     if (g->vis_total >= g->Uin + 1) {
         set_error("asep_gnn_attach_backbone: %d visual dims exceed the fed node feature width %d", g->vis_total, g->Uin);
-        g->free_visual();
         return ASEP_ERR_ARG;
     }
+    undo.g = nullptr;
     g->backbone = backbone;
     return ASEP_OK;
     ASEP_GUARD_END
@@ -1105,60 +1143,15 @@ int asep_gnn_forward_visual_dev(asep_gnn* g, int N, int E, const int32_t* d_edge
                                 const int32_t* d_num_points, const float* d_edge_regions, const int32_t* d_edge_num_points,
                                 int R, const int32_t* d_relations, float* d_probs_out, void* stream) {
     ASEP_GUARD_BEGIN
-    const char* fn = "asep_gnn_forward_visual_dev";
-    if (!g || !g->backbone) { set_error("%s: no backbone attached", fn); return ASEP_ERR_ARG; }
-    if (h < 1 || w < 1 || P < 1) { set_error("%s: bad argument", fn); return ASEP_ERR_ARG; }
     const asep_gnn_page q{N, E, R, d_edges, d_node_feat, d_edge_feat, d_image, d_regions, d_num_points, d_edge_regions, d_edge_num_points,
                           d_relations, d_probs_out};
-    int rc = check_visual_page(g, fn, -1, q, true);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    g->vis_pool.begin();
-    const int ncls = std::max(1, aru_num_classes(g->backbone));
-    float* d_bo = (float*)g->vis_pool.get((size_t)h * w * ncls * sizeof(float));   // backbone logits (not used by the graph)
-    rc = reserve_floats(&g->d_u_cat, &g->u_cat_cap, (size_t)N * g->Uin);
-    if (!rc && g->vise_total > 0 && E > 0) rc = reserve_floats(&g->d_ef_cat, &g->ef_cat_cap, (size_t)E * g->Ed);
-    if (rc) return rc;
-    rc = asep_aru_forward_dev(g->backbone, d_image, h, w, d_bo, nullptr, nullptr, 0.f, s);
-    if (rc) return rc;
-    float* d_u = g->d_u_cat;
-    float* d_efc = g->d_ef_cat;
-    return visual_page_dev(g, q, std::string(), P, &d_u, &d_efc, s);
+    return visual_uniform_impl(g, "asep_gnn_forward_visual_dev", 1, &q, h, w, P, (hipStream_t)stream, /*name_pages=*/false);
     ASEP_GUARD_END
 }
 
 int asep_gnn_forward_visual_batch_dev(asep_gnn* g, int n_pages, const asep_gnn_page* pages, int h, int w, int P, void* stream) {
     ASEP_GUARD_BEGIN
-    const char* fn = "asep_gnn_forward_visual_batch_dev";
-    if (!g || !g->backbone) { set_error("%s: no backbone attached", fn); return ASEP_ERR_ARG; }
-    if (n_pages < 1 || !pages || h < 1 || w < 1 || P < 1) { set_error("%s: bad argument", fn); return ASEP_ERR_ARG; }
-    size_t nu = 0, nef = 0;
-    for (int b = 0; b < n_pages; ++b) {
-        if (int rc = check_visual_page(g, fn, b, pages[b], true)) return rc;
-        nu += (size_t)pages[b].N * g->Uin;
-        if (g->vise_total > 0) nef += (size_t)pages[b].E * g->Ed;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    g->vis_pool.begin();
-    const int ncls = std::max(1, aru_num_classes(g->backbone));
-    std::vector<const float*> imgs(n_pages);
-    std::vector<float*> outs(n_pages);
-    for (int b = 0; b < n_pages; ++b) {
-        imgs[b] = pages[b].d_image;
-        outs[b] = (float*)g->vis_pool.get((size_t)h * w * ncls * sizeof(float));      // backbone logits (not used by the graph)
-    }
-    int rc = reserve_floats(&g->d_u_cat, &g->u_cat_cap, nu);
-    if (!rc && nef) rc = reserve_floats(&g->d_ef_cat, &g->ef_cat_cap, nef);
-    if (rc) return rc;
-    // ONE grouped backbone forward for all pages (every layer is one launch over the page list), then per page the generated maps, the ROI
-    // kernels and the graph -- the single-page call's launches -- queued back to back on the same stream
-    rc = asep_aru_forward_batch_dev(g->backbone, n_pages, imgs.data(), h, w, outs.data(), nullptr, nullptr, 0.f, s);
-    if (rc) return rc;
-    float* d_u = g->d_u_cat;
-    float* d_efc = g->d_ef_cat;
-    for (int b = 0; b < n_pages; ++b)
-        if ((rc = visual_page_dev(g, pages[b], page_prefix(b), P, &d_u, &d_efc, s))) return rc;
-    return ASEP_OK;
+    return visual_uniform_impl(g, "asep_gnn_forward_visual_batch_dev", n_pages, pages, h, w, P, (hipStream_t)stream, /*name_pages=*/true);
     ASEP_GUARD_END
 }
 
@@ -1207,183 +1200,150 @@ int tables_read(asep_gnn::TableSlot* t, hipStream_t s) {
 
 struct ScanIn { const uint8_t* d_scan; int H, W, C; };
 
-int visual_batch2_impl(asep_gnn* g, const char* fn, int n_pages, std::vector<asep_gnn_page>& pages, const ScanIn* scans, const int32_t* h,
-                       const int32_t* w, int P, hipStream_t s);
+// ---- the table schedule (asep_gnn_forward_visual_batch_dev2 / _u8_dev) as stages.  Each stage below reads and fills the call's plan: the
+//      page list, the sizes and the addresses carved so far.  visual_batch2_impl runs them in order and stops at the first that fails ----
+struct GenMap { int page; size_t map; const float* src; float* mid; };   // a generated (page, map) pair: the end point its 1x1 reads (if it reads one), the 1x1's output
+struct FmapLaunch { size_t pages1 = 0, begin1 = 0, pages3 = 0, begin3 = 0; int grid1 = 0, grid3 = 0; bool bf = false; double fl1 = 0, by1 = 0, fl3 = 0, by3 = 0; };
+struct RoiLaunch { std::vector<RoiArgs> e; std::vector<size_t> rows; size_t eoff = 0, boff = 0; int grid = 0; };
+struct TablePlan {
+    // the call: scans = the u8 entry's, or nullptr (then table_arenas fills in the pages' d_image)
+    const char* fn; int n_pages; std::vector<asep_gnn_page>& pages; const ScanIn* scans; const int32_t *h, *w; int P; hipStream_t s;
+    int ncls = 1, chans = 1; size_t n_maps = 0, nu = 0, nef = 0; std::vector<size_t> logit_items;                          // table_checks
+    bool mvn = false; std::vector<size_t> img_items, mom_items, mom_off; double* d_mom = nullptr;                        // table_arenas
+    std::vector<const float*> imgs; std::vector<float*> outs;
+    std::vector<asep_gnn::PageRec> recs; std::vector<std::vector<FmapStep>> plans;                                       // table_map_plan
+    std::vector<GenMap> gen;                                                                                             // (page by page, a page's maps in order)
+    TableBlob blob; std::vector<FmapLaunch> fl; RoiLaunch roi[2];               // table_build_fmaps, table_build_rois; roi[0] fp32 maps, [1] bf16 maps
+};
 
-}  // namespace
-
-extern "C" {
-
-// ABI 9: asep_gnn_forward_visual_batch_dev for pages of DIFFERENT image sizes.  One launch per call, over a page table in device memory, for:
-// the resize of uint8 scans (the u8 entry), the per-image moments of the backbone's standardisation, the two convolutions of each generated
-// map, ROI max + compression of all node and interaction regions.  The backbones run as one grouped forward over the page list
-// (asep_aru_forward_batch_dev2's launches), the graphs page by page as before.  The kernels' bodies are the single-page ones.
-namespace {
-int batch2_head_checks(asep_gnn* g, const char* fn, int n_pages, const void* pages, const int32_t* h, const int32_t* w) {
-    if (!g || !g->backbone) { set_error("%s: no backbone attached", fn); return ASEP_ERR_ARG; }
-    if (n_pages < 1) { set_error("%s: n_pages = %d, at least one page is needed", fn, n_pages); return ASEP_ERR_ARG; }
-    if (!pages) { set_error("%s: pages is NULL", fn); return ASEP_ERR_ARG; }
-    if (!h || !w) { set_error("%s: the size array %s is NULL (page 0 and every other page need h[b] x w[b])", fn, !h ? "h" : "w"); return ASEP_ERR_ARG; }
-    return ASEP_OK;
-}
-}  // namespace
-
-int asep_gnn_forward_visual_batch_dev2(asep_gnn* g, int n_pages, const asep_gnn_page* pages, const int32_t* h, const int32_t* w, int P,
-                                       void* stream) {
-    ASEP_GUARD_BEGIN
-    const char* fn = "asep_gnn_forward_visual_batch_dev2";
-    if (int rc = batch2_head_checks(g, fn, n_pages, pages, h, w)) return rc;
-    std::vector<asep_gnn_page> pg(pages, pages + n_pages);
-    return visual_batch2_impl(g, fn, n_pages, pg, nullptr, h, w, P, (hipStream_t)stream);
-    ASEP_GUARD_END
-}
-
-int asep_gnn_forward_visual_batch_u8_dev(asep_gnn* g, int n_pages, const asep_gnn_page_u8* pages, const int32_t* h, const int32_t* w, int P,
-                                         void* stream) {
-    ASEP_GUARD_BEGIN
-    const char* fn = "asep_gnn_forward_visual_batch_u8_dev";
-    if (int rc = batch2_head_checks(g, fn, n_pages, pages, h, w)) return rc;
-    std::vector<asep_gnn_page> pg(n_pages);
-    std::vector<ScanIn> scans(n_pages);
-    for (int b = 0; b < n_pages; ++b) {
-        pg[b] = pages[b].page;
-        scans[b] = ScanIn{pages[b].d_scan, pages[b].src_h, pages[b].src_w, pages[b].src_c};
-    }
-    return visual_batch2_impl(g, fn, n_pages, pg, scans.data(), h, w, P, (hipStream_t)stream);
-    ASEP_GUARD_END
-}
-
-}  // extern "C"
-
-namespace {
-
-int visual_batch2_impl(asep_gnn* g, const char* fn, int n_pages, std::vector<asep_gnn_page>& pages, const ScanIn* scans, const int32_t* h,
-                       const int32_t* w, int P, hipStream_t s) {
-    if (P < 1) { set_error("%s: P = %d region points", fn, P); return ASEP_ERR_ARG; }
-    const int ug = g->Uin - g->vis_total, U = g->Uin, Ed = g->Ed;
-    const int ncls = std::max(1, aru_num_classes(g->backbone)), chans = std::max(1, aru_input_channels(g->backbone));
-    const size_t n_maps = g->vis_names.size();
-    std::vector<size_t> logit_items(n_pages);
-    size_t nu = 0, nef = 0;
-    for (int b = 0; b < n_pages; ++b) {
-        const asep_gnn_page& q = pages[b];
-        if (h[b] < 1 || w[b] < 1) { set_error("%s: page %d has the size %d x %d, both sides must be positive", fn, b, h[b], w[b]); return ASEP_ERR_ARG; }
-        if (scans) {
-            const ScanIn& sc = scans[b];
-            if (!sc.d_scan || sc.H < 1 || sc.W < 1 || (size_t)sc.H * sc.W > 0x7fffffffull || (size_t)h[b] * w[b] > 0x7fffffffull) {
-                set_error("%s: page %d: the scan is NULL or its size %d x %d (target %d x %d) is not served", fn, b, sc.H, sc.W, h[b], w[b]);
+int table_checks(const asep_gnn* g, TablePlan& p) {
+    const char* fn = p.fn;
+    if (p.P < 1) { set_error("%s: P = %d region points", fn, p.P); return ASEP_ERR_ARG; }
+    p.ncls = std::max(1, aru_num_classes(g->backbone));
+    p.chans = std::max(1, aru_input_channels(g->backbone));
+    p.n_maps = g->vis_names.size();
+    p.logit_items.resize(p.n_pages);
+    for (int b = 0; b < p.n_pages; ++b) {
+        const asep_gnn_page& q = p.pages[b];
+        const int h = p.h[b], w = p.w[b];
+        if (h < 1 || w < 1) { set_error("%s: page %d has the size %d x %d, both sides must be positive", fn, b, h, w); return ASEP_ERR_ARG; }
+        if (p.scans) {
+            const ScanIn& sc = p.scans[b];
+            if (!sc.d_scan || sc.H < 1 || sc.W < 1 || (size_t)sc.H * sc.W > 0x7fffffffull || (size_t)h * w > 0x7fffffffull) {
+                set_error("%s: page %d: the scan is NULL or its size %d x %d (target %d x %d) is not served", fn, b, sc.H, sc.W, h, w);
                 return ASEP_ERR_ARG;
             }
-            if (!(sc.C == chans || (sc.C == 3 && chans == 1))) {   // 3 -> 1 is Pillow's luma per tap; 1 -> 3 has no meaning
-                set_error("%s: page %d: the scan has %d image channel(s), the backbone takes %d", fn, b, sc.C, chans);
+            if (!(sc.C == p.chans || (sc.C == 3 && p.chans == 1))) {   // 3 -> 1 is Pillow's luma per tap; 1 -> 3 has no meaning
+                set_error("%s: page %d: the scan has %d image channel(s), the backbone takes %d", fn, b, sc.C, p.chans);
                 return ASEP_ERR_ARG;
             }
         }
-        if (int rc = check_visual_page(g, fn, b, q, !scans)) return rc;
+        if (int rc = check_visual_page(g, fn, b, q, !p.scans)) return rc;
         if ((size_t)q.N * q.N > (size_t)1 << 30) { set_error("%s: page %d: N=%d too large for the dense edge table", fn, b, q.N); return ASEP_ERR_UNSUPPORTED; }
-        logit_items[b] = (size_t)h[b] * w[b] * ncls;
-        nu += (size_t)q.N * U;
-        if (g->vise_total > 0) nef += (size_t)q.E * Ed;
+        p.logit_items[b] = (size_t)h * w * p.ncls;
+        p.nu += (size_t)q.N * g->Uin;
+        if (g->vise_total > 0) p.nef += (size_t)q.E * g->Ed;
     }
-    // arenas: ONE buffer each for the pages' logits, node features, edge features and generated maps, carved per page.  Each keeps the largest
-    // sum it has served, so a call whose page mix changes allocates only when its sum is a new maximum
-    std::vector<size_t> off;
-    const size_t logit_total = arena_offsets(logit_items.data(), n_pages, 64, off);
+    return ASEP_OK;
+}
+
+// arenas: ONE buffer each for the pages' logits, node features, edge features and generated maps, carved per page.  Each keeps the largest
+// sum it has served, so a call whose page mix changes allocates only when its sum is a new maximum
+int table_arenas(asep_gnn* g, TablePlan& p) {
+    const int n = p.n_pages;
+    std::vector<size_t> off, img_off;
+    const size_t logit_total = arena_offsets(p.logit_items.data(), n, 64, off);
     g->vis_pool.begin();
     float* d_logits = (float*)g->vis_pool.get(logit_total * sizeof(float));
     // (the same three requests in the same order whatever the call needs, so that a buffer keeps its role from call to call)
-    const bool mvn = aru_mvn(g->backbone);
-    std::vector<size_t> img_items(n_pages), img_off, mom_items(n_pages), mom_off;
-    for (int b = 0; b < n_pages; ++b) {
-        img_items[b] = (size_t)h[b] * w[b] * chans;
-        mom_items[b] = 2 * (size_t)moments_parts(img_items[b]) + 2;          // doubles: the partial pairs, then room for {mean, 1 / sd}
+    p.mvn = aru_mvn(g->backbone);
+    p.img_items.resize(n); p.mom_items.resize(n);
+    for (int b = 0; b < n; ++b) {
+        p.img_items[b] = (size_t)p.h[b] * p.w[b] * p.chans;
+        p.mom_items[b] = 2 * (size_t)moments_parts(p.img_items[b]) + 2;      // doubles: the partial pairs, then room for {mean, 1 / sd}
     }
-    const size_t img_total = scans ? arena_offsets(img_items.data(), n_pages, 64, img_off) : 0;
-    const size_t mom_total = mvn ? arena_offsets(mom_items.data(), n_pages, 2, mom_off) : 0;
+    const size_t img_total = p.scans ? arena_offsets(p.img_items.data(), n, 64, img_off) : 0;
+    const size_t mom_total = p.mvn ? arena_offsets(p.mom_items.data(), n, 2, p.mom_off) : 0;
     float* d_images = (float*)g->vis_pool.get(img_total * sizeof(float));
-    double* d_mom = (double*)g->vis_pool.get(mom_total * sizeof(double));
+    p.d_mom = (double*)g->vis_pool.get(mom_total * sizeof(double));
     g->batch_images.clear();
-    if (scans)
-        for (int b = 0; b < n_pages; ++b) {
-            pages[b].d_image = d_images + img_off[b];
-            g->batch_images.push_back(asep_gnn::FmapRef{pages[b].d_image, h[b], w[b], chans, 0});
+    if (p.scans)
+        for (int b = 0; b < n; ++b) {
+            p.pages[b].d_image = d_images + img_off[b];
+            g->batch_images.push_back(asep_gnn::FmapRef{p.pages[b].d_image, p.h[b], p.w[b], p.chans, 0});
         }
-    std::vector<const float*> imgs(n_pages);
-    std::vector<float*> outs(n_pages);
-    for (int b = 0; b < n_pages; ++b) { imgs[b] = pages[b].d_image; outs[b] = d_logits + off[b]; }
-    int rc = reserve_floats(&g->d_u_cat, &g->u_cat_cap, nu);
-    if (!rc && nef) rc = reserve_floats(&g->d_ef_cat, &g->ef_cat_cap, nef);
-    if (rc) return rc;
+    p.imgs.resize(n); p.outs.resize(n);
+    for (int b = 0; b < n; ++b) { p.imgs[b] = p.pages[b].d_image; p.outs[b] = d_logits + off[b]; }
+    int rc = reserve_floats(&g->d_u_cat, &g->u_cat_cap, p.nu);
+    if (!rc && p.nef) rc = reserve_floats(&g->d_ef_cat, &g->ef_cat_cap, p.nef);
+    return rc;
+}
+
+// in front of the backbone: the scans' resize and the pages' moments, one launch per call each, over one table; then the grouped backbone forward
+int table_backbone(asep_gnn* g, TablePlan& p) {
+    const int n = p.n_pages; hipStream_t s = p.s;
     g->stream = s;
     aru_prof_stream(g->backbone, s);
-    // ---- in front of the backbone: the scans' resize and the pages' moments, one launch per call each ----
-    std::vector<const float*> stats(n_pages, nullptr);
-    if (scans || mvn) {
+    std::vector<const float*> stats(n, nullptr);
+    int rc = ASEP_OK;
+    if (p.scans || p.mvn) {
         TableBlob pre;
         size_t r_pages = 0, r_begin = 0, m_pages = 0, m_begin = 0;
         std::vector<int32_t> rb, mb;
-        if (scans) {
-            std::vector<ResizePage> rp(n_pages);
-            std::vector<size_t> px(n_pages);
-            for (int b = 0; b < n_pages; ++b) {
-                rp[b] = resize_page(scans[b].d_scan, scans[b].H, scans[b].W, scans[b].C, scans[b].C != chans, h[b], w[b], const_cast<float*>(pages[b].d_image));
-                px[b] = (size_t)h[b] * w[b];
+        if (p.scans) {
+            std::vector<ResizePage> rp(n);
+            std::vector<size_t> px(n);
+            for (int b = 0; b < n; ++b) {
+                const ScanIn& sc = p.scans[b];
+                rp[b] = resize_page(sc.d_scan, sc.H, sc.W, sc.C, sc.C != p.chans, p.h[b], p.w[b], const_cast<float*>(p.pages[b].d_image));
+                px[b] = (size_t)p.h[b] * p.w[b];
             }
-            if (!page_unit_table(px.data(), n_pages, 256, rb)) { set_error("%s: the %d pages are too large for one resize launch", fn, n_pages); return ASEP_ERR_UNSUPPORTED; }
+            if (!page_unit_table(px.data(), n, 256, rb)) { set_error("%s: the %d pages are too large for one resize launch", p.fn, n); return ASEP_ERR_UNSUPPORTED; }
             r_pages = pre.add(rp.data(), rp.size()); r_begin = pre.add(rb.data(), rb.size());
         }
-        if (mvn) {
-            std::vector<MomentsPage> mp(n_pages);
-            std::vector<size_t> parts(n_pages);
-            for (int b = 0; b < n_pages; ++b) {
-                double* base = d_mom + mom_off[b];
-                mp[b] = MomentsPage{pages[b].d_image, img_items[b], base, (float*)(base + mom_items[b] - 2), moments_parts(img_items[b])};
+        if (p.mvn) {
+            std::vector<MomentsPage> mp(n);
+            std::vector<size_t> parts(n);
+            for (int b = 0; b < n; ++b) {
+                double* base = p.d_mom + p.mom_off[b];
+                mp[b] = MomentsPage{p.pages[b].d_image, p.img_items[b], base, (float*)(base + p.mom_items[b] - 2), moments_parts(p.img_items[b])};
                 parts[b] = (size_t)mp[b].parts;
                 stats[b] = mp[b].stats;
             }
-            if (!page_unit_table(parts.data(), n_pages, 1, mb)) { set_error("%s: too many pages for one moments launch", fn); return ASEP_ERR_UNSUPPORTED; }
+            if (!page_unit_table(parts.data(), n, 1, mb)) { set_error("%s: too many pages for one moments launch", p.fn); return ASEP_ERR_UNSUPPORTED; }
             m_pages = pre.add(mp.data(), mp.size()); m_begin = pre.add(mb.data(), mb.size());
         }
         asep_gnn::TableSlot* slot = nullptr;
-        rc = put_tables(g, pre, s, &slot);
-        if (rc) return rc;
-        if (scans) {
-            void* ps = aru_prof_begin(g->backbone, "prep_resize_tf1_pages_kernel", (std::to_string(n_pages) + " pages").c_str(), 0.0, 0.0);
-            rc = resize_tf1_pages_launch((const ResizePage*)(slot->d + r_pages), (const int32_t*)(slot->d + r_begin), n_pages, rb[n_pages], s);
-            aru_prof_end(ps);
-            if (rc) return rc;
+        if ((rc = put_tables(g, pre, s, &slot))) return rc;
+        if (p.scans) {
+            ProfiledLaunch pl(g, "prep_resize_tf1_pages_kernel", std::to_string(n) + " pages", 0.0, 0.0);
+            rc = resize_tf1_pages_launch((const ResizePage*)(slot->d + r_pages), (const int32_t*)(slot->d + r_begin), n, rb[n], s);
         }
-        if (mvn) {
-            rc = aru_moments_pages(g->backbone, (const MomentsPage*)(slot->d + m_pages), (const int32_t*)(slot->d + m_begin), n_pages, mb[n_pages], s);
-            if (rc) return rc;
-        }
-        rc = tables_read(slot, s);
         if (rc) return rc;
+        if (p.mvn && (rc = aru_moments_pages(g->backbone, (const MomentsPage*)(slot->d + m_pages), (const int32_t*)(slot->d + m_begin), n, mb[n], s))) return rc;
+        if ((rc = tables_read(slot, s))) return rc;
     }
-    if (mvn) aru_set_page_stats(g->backbone, stats.data());
-    rc = asep_aru_forward_batch_dev2(g->backbone, n_pages, imgs.data(), h, w, outs.data(), nullptr, nullptr, 0.f, s);
+    if (p.mvn) aru_set_page_stats(g->backbone, stats.data());
+    rc = asep_aru_forward_batch_dev2(g->backbone, n, p.imgs.data(), p.h, p.w, p.outs.data(), nullptr, nullptr, 0.f, s);
     aru_set_page_stats(g->backbone, nullptr);
-    if (rc) return rc;
-    g->stream = s;
+    if (!rc) g->stream = s;
+    return rc;
+}
 
-    // ---- every map of every page: the backbone's end points (known once the forward is queued), the generated ones in one arena ----
-    std::vector<asep_gnn::PageRec> recs(n_pages);
-    std::vector<std::vector<FmapStep>> plans(n_pages);
-    std::vector<const float*> src_p((size_t)n_pages * n_maps, nullptr);   // per generated (page, map): the end point its 1x1 reads, if it reads one
-    std::vector<float*> mid(src_p.size(), nullptr);                       // ... and the 1x1's output
+// every map of every page: the backbone's end points (known once the forward is queued), the generated ones in one arena
+int table_map_plan(asep_gnn* g, TablePlan& p) {
+    p.recs.resize(p.n_pages); p.plans.resize(p.n_pages);
     std::vector<size_t> arena_items;                                  // per generated (page, map): the 1x1's output, then the map itself
-    for (int b = 0; b < n_pages; ++b) {
+    for (int b = 0; b < p.n_pages; ++b) {
         std::vector<const float*> end_p;
-        rc = page_map_plan(g, page_prefix(b), plans[b], end_p);
-        if (rc) return rc;
-        recs[b].maps.resize(n_maps);
-        for (size_t i = 0; i < n_maps; ++i) {
-            const FmapStep& k = plans[b][i];
-            recs[b].maps[i] = map_ref(k.generated ? nullptr : end_p[i], k.out);   // (a generated one's address follows below)
+        if (int rc = page_map_plan(g, page_prefix(b), p.plans[b], end_p)) return rc;
+        p.recs[b].maps.resize(p.n_maps);
+        for (size_t i = 0; i < p.n_maps; ++i) {
+            const FmapStep& k = p.plans[b][i];
+            p.recs[b].maps[i] = map_ref(k.generated ? nullptr : end_p[i], k.out);   // (a generated one's address follows below)
             if (!k.generated) continue;
-            src_p[(size_t)b * n_maps + i] = end_p[i];
-            arena_items.push_back(k.n1);
-            arena_items.push_back(k.n2);
+            p.gen.push_back(GenMap{b, i, end_p[i], nullptr});
+            arena_items.push_back(k.n1); arena_items.push_back(k.n2);
         }
     }
     if (g->n_generated) {
@@ -1391,146 +1351,157 @@ int visual_batch2_impl(asep_gnn* g, const char* fn, int n_pages, std::vector<ase
         const size_t total = arena_offsets(arena_items.data(), (int)arena_items.size(), 64, aoff);
         g->fmap_pool.begin();
         float* base = (float*)g->fmap_pool.get(total * sizeof(float));
-        size_t k = 0;
-        for (int b = 0; b < n_pages; ++b)
-            for (size_t i = 0; i < n_maps; ++i) {
-                if (!plans[b][i].generated) continue;
-                mid[(size_t)b * n_maps + i] = base + aoff[k];
-                recs[b].maps[i].p = base + aoff[k + 1];
-                k += 2;
-            }
+        for (size_t k = 0; k < p.gen.size(); ++k) {
+            p.gen[k].mid = base + aoff[2 * k];
+            p.recs[p.gen[k].page].maps[p.gen[k].map].p = base + aoff[2 * k + 1];
+        }
     }
+    return ASEP_OK;
+}
 
-    // ---- the tables: per generated map two (1x1, 3x3), then the regions' entries, fp32 maps and bf16 maps apart ----
-    TableBlob blob;
-    struct FmapLaunch { size_t pages1 = 0, begin1 = 0, pages3 = 0, begin3 = 0; int grid1 = 0, grid3 = 0; bool bf = false; double fl1 = 0, by1 = 0, fl3 = 0, by3 = 0; };
-    std::vector<FmapLaunch> fl(n_maps);
-    for (size_t i = 0; i < n_maps; ++i) {
-        const asep_gnn::FmapGen& G = g->vis_gen[i];
-        if (G.depth < 0) continue;
-        std::vector<FmapPage> p1(n_pages), p3(n_pages);
-        std::vector<size_t> it1(n_pages), it3(n_pages);
-        FmapLaunch& L = fl[i];
-        L.bf = plans[0][i].in.bf != 0;
-        for (int b = 0; b < n_pages; ++b) {
-            const FmapStep& k = plans[b][i];
-            if ((k.in.bf != 0) != L.bf) { set_error("%s: end points of one call differ in precision", fn); return ASEP_ERR_ARG; }
-            float* m1 = mid[(size_t)b * n_maps + i];
-            p1[b] = FmapPage{k.src < 0 ? src_p[(size_t)b * n_maps + i] : recs[b].maps[k.src].p, m1, k.d.ih, k.d.iw, k.d.ih, k.d.iw, 0, 0};
-            p3[b] = FmapPage{m1, const_cast<float*>(recs[b].maps[i].p), k.d.ih, k.d.iw, k.d.oh, k.d.ow, k.d.pad_t, k.d.pad_l};
+// the tables of the generated maps: per map two (1x1, 3x3) over the pages
+int table_build_fmaps(const asep_gnn* g, TablePlan& p) {
+    const int n = p.n_pages;
+    p.fl.resize(p.n_maps);
+    for (size_t i = 0; i < p.n_maps; ++i) {
+        if (g->vis_gen[i].depth < 0) continue;
+        std::vector<FmapPage> p1(n), p3(n);
+        std::vector<size_t> it1(n), it3(n);
+        FmapLaunch& L = p.fl[i];
+        L.bf = p.plans[0][i].in.bf != 0;
+        for (const GenMap& m : p.gen) {                              // map i of every page, in page order
+            if (m.map != i) continue;
+            const int b = m.page;
+            const FmapStep& k = p.plans[b][i];
+            if ((k.in.bf != 0) != L.bf) { set_error("%s: end points of one call differ in precision", p.fn); return ASEP_ERR_ARG; }
+            p1[b] = FmapPage{k.src < 0 ? m.src : p.recs[b].maps[k.src].p, m.mid, k.d.ih, k.d.iw, k.d.ih, k.d.iw, 0, 0};
+            p3[b] = FmapPage{m.mid, const_cast<float*>(p.recs[b].maps[i].p), k.d.ih, k.d.iw, k.d.oh, k.d.ow, k.d.pad_t, k.d.pad_l};
             it1[b] = k.n1; it3[b] = k.n2;
             L.fl1 += k.fl1; L.by1 += k.io1; L.fl3 += k.fl3; L.by3 += k.io3;
         }
-        L.by1 += plans[0][i].w1;                                      // (the filter and bias once per launch)
-        L.by3 += plans[0][i].w3;
+        L.by1 += p.plans[0][i].w1;                                    // (the filter and bias once per launch)
+        L.by3 += p.plans[0][i].w3;
         std::vector<int32_t> b1, b3;
-        if (!page_unit_table(it1.data(), n_pages, 256, b1) || !page_unit_table(it3.data(), n_pages, 256, b3)) {
-            set_error("%s: feature map %zu of the %d pages is too large for one launch", fn, i, n_pages);
+        if (!page_unit_table(it1.data(), n, 256, b1) || !page_unit_table(it3.data(), n, 256, b3)) {
+            set_error("%s: feature map %zu of the %d pages is too large for one launch", p.fn, i, n);
             return ASEP_ERR_UNSUPPORTED;
         }
-        L.grid1 = b1[n_pages]; L.grid3 = b3[n_pages];
-        L.pages1 = blob.add(p1.data(), p1.size()); L.begin1 = blob.add(b1.data(), b1.size());
-        L.pages3 = blob.add(p3.data(), p3.size()); L.begin3 = blob.add(b3.data(), b3.size());
+        L.grid1 = b1[n]; L.grid3 = b3[n];
+        L.pages1 = p.blob.add(p1.data(), p1.size()); L.begin1 = p.blob.add(b1.data(), b1.size());
+        L.pages3 = p.blob.add(p3.data(), p3.size()); L.begin3 = p.blob.add(b3.data(), b3.size());
     }
-    struct RoiLaunch { std::vector<RoiArgs> e; std::vector<size_t> rows; size_t eoff = 0, boff = 0; int grid = 0; };
-    RoiLaunch roi[2];                                               // [0] fp32 maps, [1] bf16 maps
-    {
-        const RoiSide nodes = node_side(g), edges = edge_side(g);
-        size_t urow = 0, efrow = 0;
-        for (int b = 0; b < n_pages; ++b) {
-            const asep_gnn_page& q = pages[b];
-            recs[b].N = q.N; recs[b].u_off = urow * U;
-            int col = ug, ecol = g->Ed_fed;
-            for (size_t i = 0; i < n_maps; ++i) {
-                const asep_gnn::FmapRef& m = recs[b].maps[i];
-                roi[m.bf ? 1 : 0].e.push_back(roi_entry(m, q.d_regions, P, q.d_num_points, nodes, i, g->d_u_cat + urow * U, col));
-                roi[m.bf ? 1 : 0].rows.push_back((size_t)q.N);
-                col += g->vis_d[i];
-                if (g->vise_total > 0 && q.E > 0) {
-                    roi[m.bf ? 1 : 0].e.push_back(roi_entry(m, q.d_edge_regions, P, q.d_edge_num_points, edges, i, g->d_ef_cat + efrow * Ed, ecol));
-                    roi[m.bf ? 1 : 0].rows.push_back((size_t)q.E);
-                    ecol += g->vise_d[i];
-                }
-            }
-            urow += (size_t)q.N;
-            if (g->vise_total > 0) efrow += (size_t)q.E;
-        }
-        for (RoiLaunch& L : roi) {
-            if (L.e.empty()) continue;
-            std::vector<int32_t> bg;
-            if (!page_unit_table(L.rows.data(), (int)L.rows.size(), 1, bg)) { set_error("%s: too many regions for one launch", fn); return ASEP_ERR_UNSUPPORTED; }
-            L.grid = bg.back();
-            L.eoff = blob.add(L.e.data(), L.e.size());
-            L.boff = blob.add(bg.data(), bg.size());
-        }
-    }
-    asep_gnn::TableSlot* slot2 = nullptr;
-    rc = put_tables(g, blob, s, &slot2);
-    if (rc) return rc;
-    const char* tab = slot2->d;
+    return ASEP_OK;
+}
 
-    // ---- launches: one per stage over all pages ----
-    for (size_t i = 0; i < n_maps; ++i) {
+// the regions' entries, fp32 maps and bf16 maps apart; the pages' rows of d_u_cat into the page records
+int table_build_rois(asep_gnn* g, TablePlan& p) {
+    const RoiSide nodes = node_side(g), edges = edge_side(g);
+    size_t urow = 0, efrow = 0;
+    for (int b = 0; b < p.n_pages; ++b) {
+        const asep_gnn_page& q = p.pages[b];
+        p.recs[b].N = q.N; p.recs[b].u_off = urow * g->Uin;
+        int col = nodes.fed, ecol = edges.fed;
+        for (size_t i = 0; i < p.n_maps; ++i) {
+            const asep_gnn::FmapRef& m = p.recs[b].maps[i];
+            RoiLaunch& L = p.roi[m.bf ? 1 : 0];
+            L.e.push_back(roi_entry(m, q.d_regions, p.P, q.d_num_points, nodes, i, g->d_u_cat + urow * g->Uin, col));
+            L.rows.push_back((size_t)q.N);
+            col += g->vis_d[i];
+            if (g->vise_total > 0 && q.E > 0) {
+                L.e.push_back(roi_entry(m, q.d_edge_regions, p.P, q.d_edge_num_points, edges, i, g->d_ef_cat + efrow * g->Ed, ecol));
+                L.rows.push_back((size_t)q.E);
+                ecol += g->vise_d[i];
+            }
+        }
+        urow += (size_t)q.N;
+        if (g->vise_total > 0) efrow += (size_t)q.E;
+    }
+    for (RoiLaunch& L : p.roi) {
+        if (L.e.empty()) continue;
+        std::vector<int32_t> bg;
+        if (!page_unit_table(L.rows.data(), (int)L.rows.size(), 1, bg)) { set_error("%s: too many regions for one launch", p.fn); return ASEP_ERR_UNSUPPORTED; }
+        L.grid = bg.back();
+        L.eoff = p.blob.add(L.e.data(), L.e.size());
+        L.boff = p.blob.add(bg.data(), bg.size());
+    }
+    return ASEP_OK;
+}
+
+// the tables to the device, then one launch per stage over all pages
+int table_launches(asep_gnn* g, const TablePlan& p) {
+    const int n = p.n_pages; hipStream_t s = p.s;
+    asep_gnn::TableSlot* slot = nullptr;
+    if (int rc = put_tables(g, p.blob, s, &slot)) return rc;
+    const char* tab = slot->d;
+    for (size_t i = 0; i < p.n_maps; ++i) {
         const asep_gnn::FmapGen& G = g->vis_gen[i];
         if (G.depth < 0) continue;
-        const FmapLaunch& L = fl[i];
-        const std::string where = "fm_" + std::to_string(i) + " " + std::to_string(n_pages) + " pages";
+        const FmapLaunch& L = p.fl[i];
+        const std::string where = "fm_" + std::to_string(i) + " " + std::to_string(n) + " pages";
         FmapPagesArgs a{};
-        a.pages = (const FmapPage*)(tab + L.pages1); a.begin = (const int32_t*)(tab + L.begin1); a.n_pages = n_pages;
+        a.pages = (const FmapPage*)(tab + L.pages1); a.begin = (const int32_t*)(tab + L.begin1); a.n_pages = n;
         a.W = G.W1; a.b = G.b1; a.Ci = G.Cin; a.Co = G.depth / 2; a.stride = 1;
         if (L.grid1 > 0) {
-            const std::string det = where + " " + std::to_string(G.Cin) + "->" + std::to_string(G.depth / 2);
-            void* ps = aru_prof_begin(g->backbone, L.bf ? "fmap_conv1x1_pages_kernel<true>" : "fmap_conv1x1_pages_kernel<false>", det.c_str(), L.fl1, L.by1);
+            ProfiledLaunch pl(g, L.bf ? "fmap_conv1x1_pages_kernel<true>" : "fmap_conv1x1_pages_kernel<false>", where + " " + std::to_string(G.Cin) + "->" + std::to_string(G.depth / 2), L.fl1, L.by1);
             if (L.bf) hipLaunchKernelGGL(fmap_conv1x1_pages_kernel<true>, dim3((unsigned)L.grid1), dim3(256), 0, s, a);
             else hipLaunchKernelGGL(fmap_conv1x1_pages_kernel<false>, dim3((unsigned)L.grid1), dim3(256), 0, s, a);
-            aru_prof_end(ps);
         }
         FmapPagesArgs c = a;
         c.pages = (const FmapPage*)(tab + L.pages3); c.begin = (const int32_t*)(tab + L.begin3);
         c.W = G.W2; c.b = G.b2; c.Ci = G.depth / 2; c.Co = G.depth; c.stride = G.stride;
         if (L.grid3 > 0) {
-            const std::string det = where + " " + std::to_string(G.depth / 2) + "->" + std::to_string(G.depth) + " s" + std::to_string(G.stride);
-            void* ps = aru_prof_begin(g->backbone, "fmap_conv3x3_pages_kernel", det.c_str(), L.fl3, L.by3);
+            ProfiledLaunch pl(g, "fmap_conv3x3_pages_kernel", where + " " + std::to_string(G.depth / 2) + "->" + std::to_string(G.depth) + " s" + std::to_string(G.stride), L.fl3, L.by3);
             hipLaunchKernelGGL(fmap_conv3x3_pages_kernel, dim3((unsigned)L.grid3), dim3(256), 0, s, c);
-            aru_prof_end(ps);
         }
     }
     for (int k = 0; k < 2; ++k) {
-        const RoiLaunch& L = roi[k];
+        const RoiLaunch& L = p.roi[k];
         if (L.grid < 1) continue;
         RoiPagesArgs a{(const RoiArgs*)(tab + L.eoff), (const int32_t*)(tab + L.boff), (int)L.e.size()};
-        const std::string det = std::to_string(n_pages) + " pages " + std::to_string(L.e.size()) + " entries " + std::to_string(L.grid) + " regions";
-        void* ps = aru_prof_begin(g->backbone, k ? "gnn_roi_compress_pages_kernel<true>" : "gnn_roi_compress_pages_kernel<false>", det.c_str(), 0.0, 0.0);
+        ProfiledLaunch pl(g, k ? "gnn_roi_compress_pages_kernel<true>" : "gnn_roi_compress_pages_kernel<false>",
+                          std::to_string(n) + " pages " + std::to_string(L.e.size()) + " entries " + std::to_string(L.grid) + " regions", 0.0, 0.0);
         if (k) hipLaunchKernelGGL(gnn_roi_compress_pages_kernel<true>, dim3((unsigned)L.grid), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(gnn_roi_compress_pages_kernel<false>, dim3((unsigned)L.grid), dim3(256), 0, s, a);
-        aru_prof_end(ps);
     }
     ASEP_HIP_CHECK(hipGetLastError());
-    rc = tables_read(slot2, s);
-    if (rc) return rc;
+    return tables_read(slot, s);
+}
 
-    // ---- the graphs, page by page (they batch nothing across pages today: N, E and R differ) ----
-    float* d_u = g->d_u_cat;
-    float* d_efc = g->d_ef_cat;
-    for (int b = 0; b < n_pages; ++b) {
-        const asep_gnn_page& q = pages[b];
-        if (ug > 0) hipLaunchKernelGGL(gnn_copy_cols_kernel, dim3(cdiv(q.N * ug, 256)), dim3(256), 0, s, q.d_node_feat, q.N, ug, d_u, U);
-        const float* d_ef = q.d_edge_feat;
-        if (g->vise_total > 0) {
-            if (q.E > 0) {
-                if (g->Ed_fed > 0) hipLaunchKernelGGL(gnn_copy_cols_kernel, dim3(cdiv(q.E * g->Ed_fed, 256)), dim3(256), 0, s, q.d_edge_feat, q.E, g->Ed_fed, d_efc, Ed);
-                d_ef = d_efc;
-            }
-            d_efc += (size_t)q.E * Ed;
-        }
-        rc = forward_impl(g, g->pool, q.N, q.E, q.d_edges, d_u, d_ef, q.R, q.d_relations, q.d_probs_out, s);
-        if (rc) return rc;
-        d_u += (size_t)q.N * U;
+// the graphs, page by page (they batch nothing across pages today: N, E and R differ); then what the read-backs serve
+int table_graphs(asep_gnn* g, TablePlan& p) {
+    const RoiSide nodes = node_side(g), edges = edge_side(g);
+    float *d_u = g->d_u_cat, *d_efc = g->d_ef_cat;
+    for (int b = 0; b < p.n_pages; ++b) {
+        const asep_gnn_page& q = p.pages[b];
+        copy_fed_cols(nodes, q.N, q.d_node_feat, d_u, p.s);
+        if (g->vise_total > 0 && q.E > 0) copy_fed_cols(edges, q.E, q.d_edge_feat, d_efc, p.s);
+        if (int rc = visual_graph_dev(g, q, &d_u, &d_efc, p.s)) return rc;
     }
-    g->fmap_last = recs[n_pages - 1].maps;                          // as after the old entry: the last page's maps
-    g->fmap_last_prefix = page_prefix(n_pages - 1);
-    g->batch_pages = std::move(recs);
+    g->fmap_last = p.recs[p.n_pages - 1].maps;                      // as after the uniform entry: the last page's maps
+    g->fmap_last_prefix = page_prefix(p.n_pages - 1);
+    g->batch_pages = std::move(p.recs);
     g->batch_serial = g->fwd_serial;
+    return ASEP_OK;
+}
+
+int visual_batch2_impl(asep_gnn* g, TablePlan&& p) {
+    int rc = table_checks(g, p);
+    if (!rc) rc = table_arenas(g, p);
+    if (!rc) rc = table_backbone(g, p);
+    if (!rc) rc = table_map_plan(g, p);
+    if (!rc) rc = table_build_fmaps(g, p);
+    if (!rc) rc = table_build_rois(g, p);
+    if (!rc) rc = table_launches(g, p);
+    if (!rc) rc = table_graphs(g, p);
+    return rc;
+}
+
+// what the two entries check before they copy their page lists
+int batch2_head_checks(asep_gnn* g, const char* fn, int n_pages, const void* pages, const int32_t* h, const int32_t* w) {
+    if (!g || !g->backbone) { set_error("%s: no backbone attached", fn); return ASEP_ERR_ARG; }
+    if (n_pages < 1) { set_error("%s: n_pages = %d, at least one page is needed", fn, n_pages); return ASEP_ERR_ARG; }
+    if (!pages) { set_error("%s: pages is NULL", fn); return ASEP_ERR_ARG; }
+    if (!h || !w) { set_error("%s: the size array %s is NULL (page 0 and every other page need h[b] x w[b])", fn, !h ? "h" : "w"); return ASEP_ERR_ARG; }
     return ASEP_OK;
 }
 
@@ -1544,6 +1515,33 @@ const asep_gnn::PageRec* batch_page(asep_gnn* g, const char* fn, int page) {
 }  // namespace
 
 extern "C" {
+
+// ABI 9: asep_gnn_forward_visual_batch_dev for pages of DIFFERENT image sizes.  One launch per call, over a page table in device memory, for:
+// the resize of uint8 scans (the u8 entry), the per-image moments of the backbone's standardisation, the two convolutions of each generated
+// map, ROI max + compression of all node and interaction regions.  The backbones run as one grouped forward over the page list
+// (asep_aru_forward_batch_dev2's launches), the graphs page by page as before.  The kernels' bodies are the single-page ones.
+int asep_gnn_forward_visual_batch_dev2(asep_gnn* g, int n_pages, const asep_gnn_page* pages, const int32_t* h, const int32_t* w, int P, void* stream) {
+    ASEP_GUARD_BEGIN
+    const char* fn = "asep_gnn_forward_visual_batch_dev2";
+    if (int rc = batch2_head_checks(g, fn, n_pages, pages, h, w)) return rc;
+    std::vector<asep_gnn_page> pg(pages, pages + n_pages);
+    return visual_batch2_impl(g, TablePlan{fn, n_pages, pg, nullptr, h, w, P, (hipStream_t)stream});
+    ASEP_GUARD_END
+}
+
+int asep_gnn_forward_visual_batch_u8_dev(asep_gnn* g, int n_pages, const asep_gnn_page_u8* pages, const int32_t* h, const int32_t* w, int P, void* stream) {
+    ASEP_GUARD_BEGIN
+    const char* fn = "asep_gnn_forward_visual_batch_u8_dev";
+    if (int rc = batch2_head_checks(g, fn, n_pages, pages, h, w)) return rc;
+    std::vector<asep_gnn_page> pg(n_pages);
+    std::vector<ScanIn> scans(n_pages);
+    for (int b = 0; b < n_pages; ++b) {
+        pg[b] = pages[b].page;
+        scans[b] = ScanIn{pages[b].d_scan, pages[b].src_h, pages[b].src_w, pages[b].src_c};
+    }
+    return visual_batch2_impl(g, TablePlan{fn, n_pages, pg, scans.data(), h, w, P, (hipStream_t)stream});
+    ASEP_GUARD_END
+}
 
 int asep_gnn_get_page_node_features(asep_gnn* g, int page, float* out, size_t max_floats) {
     ASEP_GUARD_BEGIN

@@ -7,11 +7,15 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 namespace asep {
 
 constexpr int MAXP = 12;                  // problems of one launch: the p[] of every *Args struct
+
+// the end points of page b of a grouped backbone forward are "<page_prefix(b)><name>": the ARU engine names them, the relation net looks them up
+inline std::string page_prefix(int b) { return b ? "p" + std::to_string(b) + "/" : std::string(); }
 
 // ---- the cut of n problems into launches: chunk c = problems [chunk_begin(c), chunk_end(n, c)) ----
 inline size_t num_chunks(size_t n) { return (n + MAXP - 1) / MAXP; }

@@ -173,9 +173,17 @@ void check_xcd_order() {
     for (int k = 0; k < 32; ++k) CHECK(s[8 * k] == (k / 8) * 8 + k % 8);
 }
 
+// the one spelling of a page's end-point prefix that both engines use: page 0 has none
+void check_page_prefix() {
+    CHECK(page_prefix(0) == "");
+    CHECK(page_prefix(1) == "p1/");
+    CHECK(page_prefix(12) == "p12/");
+}
+
 }  // namespace
 
 int main() {
+    check_page_prefix();
     check_chunks();
     check_tile_numbering();
     check_blocks();

@@ -284,6 +284,110 @@ def _records(graph, run):
     return [(r["kernel"], int(r["calls"])) for r in json.loads(buf.value.decode())]
 
 
+# The launch records [(kernel with layer text, calls)] of the three visual entries on the one page of the test below, in the report's order
+# (a kernel stands where it was first launched).  Recorded on an MI355X with the build in front of the refactor that gave the single and the
+# uniform entry one body and the table entry its stages; literal on purpose: nothing here is computed from the code under test.
+_BACKBONE_LAUNCHES = [
+    ('res8v_down_kernel<0> unet_down_0 (conv1+3xconvR+add+pool) 71x53', 1),
+    ('conv_mfma_kernel<3,3,1,true,16,false,false,false,4> aru_net/featMapG/unet_down_1/conv1 36x27 8->16', 1),
+    ('conv_mfma_kernel<3,3,1,false,16,false,false,false,4> aru_net/featMapG/unet_down_1/convR_0 36x27 16->16', 1),
+    ('conv_mfma_kernel<3,3,1,false,16,false,false,false,4> aru_net/featMapG/unet_down_1/convR_1 36x27 16->16', 1),
+    ('conv_mfma_kernel<3,3,1,false,16,false,false,false,2> aru_net/featMapG/unet_down_1/convR_2 36x27 16->16', 1),
+    ('conv_winor_kernel<false,2,false> aru_net/featMapG/unet_down_2/conv1 18x14 16->32', 1),
+    ('conv_winor_kernel<false,2,false> aru_net/featMapG/unet_down_2/convR_0 18x14 32->32', 1),
+    ('conv_winor_kernel<false,2,false> aru_net/featMapG/unet_down_2/convR_1 18x14 32->32', 1),
+    ('conv_winor_kernel<false,2,true> aru_net/featMapG/unet_down_2/convR_2 18x14 32->32', 1),
+    ('conv_wino_kernel<4,false> aru_net/featMapG/unet_down_3/conv1 9x7 32->64', 1),
+    ('conv_wino_kernel<4,false> aru_net/featMapG/unet_down_3/convR_0 9x7 64->64', 1),
+    ('conv_wino_kernel<4,false> aru_net/featMapG/unet_down_3/convR_1 9x7 64->64', 1),
+    ('conv_wino_kernel<4,false> aru_net/featMapG/unet_down_3/convR_2 9x7 64->64', 1),
+    ('maxpool2_kernel', 1),
+    ('conv_wino_kernel<4,false> aru_net/featMapG/unet_down_4/conv1 5x4 64->128', 1),
+    ('conv_wino_kernel<4,false> aru_net/featMapG/unet_down_4/convR_0 5x4 128->128', 1),
+    ('conv_wino_kernel<4,false> aru_net/featMapG/unet_down_4/convR_1 5x4 128->128', 1),
+    ('conv_wino_kernel<4,false> aru_net/featMapG/unet_down_4/convR_2 5x4 128->128', 1),
+    ('deconv_mfma_kernel<2,false> aru_net/featMapG/unet_up_3/deconv 5x4 128->64', 1),
+    ('conv_wino_kernel<4,false> aru_net/featMapG/unet_up_3/conv1 9x7 128->64', 1),
+    ('conv_wino_kernel<4,false> aru_net/featMapG/unet_up_3/convR_0 9x7 64->64', 1),
+    ('conv_wino_kernel<4,false> aru_net/featMapG/unet_up_3/convR_1 9x7 64->64', 1),
+    ('conv_wino_kernel<4,false> aru_net/featMapG/unet_up_3/convR_2 9x7 64->64', 1),
+    ('deconv_mfma_kernel<2,false> aru_net/featMapG/unet_up_2/deconv 9x7 64->32', 1),
+    ('conv_winor_kernel<false,2,false> aru_net/featMapG/unet_up_2/conv1 18x14 64->32', 1),
+    ('conv_winor_kernel<false,2,false> aru_net/featMapG/unet_up_2/convR_0 18x14 32->32', 1),
+    ('conv_winor_kernel<false,2,false> aru_net/featMapG/unet_up_2/convR_1 18x14 32->32', 1),
+    ('conv_winor_kernel<false,2,true> aru_net/featMapG/unet_up_2/convR_2 18x14 32->32', 1),
+    ('deconv_mfma_kernel<1,false> aru_net/featMapG/unet_up_1/deconv 18x14 32->16', 1),
+    ('conv_mfma_kernel<3,3,1,false,16,false,false,false,4> aru_net/featMapG/unet_up_1/conv1 36x27 32->16', 1),
+    ('conv_mfma_kernel<3,3,1,false,16,false,false,false,4> aru_net/featMapG/unet_up_1/convR_0 36x27 16->16', 1),
+    ('conv_mfma_kernel<3,3,1,false,16,false,false,false,4> aru_net/featMapG/unet_up_1/convR_1 36x27 16->16', 1),
+    ('conv_mfma_kernel<3,3,1,false,16,false,false,false,2> aru_net/featMapG/unet_up_1/convR_2 36x27 16->16', 1),
+    ('deconv8v_kernel aru_net/featMapG/unet_up_0/deconv 36x27 16->8', 1),
+    ('res8v_up_kernel<0> unet_up_0 (conv1[16->8]+3xconvR+add) 71x53', 1),
+    ('combine_kernel<8,2,false,1>', 1),
+]
+SINGLE_LAUNCHES = _BACKBONE_LAUNCHES + [
+    ('fmap_conv1x1_kernel<false> fm_1 36x27 16->3', 1),
+    ('fmap_conv3x3_kernel fm_1 36x27 3->6 s1', 1),
+    ('fmap_conv1x1_kernel<false> fm_2 36x27 6->1', 1),
+    ('fmap_conv3x3_kernel fm_2 36x27 1->2 s2', 1),
+]
+UNIFORM_LAUNCHES = _BACKBONE_LAUNCHES + [
+    ('fmap_conv1x1_kernel<false> fm_1 36x27 16->3', 1),
+    ('fmap_conv3x3_kernel fm_1 36x27 3->6 s1', 1),
+    ('fmap_conv1x1_kernel<false> fm_2 36x27 6->1', 1),
+    ('fmap_conv3x3_kernel fm_2 36x27 1->2 s2', 1),
+]
+TABLE_LAUNCHES = [
+    ('moments_pages_kernel 1 pages', 1),
+    ('moments_finish_pages_kernel 1 pages', 1),
+] + _BACKBONE_LAUNCHES + [
+    ('fmap_conv1x1_pages_kernel<false> fm_1 1 pages 16->3', 1),
+    ('fmap_conv3x3_pages_kernel fm_1 1 pages 3->6 s1', 1),
+    ('fmap_conv1x1_pages_kernel<false> fm_2 1 pages 6->1', 1),
+    ('fmap_conv3x3_pages_kernel fm_2 1 pages 1->2 s2', 1),
+    ('gnn_roi_compress_pages_kernel<false> 1 pages 6 entries 48 regions', 1),
+]
+
+
+def test_one_page_through_the_three_entries_keeps_each_launch_sequence_and_nothing_left_in_the_handle_changes_a_later_call():
+    """one handle (an end point, a generated stride-1 and a generated stride-2 map, interaction visual features; fp32), one page of 71 x 53 with
+    N = 4 nodes and 12 interactions, four calls with the launch records on: the single entry, the uniform entry with one page, the table entry
+    with one page, the single entry again.  The first and the last call must give the same output bits and the same records, and every entry's
+    records must be the literal list above."""
+    import torch
+    from citlab_article_separation_new_amd import gnn_io
+    from citlab_article_separation_new_amd.config import GnnConfig
+    from citlab_article_separation_new_amd.weights import init_gnn_weights
+    cfg = GnnConfig(node_feature_dim=7, mvn=True, visual_layers=[UP1, UP1, ""], visual_layer_depths=[-1, 6, 2], visual_dims=[8, 4, 4], visual_edges=True,
+                    backbone={"compute_dtype": "f32"})
+    graph = gnn_io.GnnGraph(init_gnn_weights(cfg, 11, bias_jitter=0.05), cfg)
+    h, w = 71, 53
+    host = _host_pages(cfg, [(h, w)], seed=23, nodes=[4])
+    assert host[0]["E"] == 12
+    t, q = _upload(host[0], cfg.num_classes)
+    entries = {
+        "single": lambda: gnn_io.gnn_forward_visual_dev(graph, q["N"], q["E"], q["d_edges"], q["d_node_feat"], q["d_edge_feat"], q["d_image"], h, w,
+                                                        q["d_regions"], P, q["d_num_points"], q["R"], q["d_relations"], q["d_probs_out"], None, 0,
+                                                        d_edge_regions=q["d_edge_regions"], d_edge_num_points=q["d_edge_num_points"]),
+        "uniform": lambda: gnn_io.gnn_forward_visual_batch_dev(graph, [q], h, w, P),
+        "table": lambda: gnn_io.gnn_forward_visual_batch_dev2(graph, [q], [h], [w], P),
+    }
+    got = []
+    for name in ("single", "uniform", "table", "single"):
+        t["out"].zero_()
+        recs = _records(graph, entries[name])
+        torch.cuda.synchronize()
+        got.append((name, recs, t["out"].cpu().numpy()))
+        print(name, recs)
+    graph.close()
+    (_, recs1, out1), (_, recs4, out4) = got[0], got[3]
+    assert np.isfinite(out1).all() and out1.shape == (16, 2)
+    assert _same(out4, out1) and recs4 == recs1
+    want = {"single": SINGLE_LAUNCHES, "uniform": UNIFORM_LAUNCHES, "table": TABLE_LAUNCHES}
+    for name, recs, _ in got:
+        assert recs == want[name], (name, recs)
+
+
 def test_every_batched_stage_is_one_launch_per_call(cases):
     """what fails when the entry is a loop over the single-page one: per call ONE launch of the normalisation's moments (and one of their
     finish), ONE per convolution of each generated map and ONE ROI / compression launch, none of the single-page kernels"""
