@@ -149,6 +149,9 @@ SIGNATURES = {
     "asep_textblock_neighbour_words": (C.c_longlong, [C.c_int, _P]),
     "asep_textblock_neighbours": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_double, _P, C.c_longlong]),
     "asep_textblock_last_kernel_us": (C.c_double, [C.c_int]),
+    "asep_alpha_shapes": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "asep_alpha_shapes_last_kernel_us": (C.c_double, [C.c_int]),
+    "asep_alpha_shapes_lds_points": (C.c_int, []),
     "asep_measure_run": (C.c_longlong, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
     "asep_measure_fetch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "asep_measure_last_kernel_us": (C.c_double, [C.c_int]),

@@ -1,7 +1,7 @@
 """CLI mirror of ``article_separation/run_textregion_generation.py`` (+ ``textregion_generation/textregion_generation.py``).
 
     python -m citlab_article_separation_new_amd.run_textregion_generation --path_to_xml_lst pages.lst \\
-        [--des_dist 50] [--max_d 100] [--alpha 75] [--num_threads N]
+        [--des_dist 50] [--max_d 100] [--alpha 75] [--num_threads N] [--device_regions True]
 
 One alpha-shape TextRegion per article of each PAGE-XML file (one per line for lines without an article id), with
 reading orders for the regions and their lines; the existing text regions are replaced and the file is rewritten in
@@ -9,6 +9,8 @@ place.  As in the reference the region outlines use the normed baselines of ``--
 distances use the default des_dist of 5.  This process owns the GPU (one distance launch per group of pages);
 ``--num_threads`` host threads (at most the container's CPU quota) read the files and build the regions.
 ``--use_java_code`` is accepted with either value: the results always follow the reference's Python path.
+``--device_regions True`` (off by default): the host triangulates each article of a group of pages once and one engine
+call gives the alpha shapes of the whole group (textblock.create_text_regions_pages); files and printed lines are the same.
 """
 import io
 import sys
@@ -38,6 +40,9 @@ def build_parser():
                    help="accepted for compatibility with either value; the interline distances are always those of the "
                         "reference's Python path (computed on the GPU), the Java class is not used")
     p.add_argument("--num_threads", type=int, default=1, help="number of host threads reading / writing the files")
+    p.add_argument("--device_regions", type=cli_flags.str2bool, default=False,
+                   help="alpha shapes of all articles of a group of pages in one GPU call behind the host triangulation; "
+                        "same files and printed lines")
     return p
 
 
@@ -56,19 +61,22 @@ def read_page(path, des_dist):
     return page, art, lines, polys, geo.norm_poly_dists(polys, des_dist)
 
 
-def finish_page(path, page, art, lines, normed, dists, alpha):
-    """textregion_generation.py:50-77 and 102-172: synthetic Coords, alpha-shape regions, reading orders, write back.
-    Returns the lines the reference prints (its alpha retries)."""
+def page_geometry(art, lines, normed, dists):
+    """textregion_generation.py:50-77: synthetic Coords for the lines without, and what create_text_regions reads:
+    ({line id: line}, {article id: [line id, ...]}, {line id: (normed polygon, interline distance)})"""
     from . import textblock
-    out = io.StringIO()
     by_id = {tl.id: tl for ls in art.values() for tl in ls}
     geom = {}
     for tl, poly, d in zip(lines, normed, dists):
         if not tl.has_coords():
             tl.set_coords(textblock.synthetic_coords(poly[0], poly[1], d))
         geom[tl.id] = (poly, float(d))
-    art_ids = {a: [tl.id for tl in ls] for a, ls in art.items()}
-    regions = textblock.create_text_regions(art_ids, geom, alpha, log=lambda s: print(s, file=out))
+    return by_id, {a: [tl.id for tl in ls] for a, ls in art.items()}, geom
+
+
+def write_regions(path, page, by_id, regions):
+    """textregion_generation.py:102-127: reading orders, the regions in place of the page's, write back"""
+    from . import textblock
     objs = []
     for rid, points, members, ro in regions:
         tls = [by_id[i] for i in members]
@@ -78,6 +86,16 @@ def finish_page(path, page, art, lines, normed, dists, alpha):
         objs.append((rid, points, tls, ro))
     page.replace_text_regions(objs)
     page.write_page_xml(path)
+
+
+def finish_page(path, page, art, lines, normed, dists, alpha):
+    """textregion_generation.py:50-77 and 102-172: synthetic Coords, alpha-shape regions, reading orders, write back.
+    Returns the lines the reference prints (its alpha retries)."""
+    from . import textblock
+    out = io.StringIO()
+    by_id, art_ids, geom = page_geometry(art, lines, normed, dists)
+    regions = textblock.create_text_regions(art_ids, geom, alpha, log=lambda s: print(s, file=out))
+    write_regions(path, page, by_id, regions)
     return out.getvalue()
 
 
@@ -103,16 +121,45 @@ def process(paths, flags, device=0, log=print, start=1):
                        for r in read]
             dists = textblock.interline_distances_or_errors(normed5, INTERLINE_DES_DIST, flags.max_d, device)
 
+            def failed(k, e):
+                return "", "{}: not written ({}: {})".format(group[k], type(e).__name__, e)
+
             def finish(k):
                 if isinstance(dists[k], Exception):      # not read, or its baselines could not be normed
-                    e = dists[k]
-                    return "", "{}: not written ({}: {})".format(group[k], type(e).__name__, e)
+                    return failed(k, dists[k])
                 page, art, lines, polys, normed = read[k]
                 try:
                     return finish_page(group[k], page, art, lines, normed, dists[k], flags.alpha), None
                 except Exception as e:        # the reference's per-file subprocess fails without saving
-                    return "", "{}: not written ({}: {})".format(group[k], type(e).__name__, e)
-            for k, (printed, err) in enumerate(pool.map(finish, range(len(group)))):
+                    return failed(k, e)
+
+            step = finish
+            if getattr(flags, "device_regions", False):
+                # the same steps with the alpha shapes of the whole group from one engine call in between
+                good = [k for k in range(len(group)) if not isinstance(dists[k], Exception)]
+                geoms = pool.map(lambda k: _safely(page_geometry, read[k][1], read[k][2], read[k][4], dists[k]), good)
+                ready = [(k, g) for k, g in zip(good, geoms) if not isinstance(g, Exception)]
+                outs = [io.StringIO() for _ in ready]
+                regions = textblock.create_text_regions_pages(
+                    [(g[1], g[2]) for _, g in ready], flags.alpha,
+                    [lambda s, o=o: print(s, file=o) for o in outs], device, pool)
+                staged = {k: g for k, g in zip(good, geoms) if isinstance(g, Exception)}
+                staged.update({k: (g[0], r, o) for (k, g), r, o in zip(ready, regions, outs)})
+
+                def step(k):            # finish(k) with the regions already there
+                    if isinstance(dists[k], Exception):
+                        return failed(k, dists[k])
+                    if isinstance(staged[k], Exception):
+                        return failed(k, staged[k])
+                    by_id, regs, out = staged[k]
+                    if isinstance(regs, Exception):
+                        return failed(k, regs)
+                    try:
+                        write_regions(group[k], read[k][0], by_id, regs)
+                        return out.getvalue(), None
+                    except Exception as e:
+                        return failed(k, e)
+            for k, (printed, err) in enumerate(pool.map(step, range(len(group)))):
                 log("No {:5d}: {}".format(start + g0 + k, group[k]))
                 if printed:
                     log(printed.rstrip("\n"))

@@ -3,7 +3,8 @@
     interline_distances      dbscan_baselines.py:35-110 (use_java_code=False)     -> asep_textblock_interline_dists
     neighbour_lists          dbscan_baselines.py:253-307 region_query, all rows    -> asep_textblock_neighbours
     DBSCAN labels            dbscan_baselines.py:113-251, 309-333                  (host, over the device neighbour lists)
-    text regions             textregion_generation.py:17-172                       (host alpha shapes)
+    text regions             textregion_generation.py:17-172                       (host alpha shapes; device_regions=True:
+                                                                                    host triangulation -> asep_alpha_shapes)
 
 Every function takes a BATCH of pages (one list of polygons per page) so that one kernel launch serves all of them.
 The results are those of the reference's Python path; the Java class the reference can call instead
@@ -248,10 +249,16 @@ def synthetic_coords(xs, ys, dist):
     return list(zip([int(x) for x in xs] + xsh[::-1], [int(y) for y in ys] + ysh[::-1]))
 
 
-def create_text_regions(art_lines, line_geom, alpha=75, log=print):
+def create_text_regions(art_lines, line_geom, alpha=75, log=print, device_regions=False, device=0):
     """textregion_generation.py:129-172.  ``art_lines``: {article id or None: [line id, ...]} in the page's order;
     ``line_geom``: {line id: ((xs, ys) normed polygon, interline distance)}.  Returns
-    [("tr_<n>", boundary points, [line id, ...], n), ...]."""
+    [("tr_<n>", boundary points, [line id, ...], n), ...].  ``device_regions``: the alpha shapes behind the
+    triangulations come from one engine call (create_text_regions_pages), the result and the logged lines are the same."""
+    if device_regions:
+        res = create_text_regions_pages([(art_lines, line_geom)], alpha, [log], device)[0]
+        if isinstance(res, Exception):
+            raise res
+        return res
     regions = []
     counter = 0
 
@@ -283,6 +290,160 @@ def create_text_regions(art_lines, line_geom, alpha=75, log=print):
 
 def alpha_shape_int(pts, alpha, log=print):
     return [[int(j) for j in i] for i in geo.alpha_shape(np.array(pts), alpha, log)]
+
+
+# ---- text regions (device alpha shapes behind the host triangulation) -------------------------------------------------
+
+def triangulate(points):
+    """scipy's Delaunay of an (n, 2) integer array, as textblock_geometry.alpha_shape calls it: (points, simplices,
+    neighbors).  Its triangle order decides the boundary's first edge, so the engine takes it as it is."""
+    from scipy.spatial import Delaunay
+    points = np.asarray(points)
+    tri = Delaunay(points)
+    return points, np.ascontiguousarray(tri.simplices, np.int32), np.ascontiguousarray(tri.neighbors, np.int32)
+
+
+def alpha_shapes_device(pages, max_retries=None, device=0, debug=False):
+    """One asep_alpha_shapes call.  ``pages``: per page a list of articles (points (n, 2) int, simplices, neighbors,
+    alpha0) as ``triangulate`` gives them.  Returns per page a list of (ring: point indices in the reference's order
+    without the repeated first one, retries, failed); with ``debug`` each entry also holds the circumradii and the
+    boundary half-edge mask of the article's last round."""
+    import sys
+    lib, h = _handle(device)
+    arts = [a for pg in pages for a in pg]
+    art_off = np.zeros(len(pages) + 1, np.int32)
+    art_off[1:] = np.cumsum([len(pg) for pg in pages])
+    pt_off = np.zeros(len(arts) + 1, np.int64)
+    tri_off = np.zeros(len(arts) + 1, np.int64)
+    pt_off[1:] = np.cumsum([len(a[0]) for a in arts])
+    tri_off[1:] = np.cumsum([len(a[1]) for a in arts])
+    if pt_off[-1] > np.iinfo(np.int32).max or 3 * tri_off[-1] > np.iinfo(np.int32).max:
+        raise ValueError(f"alpha_shapes_device: {pt_off[-1]} points / {tri_off[-1]} triangles exceed one call")
+    pt_off, tri_off = pt_off.astype(np.int32), tri_off.astype(np.int32)
+    n_pts, n_tri = int(pt_off[-1]), int(tri_off[-1])
+    pts = np.zeros((max(n_pts, 1), 2), np.int32)
+    simp = np.zeros((max(n_tri, 1), 3), np.int32)
+    neigh = np.zeros((max(n_tri, 1), 3), np.int32)
+    for k, (p, s, nb, _) in enumerate(arts):
+        p = np.asarray(p)
+        if p.ndim != 2 or p.shape[1] != 2 or (p.size and (p.min() < -2 ** 31 or p.max() >= 2 ** 31)):
+            raise ValueError(f"alpha_shapes_device: article {k} needs (n, 2) points within int32")
+        pts[pt_off[k]:pt_off[k + 1]] = p
+        simp[tri_off[k]:tri_off[k + 1]] = s
+        neigh[tri_off[k]:tri_off[k + 1]] = nb
+    alpha0 = np.array([float(a[3]) for a in arts] + [0.0], np.float64)
+    ring = np.zeros(max(n_pts, 1), np.int32)
+    res = np.zeros((3, max(len(arts), 1)), np.int32)
+    circ = np.zeros(max(n_tri, 1), np.float64) if debug else None
+    mask = np.zeros(max(n_tri, 1), np.uint8) if debug else None
+    _lib.check(lib.asep_alpha_shapes(h, len(pages), _ptr(art_off), _ptr(pt_off), _ptr(tri_off), _ptr(pts), _ptr(simp), _ptr(neigh),
+                                     _ptr(alpha0), int(sys.getrecursionlimit() if max_retries is None else max_retries),
+                                     _ptr(ring), _ptr(res[0]), _ptr(res[1]), _ptr(res[2]),
+                                     _ptr(circ) if debug else None, _ptr(mask) if debug else None), "asep_alpha_shapes")
+    out, k = [], 0
+    for pg in pages:
+        rows = []
+        for _ in pg:
+            row = (ring[pt_off[k]:pt_off[k] + res[0, k]].copy(), int(res[1, k]), bool(res[2, k]))
+            if debug:
+                row += (circ[tri_off[k]:tri_off[k + 1]].copy(), mask[tri_off[k]:tri_off[k + 1]].copy())
+            rows.append(row)
+            k += 1
+        out.append(rows)
+    return out
+
+
+def last_alpha_shape_kernel_us(which):
+    """device time of the last circumradius (0) / boundary (1) kernel of this thread, microseconds"""
+    return float(_lib.load_library().asep_alpha_shapes_last_kernel_us(which))
+
+
+RETRY_LINE = "alpha value not suitable -> is increased"
+
+
+def _region_jobs(art_lines, line_geom, alpha):
+    """The point sets create_text_regions hands to alpha_shape, in its order: ([(points array or the exception its
+    triangulation raises, members), ...], the exception that ends the page behind them or None)."""
+    jobs = []
+
+    def outline(lid):
+        (xs, ys), d = line_geom[lid]
+        xsh, ysh = shifted_outline(xs, ys, d)
+        return list(zip([int(x) for x in xs] + xsh, [int(y) for y in ys] + ysh))
+
+    try:
+        for article_id, lines in art_lines.items():
+            if article_id is None:
+                for lid in lines:
+                    if lid in line_geom:
+                        jobs.append((np.array(outline(lid)), [lid]))
+            else:
+                pts, members = [], []
+                for lid in lines:
+                    if lid in line_geom:
+                        members.append(lid)
+                        pts += outline(lid)
+                if not pts:
+                    raise IndexError(f"article {article_id} has no line with a baseline")
+                jobs.append((np.array(pts), members))
+    except Exception as e:      # noqa: BLE001 (the host path meets it after the regions in front of it)
+        return jobs, e
+    return jobs, None
+
+
+def _triangulate_or_error(points):
+    if points.shape[0] <= 3:
+        return None                                   # util.py:620: returned as they are
+    try:
+        return triangulate(points)
+    except Exception as e:      # noqa: BLE001 (Qhull's refusal of e.g. collinear points, raised where the host path raises it)
+        return e
+
+
+def create_text_regions_pages(pages, alpha=75, logs=None, device=0, pool=None):
+    """create_text_regions for a group of pages with ONE engine call: ``pages`` = [(art_lines, line_geom), ...].
+    The host triangulates every article once (``pool.map`` when a thread pool is given); the circumradii, the boundary
+    edges, the walk and the alpha * 1.2 retries run on the device.  Returns per page the regions or the exception the
+    host path raises for it; ``logs[k]`` receives the page's retry lines, one per retry, in the host's order."""
+    import sys
+    logs = logs or [print] * len(pages)
+    max_retries = sys.getrecursionlimit()
+    plans = [_region_jobs(art, geom, alpha) for art, geom in pages]
+    flat = [pts for jobs, _ in plans for pts, _ in jobs]
+    tris = iter((pool.map if pool is not None else lambda f, xs: list(map(f, xs)))(_triangulate_or_error, flat))
+    tris = [[next(tris) for _ in jobs] for jobs, _ in plans]
+    dev_pages = []
+    for tri in tris:
+        # (behind an article that ends the page the host path computes nothing more)
+        stop = next((i for i, t in enumerate(tri) if isinstance(t, Exception)), len(tri))
+        dev_pages.append([t + (alpha,) for t in tri[:stop] if t is not None] if alpha > 0 else [])
+    rings = alpha_shapes_device(dev_pages, max_retries, device) if any(dev_pages) else [[] for _ in pages]
+    out = []
+    for (jobs, end), tri, got, log in zip(plans, tris, rings, logs):
+        got = iter(got)
+        regions = []
+        try:
+            for counter, ((points, members), t) in enumerate(zip(jobs, tri)):
+                assert alpha > 0, "alpha value has to be greater than zero"
+                if isinstance(t, Exception):
+                    raise t
+                if t is None:
+                    bp = points.tolist()
+                else:
+                    ring, retries, failed = next(got)
+                    for _ in range(retries):
+                        log(RETRY_LINE)
+                    if failed:
+                        raise RecursionError(f"alpha_shape: no single boundary after {retries} increases of alpha")
+                    bp = points[ring].tolist()
+                bp.append(bp[0])
+                regions.append(("tr_" + str(counter), [[int(j) for j in i] for i in bp], members, counter))
+            if end is not None:
+                raise end
+            out.append(regions)
+        except Exception as e:      # noqa: BLE001 (the page's error, as the host path raises it)
+            out.append(e)
+    return out
 
 
 def reading_order(baselines):

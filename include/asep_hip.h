@@ -494,6 +494,31 @@ int asep_textblock_neighbours(asep_post* p, int n_pages, const int32_t* page_off
  * or asep_textblock_neighbours (which = 1) call; -1 for another `which`. */
 double asep_textblock_last_kernel_us(int which);
 
+/* ---- text regions (python_util/geometry/util.py:568-697 alpha_shape behind the Delaunay triangulation) -----------------
+ * One call for all articles of a group of pages on the asep_post handle; host pointers in and out, the call returns after
+ * its results have arrived.  Page k holds the articles art_off[k] .. art_off[k+1]-1, article a the points
+ * pt_off[a] .. pt_off[a+1]-1 of `points` ((x, y) int32 pairs) and the triangles tri_off[a] .. tri_off[a+1]-1 of
+ * `simplices` and `neighbors` ([.][3] int32, scipy.spatial.Delaunay's tables of the article's points: indices local to
+ * the article, neighbors[t][j] = the triangle opposite corner j or -1).  alpha0 [n_articles] is the first alpha of each
+ * article; a refused alpha becomes alpha + alpha * 0.2, at most max_retries (>= 1) times.
+ *
+ * Out, per article a: out_ring[pt_off[a] ..] the point indices of the boundary in the reference's order (without the
+ * repeated first point), out_len[a] their number, out_retries[a] the increases of alpha taken, out_failed[a] = 1 when
+ * max_retries increases gave no single boundary (out_len[a] = 0 then).  Optional (NULL to skip), for tests:
+ * out_circum_r [sum T] the circumradii as the reference computes them, bit for bit; out_edge_mask [sum T] bit k set when
+ * the edge k = (corner k, corner (k+1) % 3) of the triangle is on the boundary in the article's last round.
+ * The offset tables and every corner / neighbour index are checked before anything is allocated or launched;
+ * ASEP_ERR_ARG names the page, the article and the reason.  A ring does not depend on what else shares the call. */
+int asep_alpha_shapes(asep_post* p, int n_pages, const int32_t* art_off, const int32_t* pt_off, const int32_t* tri_off,
+                      const int32_t* points, const int32_t* simplices, const int32_t* neighbors, const double* alpha0,
+                      int max_retries, int32_t* out_ring, int32_t* out_len, int32_t* out_retries, int32_t* out_failed,
+                      double* out_circum_r, uint8_t* out_edge_mask);
+/* Device time in microseconds of the circumradius (which = 0) or boundary (which = 1) kernel of the calling thread's last
+ * asep_alpha_shapes call; -1 for another `which`. */
+double asep_alpha_shapes_last_kernel_us(int which);
+/* The largest article (in points) whose vertex tables the boundary kernel keeps in LDS; larger ones use global scratch. */
+int asep_alpha_shapes_lds_points(void);
+
 /* ---- article separation measure (eval_measure.py count_rel_hits / count_rel_hits_list, Python path) -------------------
  * Batched over file pairs on the asep_post handle.  Truth and reco (hypothesis) polygons are NORMED baselines in the
  * layout of asep_textblock_interline_dists (points as (x, y) int32 pairs, poly_off, boxes {x, y, w, h}); file k holds
