@@ -174,6 +174,12 @@ SIGNATURES = {
     "asep_releval_finish": (C.c_int, [_P, _P, C.POINTER(C.c_longlong)]),
     "asep_releval_fetch": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "asep_releval_stage_us": (C.c_double, [_P, C.c_int]),
+    "asep_seg_eval_create": (_P, []),
+    "asep_seg_eval_free": (None, [_P]),
+    "asep_seg_eval_pages_dev": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "asep_seg_eval_blend_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "asep_seg_eval_last_kernel_us": (C.c_double, [_P]),
+    "asep_seg_eval_last_launches": (C.c_long, [_P, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

@@ -729,6 +729,47 @@ int asep_releval_fetch(asep_releval* h, void* stream, float* thresholds, int64_t
  * passes 0..3, 12 / 13 / 14 = curve count / scan / write, 15 = A2; -1 for another `which`. */
 double asep_releval_stage_us(const asep_releval* h, int which);
 
+/* ---- segmentation net evaluation (article_separation/plot_net_output.py) ---------------------------------------------
+ * What plot_net_output computes from a pixel labeller's output, on the probabilities where asep_aru_forward_batch_dev2 left
+ * them: the count of unsure values, the arg-max class counts, the per-class agreement with the ground truth channel images
+ * and the per-class output masks.  Only integer counts leave the device; shares and accuracies are host divisions.
+ * (The entry points of this block were added under ABI 12: the number is pinned by the suite and stays.) */
+#define ASEP_SEG_EVAL_MAX_CLASSES 8
+/* one page's counter block: ASEP_SEG_EVAL_SLOTS numbers; the per-class groups hold C entries each */
+#define ASEP_SEG_EVAL_SLOTS 48
+#define ASEP_SEG_EVAL_UNSURE 0   /* values with 0 < p < 1, before any threshold (:198-199) */
+#define ASEP_SEG_EVAL_PIXELS 1   /* H * W */
+#define ASEP_SEG_EVAL_HAS_GT 2   /* 1 if the page came with ground truth planes; the groups from EQUAL on are 0 without */
+#define ASEP_SEG_EVAL_CLASS 8    /* [c] pixels whose arg max (first maximum) is c (:216-226) */
+#define ASEP_SEG_EVAL_EQUAL 16   /* [c] pixels where the one-hot arg max equals gt_c / 255 (:109-117,241): (gt == 255 and arg max
+                                    == c) or (gt == 0 and arg max != c); any other ground truth byte never matches */
+#define ASEP_SEG_EVAL_TP 24      /* [c] arg max == c and gt_c == 255.  TP / FP / FN are an addition to the reference */
+#define ASEP_SEG_EVAL_FP 32      /* [c] arg max == c and gt_c != 255 */
+#define ASEP_SEG_EVAL_FN 40      /* [c] arg max != c and gt_c == 255 */
+typedef struct asep_seg_eval asep_seg_eval;
+asep_seg_eval* asep_seg_eval_create(void);
+void asep_seg_eval_free(asep_seg_eval* h);
+/* The pages of a call, of any sizes, in one launch per 12 pages.  Host arrays: d_probs[b] = page b's float32 [H[b], W[b], C];
+ * d_gt (or NULL) [n_pages * C]: d_gt[b * C + c] = uint8 [H[b], W[b]] plane of class c, a page's C entries all set or all NULL;
+ * d_masks (or NULL) [n_pages]: d_masks[b] (or NULL) receives the planar uint8 [C][H[b], W[b]] masks, uint8(p * 255) by
+ * truncation.  mask_threshold != 0: the values become p > 0.6 before the arg max and the masks 0 / 255 -- 0.6 whatever the
+ * flag's value, as :201-202 have it; the unsure count is taken first.  out_counters [n_pages * ASEP_SEG_EVAL_SLOTS] is host
+ * memory.  The counters are zeroed by the call; the call synchronises `stream`.
+ * Refused: C < 1 (ASEP_ERR_ARG), C > ASEP_SEG_EVAL_MAX_CLASSES or a page of H * W * C >= 2^40 values (ASEP_ERR_UNSUPPORTED), a
+ * page without probabilities or with some but not all of its ground truth planes (ASEP_ERR_ARG). */
+int asep_seg_eval_pages_dev(asep_seg_eval* h, int n_pages, const float* const* d_probs, const uint8_t* const* d_gt,
+                            uint8_t* const* d_masks, const int32_t* H, const int32_t* W, int C, int mask_threshold,
+                            unsigned long long* out_counters, void* stream);
+/* apply_mask(image, mask, (r, g, b), alpha 0.5) of :57-93: d_out [H, W, 3] = where d_mask [H, W] is 255 the truncated mean of the
+ * d_scan [H, W, 3] byte and the colour, else the scan's byte.  Queued on `stream`; d_out may be d_scan. */
+int asep_seg_eval_blend_dev(asep_seg_eval* h, const uint8_t* d_scan, const uint8_t* d_mask, int H, int W, int r, int g, int b,
+                            uint8_t* d_out, void* stream);
+/* Device time in microseconds of the scoring launches of the last asep_seg_eval_pages_dev. */
+double asep_seg_eval_last_kernel_us(const asep_seg_eval* h);
+/* The kernels launched through the handle since the start of its last asep_seg_eval_pages_dev, one name per line
+ * ("seg_eval_kernel<C,thr>", "seg_blend_kernel").  Copies at most max_bytes - 1 characters; returns the text's length. */
+long asep_seg_eval_last_launches(const asep_seg_eval* h, char* buf, size_t max_bytes);
+
 #ifdef __cplusplus
 }
 #endif
