@@ -48,6 +48,7 @@ class ClusterSetting(C.Structure):
 RESIZE_MODES = {"keep": 0, "luma": 1}                                # ASEP_RESIZE_* of include/asep_hip.h
 EDGE_RULES = {"bb": 0, "line": 1}                                   # ASEP_EDGE_RULE_* of include/asep_hip.h
 SEP_ORIENTATIONS = {None: 0, "horizontal": 1, "vertical": 2}        # ASEP_SEP_*; any other tag is ASEP_SEP_OTHER (3)
+JPEG_ORDERS = {"gray": 0, "bgr": 1, "rgb": 2}                        # ASEP_JPEG_ORDER_* of include/asep_hip.h
 CLUSTER_METHODS = {"dbscan": 0, "dbscan_std": 1, "greedy": 2}       # ASEP_CLUSTER_* of include/asep_hip.h
 
 
@@ -180,6 +181,9 @@ SIGNATURES = {
     "asep_seg_eval_blend_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "asep_seg_eval_last_kernel_us": (C.c_double, [_P]),
     "asep_seg_eval_last_launches": (C.c_long, [_P, C.c_char_p, C.c_size_t]),
+    "asep_jpeg_pixels_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P]),
+    "asep_jpeg_pixels": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "asep_jpeg_last_launches": (C.c_long, [C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

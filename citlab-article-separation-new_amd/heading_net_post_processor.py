@@ -13,12 +13,12 @@ from collections import Counter
 import numpy as np
 from scipy import ndimage
 
-from . import _lib, image_ops
+from . import _lib, image_io, image_ops
 from .host_util import rescale_points
 from .image_io import load_image_bgr
 from .path_util import get_page_path
 from .region_to_page_writer import RegionToPageWriter
-from .separator_net_post_processor import RegionNetPostProcessor
+from .separator_net_post_processor import RegionNetPostProcessor, jpeg_decode_options
 
 HEADING = "heading"          # page_constants.py:58-59 TextRegionTypes
 PARAGRAPH = "paragraph"
@@ -405,13 +405,17 @@ class HeadingNetPostProcessor(RegionNetPostProcessor):
                                    list(values), self.weight_dict, self.threshold, self.thresh_dict, self.text_line_percentage)
 
                 decode = DecodePool(self.image_paths, n_workers, register=reg, unregister=unreg,
-                                    hold=self.PAGE_GROUP + 1 if pipelined else 3)
+                                    hold=self.PAGE_GROUP + 1 if pipelined else 3,
+                                    **jpeg_decode_options(self.image_paths, self.device_jpeg))
                 if pipelined:
                     # behind the GPU: the next group is uploaded and queued before a page's lines are measured (the measuring calls
                     # wait for their small kernels; the chip has the next nets to work on meanwhile)
                     self._run_groups(decode, len(self.image_paths), self.PAGE_GROUP, self.PAGE_LANES, self.enqueue_group, finish)
                 else:
                     for image_path, image in decode:
+                        jpeg = image_io.as_jpeg_page(image)
+                        if jpeg is not None:                 # --device_jpeg: this path works on host pages, so the device's page comes back
+                            image = image_io.jpeg_page_to_device(jpeg, self.device, "bgr").cpu().numpy()
                         if self.weight_dict['net'] > 0:
                             net_output = self.heading_probability(image)
                             net_output_post = self.post_process(net_output)

@@ -4,10 +4,17 @@
     load_image_gray         cv2.imread(path, IMREAD_GRAYSCALE)       swt_dist_trafo.py:19
     get_image_dimensions    image_stats.py:23-29                     (width, height)
     load_and_scale_image    helper:28-33                             decode here, scale + gray on the GPU
+    load_jpeg_coefficients  (no counterpart)                         baseline JPEG: Huffman decode only, csrc/host_jpeg.c
+    jpeg_page_to_device     (no counterpart)                         ... its pixels on the GPU, csrc/jpeg_engine.hip
 
 Grayscale files are kept single-channel: ``cv2.imread`` would replicate the channel three times and BGR2GRAY of
 equal channels returns the value itself (3735 + 19235 + 9798 = 2^15), so the net input is identical.
 JPEG decoders differ between libjpeg builds by +-1 in places; PNG / TIFF inputs are bit-identical.
+
+``--device_jpeg True`` of run_net_post_processing splits a baseline JPEG's decode: only the Huffman decode stays on a CPU
+(``load_jpeg_coefficients``), dequantisation, inverse DCT, chroma upsampling and colour conversion run on the device
+(``jpeg_page_to_device``) and give the bytes Pillow with libjpeg-turbo gives; every file that path refuses (progressive,
+CMYK, an orientation to apply, other samplings, damaged streams ...) is decoded by ``load_image_bgr`` as before.
 """
 import ctypes as C
 import os
@@ -50,6 +57,27 @@ def _host_lib():
         except OSError:
             _host = False
     return _host
+
+
+_host_jpeg = None
+
+
+def _host_jpeg_lib():
+    """libasep_host.so with the JPEG entry points bound, or False: a library built before they existed still serves the PNG path"""
+    global _host_jpeg
+    if _host_jpeg is None:
+        lib = _host_lib()
+        try:
+            if not lib:
+                raise AttributeError
+            lib.asep_jpeg_probe.restype = C.c_int
+            lib.asep_jpeg_probe.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p]
+            lib.asep_jpeg_entropy_decode.restype = C.c_int
+            lib.asep_jpeg_entropy_decode.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+            _host_jpeg = lib
+        except AttributeError:
+            _host_jpeg = False
+    return _host_jpeg
 
 
 _deflate = None
@@ -154,6 +182,134 @@ def _load_png_plain(path):
     except MemoryError:                                     # let Pillow report what it makes of the file
         return None
     return out if rc == 0 else None
+
+
+# ---- baseline JPEG scans: Huffman decode in C (csrc/host_jpeg.c), pixels on the device (csrc/jpeg_engine.hip) ------------------------
+class JpegInfo(C.Structure):
+    """asep_jpeg_info (include/asep_host.h)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32),
+                ("mcus_w", C.c_int32), ("mcus_h", C.c_int32), ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3),
+                ("qt_index", C.c_int32 * 3), ("restart_interval", C.c_int32), ("reserved", C.c_int32), ("coef_bytes", C.c_int64)]
+
+
+_JPEG_MAGIC = b"ASEPJPG1"
+_JPEG_HEAD = 640                     # magic, JpegInfo, the four tables, padding: the coefficients start 128-byte aligned
+
+
+class JpegPage:
+    """The entropy-decoded half of a JPEG scan in ONE uint8 buffer (``packed``: what a decode worker puts into its page-locked
+    slot): the frame description, the quantisation tables (uint16 [4, 64], natural order) and the quantised coefficients
+    (int16, per component [blocks_h, blocks_w, 64] in natural order, DC prediction undone).  Views, no copies."""
+
+    def __init__(self, packed):
+        self.packed = packed
+        self.info = JpegInfo.from_buffer(packed, len(_JPEG_MAGIC))
+        self.qt = packed[8 + C.sizeof(JpegInfo):8 + C.sizeof(JpegInfo) + 512].view(np.uint16).reshape(4, 64)
+        self.coef = packed[_JPEG_HEAD:_JPEG_HEAD + self.info.coef_bytes].view(np.int16)
+
+    width = property(lambda self: self.info.width)
+    height = property(lambda self: self.info.height)
+    ncomp = property(lambda self: self.info.ncomp)
+    hs = property(lambda self: self.info.hs)
+    vs = property(lambda self: self.info.vs)
+    qt_index = property(lambda self: list(self.info.qt_index)[:self.info.ncomp])
+
+    def components(self):
+        """the coefficients per component: int16 [blocks_h, blocks_w, 64]"""
+        out, off = [], 0
+        for c in range(self.ncomp):
+            n = self.info.blocks_h[c] * self.info.blocks_w[c] * 64
+            out.append(self.coef[off:off + n].reshape(self.info.blocks_h[c], self.info.blocks_w[c], 64))
+            off += n
+        return out
+
+
+def as_jpeg_page(image):
+    """a JpegPage if ``image`` is one or the ``packed`` buffer of one (as it comes out of a decode slot), else None"""
+    if isinstance(image, JpegPage):
+        return image
+    if isinstance(image, np.ndarray) and image.ndim == 1 and image.dtype == np.uint8 and image.size >= _JPEG_HEAD \
+            and image[:8].tobytes() == _JPEG_MAGIC:
+        return JpegPage(np.require(image, requirements=['C', 'W']))
+    return None
+
+
+def load_jpeg_coefficients(path):
+    """A baseline JPEG (8-bit Huffman; gray, or YCbCr 4:4:4 / 4:2:2 / 4:2:0 in one scan, no orientation to apply) -> JpegPage; None
+    for everything else -- not a JPEG, a flavour host_jpeg.c refuses (among them a block with more energy than 8-bit samples give, where libjpeg-turbo's 16-bit
+    SIMD arithmetic and the device's would part), a damaged stream, libasep_host.so not built: such a file goes
+    through ``load_image_bgr``, so no file decodes differently than without this path."""
+    lib = _host_jpeg_lib()
+    if not lib:
+        return None
+    try:
+        with open(path, "rb") as f:
+            if f.read(2) != b"\xff\xd8":
+                return None
+            raw = b"\xff\xd8" + f.read()
+    except OSError:
+        return None
+    info = JpegInfo()
+    if lib.asep_jpeg_probe(raw, len(raw), C.byref(info)) != 0:
+        return None
+    # a header may announce any size: the same sanity check as for PNG (Pillow's decompression-bomb limit; the probe has already refused a
+    # frame with more blocks than the file's bytes could code)
+    limit = Image.MAX_IMAGE_PIXELS
+    if limit is not None and info.width * info.height > limit:
+        return None
+    try:
+        packed = np.empty(_JPEG_HEAD + info.coef_bytes, dtype=np.uint8)
+    except MemoryError:
+        return None
+    packed[:8] = np.frombuffer(_JPEG_MAGIC, dtype=np.uint8)
+    packed[8:_JPEG_HEAD] = 0
+    C.memmove(packed.ctypes.data + 8, C.byref(info), C.sizeof(info))
+    page = JpegPage(packed)
+    if lib.asep_jpeg_entropy_decode(raw, len(raw), C.byref(info), page.coef.ctypes.data, page.qt.ctypes.data) != 0:
+        return None
+    return page
+
+
+def jpeg_page_to_device(page, device=0, order="bgr", stream=None, lane=0):
+    """JpegPage -> uint8 torch tensor on ``device``, the bytes Pillow decodes: [H,W] for a one-component page whatever the order, else
+    [H,W,3] for ``order`` "bgr" (``load_image_bgr``) / "rgb" (the relation net's page_u8), [H,W] for "gray" (``load_image_gray``).
+    The coefficients are uploaded and the kernels queued on ``stream`` (a torch stream; None = the current one); ``page`` must stay
+    valid until the upload has run.  ``lane``: the scratch arena (``image_ops._workspace``), one per stream."""
+    import torch
+    from . import _lib
+    tdev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    lib, ws = image_ops._workspace(tdev.index or 0, lane)
+    with torch.cuda.device(tdev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(tdev)):
+        sp = C.c_void_p(torch.cuda.current_stream(tdev).cuda_stream)
+        d_coef = torch.empty(page.coef.size, dtype=torch.int16, device=tdev)
+        d_coef.copy_(torch.from_numpy(page.coef), non_blocking=True)
+        shape = (page.height, page.width) if page.ncomp == 1 or order == "gray" else (page.height, page.width, 3)
+        out = torch.empty(shape, dtype=torch.uint8, device=tdev)
+        _lib.check(lib.asep_jpeg_pixels_dev(ws, C.byref(page.info), d_coef.data_ptr(), page.qt.ctypes.data, _lib.JPEG_ORDERS[order],
+                                            out.data_ptr(), sp), "asep_jpeg_pixels_dev")
+        d_coef.record_stream(torch.cuda.current_stream(tdev))
+    global jpeg_device_pages
+    jpeg_device_pages += 1
+    return out
+
+
+jpeg_device_pages = 0                # pages jpeg_page_to_device has queued in this process
+
+
+def jpeg_device_launches():
+    """the kernels the calling thread's last device JPEG call launched (asep_jpeg_last_launches)"""
+    from . import _lib
+    lib = _lib.load_library()
+    buf = C.create_string_buffer(256)
+    lib.asep_jpeg_last_launches(buf, len(buf))
+    return buf.value.decode().split()
+
+
+def load_image_bgr_or_jpeg(path_to_image):
+    """DecodePool loader of ``--device_jpeg True``: the ``packed`` buffer of a JpegPage where the device path takes the file, else what
+    ``load_image_bgr`` returns"""
+    page = load_jpeg_coefficients(path_to_image)
+    return page.packed if page is not None else load_image_bgr(path_to_image)
 
 
 def load_image_bgr(path_to_image):

@@ -11,16 +11,19 @@ import argparse
 import multiprocessing as mp
 import os
 
+from .cli_flags import str2bool
 from .path_util import load_list_file
 
 MAX_SUBLIST_SIZE = 50
 
 
-def run_separator(image_list, path_to_pb, fixed_height, scaling_factor, threshold, gpu_devices='0', host_workers=0):
+def run_separator(image_list, path_to_pb, fixed_height, scaling_factor, threshold, gpu_devices='0', host_workers=0,
+                  device_jpeg=False):
     from .separator_net_post_processor import SeparatorNetPostProcessor
     import time
     proc = SeparatorNetPostProcessor(image_list, path_to_pb, fixed_height, scaling_factor, threshold,
                                      gpu_devices=gpu_devices, host_workers=host_workers)
+    proc.device_jpeg = device_jpeg
     t0 = time.perf_counter()
     proc.run()
     _owner_stats(gpu_devices, len(image_list), time.perf_counter() - t0, host_workers, proc)
@@ -40,7 +43,7 @@ def _owner_stats(gpu, n_pages, seconds, host_workers, proc):
 
 
 def run_heading(image_list, path_to_pb, fixed_height=900, scaling_factor=1, is_heading_threshold=0.4,
-                weight_dict=None, thresh_dict=None, text_line_percentage=0.8, gpu_devices='0', host_workers=0):
+                weight_dict=None, thresh_dict=None, text_line_percentage=0.8, gpu_devices='0', host_workers=0, device_jpeg=False):
     from .heading_net_post_processor import HeadingNetPostProcessor
     if thresh_dict is None:
         thresh_dict = {'net_thresh': 1.0, 'stroke_width_thresh': 1.0, 'text_height_thresh': 0.9, 'sw_th_thresh': 0.9}
@@ -49,6 +52,7 @@ def run_heading(image_list, path_to_pb, fixed_height=900, scaling_factor=1, is_h
     proc = HeadingNetPostProcessor(image_list, path_to_pb, fixed_height, scaling_factor, weight_dict, is_heading_threshold,
                                    thresh_dict, text_line_percentage)
     proc.host_workers = host_workers
+    proc.device_jpeg = device_jpeg
     proc.run(gpu_device=gpu_devices)
 
 
@@ -67,6 +71,10 @@ def build_parser():
                         help="Which information should be processed, e.g. headings or separator.")
     parser.add_argument("--threshold", type=float, required=False, default=0.05,
                         help="Threshold for binarization of net output.")
+    parser.add_argument("--device_jpeg", type=str2bool, required=False, default=False,
+                        help="True: baseline JPEG scans are only Huffman-decoded on the host; dequantisation, inverse DCT, chroma "
+                             "upsampling and colour conversion run on the GPU and give the same bytes.  Files that path does not take "
+                             "(PNG, TIFF, progressive / CMYK / rotated / damaged JPEG ...) are decoded as without the flag.")
     return parser
 
 
@@ -80,16 +88,16 @@ def build_sub_lists(image_path_list, num_processes):
     return [image_path_list[i: i + size_sub_lists] for i in range(0, len(image_path_list), size_sub_lists)]
 
 
-def _worker(mode, sub_lists, path_to_pb, fixed_height, scaling_factor, threshold, gpu, host_workers=0):
+def _worker(mode, sub_lists, path_to_pb, fixed_height, scaling_factor, threshold, gpu, host_workers=0, device_jpeg=False):
     # one model per GPU owner: its sub-lists are processed as one stream so that the decode workers never run dry at a
     # sub-list boundary (the 50-page cap of :70 only bounded the memory of the reference's per-run image lists)
     images = [p for sub in sub_lists for p in sub]
     if mode == 'separator':
         run_separator(images, path_to_pb, fixed_height, scaling_factor, threshold, gpu_devices=str(gpu),
-                      host_workers=host_workers)
+                      host_workers=host_workers, device_jpeg=device_jpeg)
     else:
         run_heading(images, path_to_pb, fixed_height, scaling_factor, 0.4, None, None, 0.8, gpu_devices=str(gpu),
-                    host_workers=host_workers)
+                    host_workers=host_workers, device_jpeg=device_jpeg)
 
 
 def main(argv=None):
@@ -121,11 +129,12 @@ def main(argv=None):
     host_workers = max(1, args.num_processes) // n_workers            # decode / XML workers per owner (<= 1: inline)
     per_worker = [sub_lists[i::n_workers] for i in range(n_workers)]
     if n_workers == 1:
-        _worker(mode, per_worker[0], args.path_to_pb, fixed_height, args.scaling_factor, args.threshold, devices[0], host_workers)
+        _worker(mode, per_worker[0], args.path_to_pb, fixed_height, args.scaling_factor, args.threshold, devices[0], host_workers,
+                args.device_jpeg)
         return 0
     ctx = mp.get_context("spawn")
     procs = [ctx.Process(target=_worker, args=(mode, per_worker[i], args.path_to_pb, fixed_height,
-                                               args.scaling_factor, args.threshold, devices[i], host_workers))
+                                               args.scaling_factor, args.threshold, devices[i], host_workers, args.device_jpeg))
              for i in range(n_workers)]
     for p in procs:
         p.start()

@@ -12,7 +12,7 @@ import time
 
 import numpy as np
 
-from . import _lib, image_ops, polygonize
+from . import _lib, image_io, image_ops, polygonize
 from .host_util import rescale_points
 from .net_post_processing_helper import _device_of, get_scaling_factor, load_graph
 from .path_util import get_page_path, load_list_file
@@ -28,6 +28,9 @@ class RegionNetPostProcessor:
         # worker processes that decode images ahead of the GPU and write PAGE-XML behind it (host_pipeline.py);
         # 0 / 1 = everything inline in this process
         self.host_workers = host_workers
+        # True: baseline JPEG scans are only entropy-decoded on the host (image_io.load_jpeg_coefficients); their pixels are computed on the
+        # device in front of resize + gray.  Every other file, and every JPEG that path refuses, is decoded as without the flag.
+        self.device_jpeg = False
         self.device_seconds = 0.0      # wall time this process spent inside the device stages (upload .. results back)
         self.wait_seconds = 0.0        # ... waiting for the next decoded image
         self.first_page_seconds = None # run() start -> first decoded image in hand (worker start-up, slot page-locking)
@@ -108,10 +111,16 @@ class RegionNetPostProcessor:
         tickets = []
         with self._on_lane(lane) as (lib, ws, tdev, stream, sp):
             for image in images:
-                image = np.require(image, dtype=np.uint8, requirements=['C', 'W'])   # Pillow hands out read-only views
-                if image.ndim == 2:
-                    image = image[:, :, None]
-                H, W, Cn = image.shape
+                jpeg = image_io.as_jpeg_page(image) if reuse is None else None
+                if jpeg is not None:                                 # --device_jpeg: coefficients in, the page is computed on the device
+                    H, W, Cn = jpeg.height, jpeg.width, jpeg.ncomp
+                elif reuse is not None:
+                    H, W, Cn = reuse[len(tickets)]["d_img"].shape
+                else:
+                    image = np.require(image, dtype=np.uint8, requirements=['C', 'W'])   # Pillow hands out read-only views
+                    if image.ndim == 2:
+                        image = image[:, :, None]
+                    H, W, Cn = image.shape
                 sc = get_scaling_factor(H, W, self.scaling_factor, fixed_height=self.fixed_height)
                 h, w = image_ops.scaled_size(H, W, sc)
                 # the upload is queued like everything else (a page is 0.3 ms of PCIe; a copy on a second stream ended up behind the
@@ -119,8 +128,12 @@ class RegionNetPostProcessor:
                 # page's upload has run -- DecodePool(hold=...) guarantees that for its slots, pageable arrays are staged by the runtime
                 # before the call returns
                 if reuse is None:
-                    d_img = torch.empty((H, W, Cn), dtype=torch.uint8, device=tdev)
-                    d_img.copy_(torch.from_numpy(image), non_blocking=True)
+                    if jpeg is not None:
+                        d_img = image_io.jpeg_page_to_device(jpeg, tdev, "bgr", stream, lane=0 if lane == 0 else 10 + lane)
+                        d_img = d_img.reshape(H, W, Cn)
+                    else:
+                        d_img = torch.empty((H, W, Cn), dtype=torch.uint8, device=tdev)
+                        d_img.copy_(torch.from_numpy(image), non_blocking=True)
                     t = {"sc": sc, "size": (h, w), "device": tdev.index, "d_img": d_img, "uploaded": torch.cuda.Event()}
                     t["uploaded"].record(stream)
                 else:
@@ -177,6 +190,15 @@ class RegionNetPostProcessor:
             raise RuntimeError(f"the decoder yielded {n_seen} of {n_paths} pages")
         for item in pending:
             finish(*item)
+
+
+def jpeg_decode_options(paths, device_jpeg):
+    """DecodePool arguments of ``--device_jpeg``: the loader that hands out coefficients where it can, and slots that hold them (int16
+    per sample: up to twice the widest decoded page, plus the padding to whole MCUs and the tables)"""
+    if not device_jpeg:
+        return {}
+    from .host_pipeline import needed_slot_bytes, SLOT_BYTES_MAX
+    return {"loader": "load_image_bgr_or_jpeg", "slot_bytes": min(SLOT_BYTES_MAX, 2 * needed_slot_bytes(paths) + (2 << 20))}
 
 
 def write_separator_page(page_path, image_path, fixed_height, scaling_factor, polygons_dict):
@@ -332,7 +354,8 @@ class SeparatorNetPostProcessor(RegionNetPostProcessor):
         pipelined = self.host_workers > 1 and not self.keep_outputs
         reg, unreg = pin_callbacks(self.device) if pipelined else (None, None)
         group = self.PAGE_GROUP if pipelined else 1
-        decode = DecodePool(self.image_paths, self.host_workers if pipelined else 0, register=reg, unregister=unreg, hold=group + 1)
+        decode = DecodePool(self.image_paths, self.host_workers if pipelined else 0, register=reg, unregister=unreg, hold=group + 1,
+                            **jpeg_decode_options(self.image_paths, self.device_jpeg))
         with WritePool(self.host_workers if pipelined else 0) as writers:
             self._run_groups(decode, len(self.image_paths), group, self.PAGE_LANES if pipelined else 1,
                              lambda images, lane: self.enqueue_group(images, edges_only=not self.keep_outputs, lane=lane),

@@ -27,6 +27,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "asep_host_jpeg.h" /* asep_jpeg_info */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -769,6 +771,26 @@ double asep_seg_eval_last_kernel_us(const asep_seg_eval* h);
 /* The kernels launched through the handle since the start of its last asep_seg_eval_pages_dev, one name per line
  * ("seg_eval_kernel<C,thr>", "seg_blend_kernel").  Copies at most max_bytes - 1 characters; returns the text's length. */
 long asep_seg_eval_last_launches(const asep_seg_eval* h, char* buf, size_t max_bytes);
+
+/* ---- JPEG pixels (added under ABI 12; csrc/jpeg_engine.hip, a code object of its own) ------------------------------------------
+ * The parallel half of a JPEG decode: asep_jpeg_probe / asep_jpeg_entropy_decode of asep_host.h give the frame description, the quantised
+ * coefficients (per component int16 [blocks_h][blocks_w][64], natural order) and the quantisation tables (uint16 [4][64], natural order,
+ * HOST memory in both forms); here they become the bytes libjpeg-turbo's defaults produce: dequantisation and the accurate integer
+ * inverse DCT, "fancy" chroma upsampling over the real downsampled size, YCbCr -> RGB in 16-bit fixed point, cropped to width x height.
+ * A one-component page gives [H, W] whatever the order.  A three-component page gives [H, W, 3] B, G, R (what load_image_bgr returns),
+ * [H, W, 3] R, G, B (the relation net's page_u8), or for ASEP_JPEG_ORDER_GRAY [H, W] with the BGR2GRAY weights of load_image_gray.
+ * Refused with ASEP_ERR_ARG: a description whose block grid, sampling or coefficient size does not follow from its width and height.
+ * asep_jpeg_pixels_dev queues on `stream` (scratch: p's arena, so one handle serves one stream); asep_jpeg_pixels uploads `coef`,
+ * runs on p's stream, copies `out` back and synchronises. */
+#define ASEP_JPEG_ORDER_GRAY 0
+#define ASEP_JPEG_ORDER_BGR 1
+#define ASEP_JPEG_ORDER_RGB 2
+int asep_jpeg_pixels_dev(asep_post* p, const asep_jpeg_info* info, const int16_t* d_coef, const uint16_t* qt, int order, uint8_t* d_out,
+                         void* stream);
+int asep_jpeg_pixels(asep_post* p, const asep_jpeg_info* info, const int16_t* coef, const uint16_t* qt, int order, uint8_t* out);
+/* The kernels the calling thread's last call of the two above launched, one name per line ("jpeg_idct_kernel", "jpeg_colour_kernel").
+ * Copies at most max_bytes - 1 characters and returns the text's length. */
+long asep_jpeg_last_launches(char* buf, size_t max_bytes);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,9 @@ long asep_png_unfilter(const uint8_t* filtered, long rows, long stride, int bpp,
 /* out[i] = {in[3i+2], in[3i+1], in[3i]}: RGB rows -> BGR (cv2's channel order), n pixels. */
 void asep_rgb_to_bgr(const uint8_t* in, size_t n, uint8_t* out);
 
+/* The entropy decode of baseline JPEG scans (csrc/host_jpeg.c, the same library): asep_jpeg_info and its two entry points. */
+#include "asep_host_jpeg.h"
+
 #ifdef __cplusplus
 }
 #endif
