@@ -732,7 +732,7 @@ void run_res8ws(asep_aru* m, bool up, const Res8Args& a, const std::vector<bool>
         bytes += r.pixels() * ((up ? 64.0 : 4.0) + 32.0 + (p.pool ? 8.0 : 0.0));
     }
     if (!n) return;
-    const int band = walk_band(strip_rows, m->num_cus, 4);   // (four waves per CU)
+    const int band = walk_band(strip_rows, m->num_cus, up ? R8WS_UP_WAVES_PER_CU : R8WS_DOWN_WAVES_PER_CU);
     for (int i = 0; i < n; ++i) {
         Res8WSProb& p = wa.p[i];
         p.band = band;
@@ -1345,6 +1345,7 @@ TL det_cnn(asep_aru* m, const TL& imgs, const std::vector<std::string>& names, c
         }
         skips.push_back(d);
         publish(d, "_unet_down_" + std::to_string(l) + "_conv");
+        if (pool) publish(pooled, "_unet_down_" + std::to_string(l) + "_pool");
         u = pool ? pooled : d;
     }
     for (int l = n - 2; l >= 0; --l) {
@@ -2148,6 +2149,15 @@ long asep_aru_profile_report(asep_aru* m, char* buf, size_t buflen) {
 double asep_aru_flops(const asep_aru* m, int H, int W) {
     if (!m) return 0.0;
     return flops_impl(m->cfg, H, W);
+}
+
+int asep_aru_walker_occupancy(int up) {
+    ASEP_GUARD_BEGIN
+    int blocks = 0;
+    if (up) { ASEP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, res8ws_kernel<true>, 64, 0)); }
+    else { ASEP_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, res8ws_kernel<false>, 64, 0)); }
+    return blocks;
+    ASEP_GUARD_END
 }
 
 }  // extern "C"

@@ -9,15 +9,18 @@
 //   * the filters are split once on the host; the fragments of all three parts of every filter the wave uses are loaded once per item
 //     into the accumulator half of the register file (UP: 45 fragments = 180 AGPRs, DOWN: 27), the MFMAs take them from there;
 //   * every intermediate stage is stored as its three part planes, split ONCE in the producing epilogue (after the ReLU, on fp32);
-//   * the raw conv1 result t stays fp32 (a ring of 16 rows x 24 pixels x 32 bytes) and is added in the stage-3 epilogue, then the ReLU;
+//   * UP: the raw conv1 result t stays fp32 (a ring of 16 rows x 24 pixels x 32 bytes) and is added in the stage-3 epilogue, then the ReLU;
+//     DOWN: no t ring.  The stage-3 epilogue computes t again for its two rows out of the image ring, with the instruction sequence of the
+//     conv1 stage (72 FMAs a pixel against about 1800 split products in the tail), so the sum t + conv is bit for bit what a t ring gave;
 //   * UP conv1 (16 -> 8 over [skip, deconv]) reads its fp32 input rows straight from global memory one iteration ahead (the lane's window
 //     pixel, two rows per iteration and source), splits them once and carries the two lower rows to the next iteration in registers;
 //   * DOWN conv1 (1 -> 8) stays on fp32 FMAs in res8v_down_kernel's order (bias, taps ky-major): t is bit-identical to res8v's; the image
-//     rows pass through a four-row fp32 ring, standardised like res8v;
+//     rows pass through a sixteen-row fp32 ring (the depth: at NI in the kernel), standardised like res8v;
 //   * the DOWN block's 2 x 2 max pool runs on the fp32 stage-3 results (rows inside the lane, the pixel pair across lane ^ 32).
-// LDS per wave (bytes): stage rings of 4 rows x 3 parts x 30 / 28 / 26 pixels x 16 = 5760 + 5376 + 4992, raw t 12288, a 16-byte dump,
-// DOWN: + the image ring 4 x 32 x 4 = 512 -> 28.4 / 28.9 KB.  Registers: UP 234 VGPRs + 196 AGPRs (filters), one wave per SIMD = four per
-// CU; DOWN 92 + 128, two waves per SIMD by registers, five per CU by LDS.
+// LDS per wave (bytes): stage rings of 4 rows x 3 parts x 30 / 28 / 26 pixels x 16 = 5760 + 5376 + 4992, a 16-byte dump, UP: + raw t 12288
+// = 28432 (27.8 KB); DOWN: + the image ring 16 x 32 x 4 = 2048 = 18192 (17.8 KB).  Registers (compiler's resource report): UP 234 VGPRs + 196
+// AGPRs (filters), one wave per SIMD = four per CU; DOWN 98 VGPRs + 128 AGPRs, no scratch, two waves per SIMD = eight per CU, which the LDS now
+// holds as well (8 x 17.8 KB of 160 KB; with the t ring it was 28.9 KB a wave and five waves per CU).
 //
 // The walker covers columns [32, 32 + 24 n) x rows [16, y_end) of a page like res8w_kernel.  The frame around it is computed by the
 // vector-ALU kernels (res8v_*_kernel) over the work units that touch it, launched BEFORE the walker: the walker then overwrites the part
@@ -69,17 +72,28 @@ __device__ __forceinline__ void r8ws_split4(f32x4 v, u32x2& h, u32x2& m, u32x2& 
     h = u32x2{h0, h1}; m = u32x2{m0, m1}; l = u32x2{l0, l1};
 }
 
+// waves (one-wave blocks) of an instance that a CU holds, for the launcher's band plan: UP one per SIMD by registers, DOWN two per SIMD by
+// registers and LDS
+constexpr int R8WS_UP_WAVES_PER_CU = 4, R8WS_DOWN_WAVES_PER_CU = 8;
+
 template <bool UP>
 __global__ __launch_bounds__(64, 1) void res8ws_kernel(const Res8WSArgs a) {
     constexpr int TW = R8W_TW;
     constexpr int W0 = TW + 6, W1 = TW + 4, W2 = TW + 2;                      // 30, 28, 26 pixels
-    constexpr int NR = 4, NT = 16;                                             // stage ring rows, raw t rows
+    constexpr int NR = 4, NT = 16;                                             // stage ring rows, raw t rows (UP)
+    // DOWN: rows of the image ring.  Iteration k's stage 3 finishes item rows 2 k - 8, 2 k - 7 (row r = image row Ya - 4 + r) and recomputes
+    // their t from the 3 x 3 windows around them, item rows 2 k - 9 .. 2 k - 6; conv1 of the same iteration stores pair k + 1, item rows
+    // 2 k + 2, 2 k + 3.  So rows 2 k - 9 .. 2 k + 3 are live, whole pairs 2 k - 10 .. 2 k + 3: 14 rows.  16 = the next power of two, so
+    // that a row's place is its number under a mask like the stage rings' (256 bytes more; eight waves fit per CU either way).
+    constexpr int NI = 16;
     constexpr int PL0 = W0 * 16, PL1 = W1 * 16, PL2 = W2 * 16;                 // bytes of one part plane of a ring row
-    constexpr int IMB = UP ? 0 : 4 * 32 * 4;                                   // DOWN: image ring of 4 rows x 32 fp32
-    constexpr int R0_OFF = IMB, R1_OFF = R0_OFF + NR * 3 * PL0, R2_OFF = R1_OFF + NR * 3 * PL1, TC_OFF = R2_OFF + NR * 3 * PL2,
-                  TRASH = TC_OFF + NT * TW * 32, LDSB = TRASH + 16;
-    // (a fragment read of lanes j >= the tile's pairs runs up to 4 pixels past its row: into the next plane, row or region, never past tc)
-    static_assert(LDSB <= 30 * 1024, "four waves per CU with room to spare");
+    // the region behind the stage rings: UP raw t, DOWN the image ring of NI rows x 32 fp32
+    constexpr int R0_OFF = 0, R1_OFF = R0_OFF + NR * 3 * PL0, R2_OFF = R1_OFF + NR * 3 * PL1, TC_OFF = R2_OFF + NR * 3 * PL2, IM_OFF = TC_OFF,
+                  TRASH = TC_OFF + (UP ? NT * TW * 32 : NI * 32 * 4), LDSB = TRASH + 16;
+    // (a fragment read of lanes j >= the tile's pairs takes units up to 33 of its row, 8 pixels past an r2 row: into the next plane, row or
+    //  region, never past the region behind the stage rings)
+    static_assert(TRASH - TC_OFF >= (34 - W2) * 16, "the fragment reads of the last r2 plane stay inside the array");
+    static_assert(UP ? LDSB <= 30 * 1024 : LDSB <= 20 * 1024, "UP: four waves per CU with room to spare; DOWN: eight");
     __shared__ __attribute__((aligned(16))) unsigned char lds[LDSB];
 
     const int lane = threadIdx.x;
@@ -137,7 +151,7 @@ __global__ __launch_bounds__(64, 1) void res8ws_kernel(const Res8WSArgs a) {
         lo = *reinterpret_cast<const f32x4*>(q);
         hi = *reinterpret_cast<const f32x4*>(q + 4);
     };
-    // DOWN: a pair of image rows = 64 fp32 = one per lane (row lane >> 5, column x0 - 4 + (lane & 31)); the ring holds image rows mod 4
+    // DOWN: a pair of image rows = 64 fp32 = one per lane (row lane >> 5, column x0 - 4 + (lane & 31)); the ring holds item rows mod NI
     float mean = 0.f, inv = 1.f;
     if constexpr (!UP) {
         if (P.stats) { mean = P.stats[0]; inv = P.stats[1]; }
@@ -145,8 +159,8 @@ __global__ __launch_bounds__(64, 1) void res8ws_kernel(const Res8WSArgs a) {
     const float* __restrict__ imp = P.img;
     const size_t ioff0 = (size_t)(Ya - 4 + (lane >> 5)) * (size_t)W + (size_t)(x0 - 4 + (lane & 31));
     auto iload = [&](int p) { return imp[ioff0 + (size_t)p * 2 * (size_t)W]; };
-    float* const iring = reinterpret_cast<float*>(lds);
-    auto istore = [&](float v, int p) { iring[(p & 1) * 64 + lane] = (v - mean) * inv; };   // pair p -> ring rows 2 p, 2 p + 1 (mod 4)
+    float* const iring = reinterpret_cast<float*>(lds + IM_OFF);
+    auto istore = [&](float v, int p) { iring[((2 * p) & (NI - 1)) * 32 + lane] = (v - mean) * inv; };   // pair p -> ring rows 2 p, 2 p + 1 (mod NI)
     float w1v[UP ? 1 : 36];
     if constexpr (!UP) {
 #pragma unroll
@@ -154,6 +168,23 @@ __global__ __launch_bounds__(64, 1) void res8ws_kernel(const Res8WSArgs a) {
 #pragma unroll
             for (int o = 0; o < 4; ++o) w1v[t * 4 + o] = a.w1f[t * 8 + ch + o];
     }
+    // conv1 of the lane's four channels at ring column cb (+ kx) of item rows r0, r0 + 1 (window rows r0 - 1 .. r0 + 2), in
+    // res8v_down_kernel's order (bias, taps ky-major).  The conv1 stage and the stage-3 epilogue both call it: the same instruction sequence
+    // on the same ring values, so the t that stage 3 adds is bit for bit the t whose ReLU went into the stage rings.
+    auto conv1_down = [&](int r0, int cb, f32x4& ra, f32x4& rb) {
+        if constexpr (!UP)
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const float va = iring[((r0 - 1 + ky) & (NI - 1)) * 32 + cb + kx], vb = iring[((r0 + ky) & (NI - 1)) * 32 + cb + kx];
+#pragma unroll
+                for (int o = 0; o < 4; ++o) {
+                    ra[o] = fmaf(va, w1v[(ky * 3 + kx) * 4 + o], ra[o]);
+                    rb[o] = fmaf(vb, w1v[(ky * 3 + kx) * 4 + o], rb[o]);
+                }
+            }
+    };
 
     const int p_last = nb / 2 + 3;                                            // input pairs 0 .. p_last: rows Ya - 4 .. Ya + nb + 3
     u32x4 cin[2][2][3] = {};                                                  // UP: split rows 0, 1 of conv1's window [row][source][part]
@@ -184,8 +215,9 @@ __global__ __launch_bounds__(64, 1) void res8ws_kernel(const Res8WSArgs a) {
     const int cs = r8w_swz(c) * 16;
     const bool v0 = j < W0 / 2, v1 = j < W1 / 2, v2 = j < W2 / 2;
     const bool tvalid = c >= 3 && c < 3 + TW;
-    const int tcol = (tvalid ? c - 3 : 0) * 32 + ch * 4;     // conv1's lane writes its half of raw t at pixel c - 3
-    const int trd = min(c, TW - 1) * 32 + ch * 4;            // stage 3 reads it at its output pixel c
+    const int tcol = (tvalid ? c - 3 : 0) * 32 + ch * 4;     // UP: conv1's lane writes its half of raw t at pixel c - 3
+    const int trd = min(c, TW - 1) * 32 + ch * 4;            // UP: stage 3 reads it at its output pixel c
+    const int tcb = min(c, TW - 1) + 3;                      // DOWN: stage 3 recomputes it at conv1's pixel c + 3 (ring columns tcb .. tcb + 2 <= 28)
     const bool ost = j < TW / 2;
     float* __restrict__ const outp = P.out;
     float* __restrict__ const poolp = P.pool;
@@ -215,13 +247,18 @@ __global__ __launch_bounds__(64, 1) void res8ws_kernel(const Res8WSArgs a) {
         const int i4 = (2 * k) & (NR - 1), i16 = (2 * k) & (NT - 1);
         const bool do_c1 = k < nb / 2 + 3, do_s1 = k >= 2 && k < nb / 2 + 4, do_s2 = k >= 4 && k < nb / 2 + 5, do_s3 = k >= 6;
 
-        // ---- stage 3: output rows Ya - 12 + 2 k, + 1 = conv of r2 rows i4 - 9 .. i4 - 6, + raw t, ReLU; DOWN: the 2 x 2 pool ----
+        // ---- stage 3: output rows Ya - 12 + 2 k, + 1 = conv of r2 rows i4 - 9 .. i4 - 6, + raw t (DOWN: recomputed), ReLU; DOWN: the 2 x 2 pool ----
         if (do_s3) {
             u32x4 q[4][3];
 #pragma unroll
             for (int r = 0; r < 4; ++r) ring_read(R2_OFF, PL2, (i4 + r - 9) & (NR - 1), q[r]);
-            const f32x4 t0 = *reinterpret_cast<const f32x4*>(lds + TC_OFF + ((i16 - 8) & (NT - 1)) * TW * 32 + trd);
-            const f32x4 t1 = *reinterpret_cast<const f32x4*>(lds + TC_OFF + ((i16 - 7) & (NT - 1)) * TW * 32 + trd);
+            f32x4 t0 = bias1, t1 = bias1;
+            if constexpr (UP) {
+                t0 = *reinterpret_cast<const f32x4*>(lds + TC_OFF + ((i16 - 8) & (NT - 1)) * TW * 32 + trd);
+                t1 = *reinterpret_cast<const f32x4*>(lds + TC_OFF + ((i16 - 7) & (NT - 1)) * TW * 32 + trd);
+            } else {
+                conv1_down(2 * k - 8, tcb, t0, t1);          // item rows 2 k - 8, 2 k - 7, conv1's pixel c + 3
+            }
             f32x4 va = biasw[2], vb = biasw[2];
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) {
@@ -283,7 +320,7 @@ __global__ __launch_bounds__(64, 1) void res8ws_kernel(const Res8WSArgs a) {
             }
             store_parts(ra, rb, R1_OFF, PL1, v1, (i4 - 2) & (NR - 1), (i4 - 1) & (NR - 1));
         }
-        // ---- conv1: item rows 2 k + 1, 2 k + 2 (image rows Ya - 3 + 2 k, + 1) -> relu(t) parts into r0 rows i4 + 1, i4 + 2, raw t into tc ----
+        // ---- conv1: item rows 2 k + 1, 2 k + 2 (image rows Ya - 3 + 2 k, + 1) -> relu(t) parts into r0 rows i4 + 1, i4 + 2, UP: raw t into tc ----
         if (do_c1) {
             f32x4 ra = bias1, rb = bias1;
             if constexpr (UP) {
@@ -322,26 +359,17 @@ __global__ __launch_bounds__(64, 1) void res8ws_kernel(const Res8WSArgs a) {
 #pragma unroll
                         for (int p = 0; p < 3; ++p) cin[r][s][p] = x2[r][s][p];
             } else {
-                // pair k + 1 -> the ring (its rows 2 k + 2, 2 k + 3 replace those of pair k - 1), pair k + 2 is requested; then the taps of the
+                // pair k + 1 -> the ring (its rows 2 k + 2, 2 k + 3 replace those of pair k - 7, which stage 3 left behind two iterations ago), pair k + 2 is requested; then the taps of the
                 // lane's pixel c (ring column c + kx) in res8v_down_kernel's order
                 istore(inx, k + 1);
                 if (k + 2 <= p_last) inx = iload(k + 2);
-                const int cb = min(c, 29);
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const float va = iring[((2 * k + ky) & 3) * 32 + cb + kx], vb = iring[((2 * k + 1 + ky) & 3) * 32 + cb + kx];
-#pragma unroll
-                        for (int o = 0; o < 4; ++o) {
-                            ra[o] = fmaf(va, w1v[(ky * 3 + kx) * 4 + o], ra[o]);
-                            rb[o] = fmaf(vb, w1v[(ky * 3 + kx) * 4 + o], rb[o]);
-                        }
-                    }
+                conv1_down(2 * k + 1, min(c, 29), ra, rb);
             }
-            if (tvalid) {
-                *reinterpret_cast<f32x4*>(lds + TC_OFF + ((i16 + 1) & (NT - 1)) * TW * 32 + tcol) = ra;
-                *reinterpret_cast<f32x4*>(lds + TC_OFF + ((i16 + 2) & (NT - 1)) * TW * 32 + tcol) = rb;
+            if constexpr (UP) {
+                if (tvalid) {
+                    *reinterpret_cast<f32x4*>(lds + TC_OFF + ((i16 + 1) & (NT - 1)) * TW * 32 + tcol) = ra;
+                    *reinterpret_cast<f32x4*>(lds + TC_OFF + ((i16 + 2) & (NT - 1)) * TW * 32 + tcol) = rb;
+                }
             }
             store_parts(ra, rb, R0_OFF, PL0, v0, (i4 + 1) & (NR - 1), (i4 + 2) & (NR - 1));
         }

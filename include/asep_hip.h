@@ -154,6 +154,10 @@ long asep_aru_profile_report(asep_aru* m, char* buf, size_t buflen);
 /* Algorithmic FLOPs (2*MAC of conv/deconv layers) of one forward at H x W. */
 double asep_aru_flops(const asep_aru* m, int H, int W);
 
+/* Blocks of the f32s level-0 strip walker (res8ws_kernel<up != 0>, one wave each) that the runtime keeps resident on a compute unit
+ * (hipOccupancyMaxActiveBlocksPerMultiprocessor); negative on error. */
+int asep_aru_walker_occupancy(int up);
+
 /* ---- GNN relation predictor ------------------------------------------------------------------ */
 typedef struct asep_gnn_cfg {
     int32_t struct_size;           /* = sizeof(asep_gnn_cfg) of the header the caller was compiled / written against */
