@@ -154,6 +154,11 @@ SIGNATURES = {
     "asep_alpha_shapes": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "asep_alpha_shapes_last_kernel_us": (C.c_double, [C.c_int]),
     "asep_alpha_shapes_lds_points": (C.c_int, []),
+    "asep_delaunay": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "asep_alpha_shapes_points": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "asep_delaunay_last_kernel_us": (C.c_double, []),
+    "asep_delaunay_lds_points": (C.c_int, []),
+    "asep_delaunay_max_extent": (C.c_int, []),
     "asep_measure_run": (C.c_longlong, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
     "asep_measure_fetch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "asep_measure_last_kernel_us": (C.c_double, [C.c_int]),

@@ -1,7 +1,7 @@
 """CLI mirror of ``article_separation/run_textregion_generation.py`` (+ ``textregion_generation/textregion_generation.py``).
 
     python -m citlab_article_separation_new_amd.run_textregion_generation --path_to_xml_lst pages.lst \\
-        [--des_dist 50] [--max_d 100] [--alpha 75] [--num_threads N] [--device_regions True]
+        [--des_dist 50] [--max_d 100] [--alpha 75] [--num_threads N] [--device_regions True [--device_triangulation True]]
 
 One alpha-shape TextRegion per article of each PAGE-XML file (one per line for lines without an article id), with
 reading orders for the regions and their lines; the existing text regions are replaced and the file is rewritten in
@@ -11,6 +11,12 @@ distances use the default des_dist of 5.  This process owns the GPU (one distanc
 ``--use_java_code`` is accepted with either value: the results always follow the reference's Python path.
 ``--device_regions True`` (off by default): the host triangulates each article of a group of pages once and one engine
 call gives the alpha shapes of the whole group (textblock.create_text_regions_pages); files and printed lines are the same.
+``--device_triangulation True`` (off by default, needs ``--device_regions True``): that call triangulates the articles too, the
+host no longer calls scipy.  The printed lines are the same; every region is the same polygon as without the flag (the same
+cyclic vertex sequence after the same alpha retries) but NOT the same bytes: it is written from its vertex with the smallest
+(y, x) in the direction of positive shoelace area (textblock.canonical_ring), where the default path starts at an edge that
+Qhull's internal order picks.  Articles with a bounding box over 16383 px, more than 4096 points, fewer than 3 distinct points
+or all points on one line go through the host function.
 """
 import io
 import sys
@@ -43,7 +49,21 @@ def build_parser():
     p.add_argument("--device_regions", type=cli_flags.str2bool, default=False,
                    help="alpha shapes of all articles of a group of pages in one GPU call behind the host triangulation; "
                         "same files and printed lines")
+    p.add_argument("--device_triangulation", type=cli_flags.str2bool, default=False,
+                   help="with --device_regions True: the GPU call triangulates the articles too (no scipy).  Same printed lines "
+                        "and the same polygons (same cyclic vertex sequence, same alpha retries), written from the vertex with "
+                        "the smallest (y, x) in the direction of positive shoelace area: not the same bytes as the default path.  "
+                        "Articles with a box over 16383 px or more than 4096 points and degenerate ones take the host function")
     return p
+
+
+def parse_flags(argv):
+    """the known flags of ``argv``; --device_triangulation without --device_regions is a usage error"""
+    parser = build_parser()
+    flags = parser.parse_known_args(argv)[0]
+    if flags.device_triangulation and not flags.device_regions:
+        parser.error("--device_triangulation True needs --device_regions True")
+    return flags
 
 
 def read_page(path, des_dist):
@@ -142,7 +162,8 @@ def process(paths, flags, device=0, log=print, start=1):
                 outs = [io.StringIO() for _ in ready]
                 regions = textblock.create_text_regions_pages(
                     [(g[1], g[2]) for _, g in ready], flags.alpha,
-                    [lambda s, o=o: print(s, file=o) for o in outs], device, pool)
+                    [lambda s, o=o: print(s, file=o) for o in outs], device, pool,
+                    device_triangulation=getattr(flags, "device_triangulation", False))
                 staged = {k: g for k, g in zip(good, geoms) if isinstance(g, Exception)}
                 staged.update({k: (g[0], r, o) for (k, g), r, o in zip(ready, regions, outs)})
 
@@ -170,7 +191,7 @@ def process(paths, flags, device=0, log=print, start=1):
 
 
 def main(argv=None):
-    flags = build_parser().parse_known_args(sys.argv[1:] if argv is None else argv)[0]
+    flags = parse_flags(sys.argv[1:] if argv is None else argv)
     if flags.path_to_xml_file:
         paths = [flags.path_to_xml_file]
     elif flags.path_to_xml_lst:

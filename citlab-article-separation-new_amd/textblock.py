@@ -4,12 +4,25 @@
     neighbour_lists          dbscan_baselines.py:253-307 region_query, all rows    -> asep_textblock_neighbours
     DBSCAN labels            dbscan_baselines.py:113-251, 309-333                  (host, over the device neighbour lists)
     text regions             textregion_generation.py:17-172                       (host alpha shapes; device_regions=True:
-                                                                                    host triangulation -> asep_alpha_shapes)
+                                                                                    host triangulation -> asep_alpha_shapes;
+                                                                                    device_triangulation=True as well:
+                                                                                    asep_alpha_shapes_points, no scipy)
 
 Every function takes a BATCH of pages (one list of polygons per page) so that one kernel launch serves all of them.
 The results are those of the reference's Python path; the Java class the reference can call instead
 (``use_java_code=True``) is not used.  No CPU fallback: without the HIP library every device function
 raises ``AsepError``.
+
+``device_triangulation=True`` promises the same polygon as the host function, not the same bytes.  The host function starts its
+ring at the first boundary edge in Qhull's triangle order, which nobody can restate; the device triangulates in its own order.  So
+that path gives the same cyclic vertex sequence as ``textblock_geometry.alpha_shape`` after the same number of alpha retries,
+written in a canonical form (``canonical_ring``): from the vertex with the smallest (y, x), in the direction of positive shoelace
+area sum(x_i * y_i+1 - x_i+1 * y_i) (counter-clockwise with y up, clockwise as a page is displayed), the first vertex repeated at
+the end.  Cocircular points may be split differently than Qhull splits them; the triangles of such a cell share one circumcircle
+and are accepted or refused together, so the boundary can differ only where a circumradius lies within rounding of an alpha that
+is tried (supposed from the geometry; tests/test_delaunay_host.py checks it on its inputs).  Articles the device does not
+triangulate (a bounding box over ``delaunay_max_extent()`` pixels, fewer than 3 distinct points, all points on one line) and
+articles of more than ``DEVICE_TRIANGULATION_MAX_POINTS`` points go through the host function one by one.
 """
 import ctypes as C
 import math
@@ -249,13 +262,18 @@ def synthetic_coords(xs, ys, dist):
     return list(zip([int(x) for x in xs] + xsh[::-1], [int(y) for y in ys] + ysh[::-1]))
 
 
-def create_text_regions(art_lines, line_geom, alpha=75, log=print, device_regions=False, device=0):
+def create_text_regions(art_lines, line_geom, alpha=75, log=print, device_regions=False, device=0, device_triangulation=False):
     """textregion_generation.py:129-172.  ``art_lines``: {article id or None: [line id, ...]} in the page's order;
     ``line_geom``: {line id: ((xs, ys) normed polygon, interline distance)}.  Returns
     [("tr_<n>", boundary points, [line id, ...], n), ...].  ``device_regions``: the alpha shapes behind the
-    triangulations come from one engine call (create_text_regions_pages), the result and the logged lines are the same."""
+    triangulations come from one engine call (create_text_regions_pages), the result and the logged lines are the same.
+    ``device_triangulation`` (needs ``device_regions``): the triangulations come from that call too; the same polygons in
+    the canonical form of ``canonical_ring`` (module docstring), the same logged lines."""
+    if device_triangulation and not device_regions:
+        raise ValueError("device_triangulation needs device_regions")
     if device_regions:
-        res = create_text_regions_pages([(art_lines, line_geom)], alpha, [log], device)[0]
+        res = create_text_regions_pages([(art_lines, line_geom)], alpha, [log], device,
+                                        device_triangulation=device_triangulation)[0]
         if isinstance(res, Exception):
             raise res
         return res
@@ -400,15 +418,19 @@ def _triangulate_or_error(points):
         return e
 
 
-def create_text_regions_pages(pages, alpha=75, logs=None, device=0, pool=None):
+def create_text_regions_pages(pages, alpha=75, logs=None, device=0, pool=None, device_triangulation=False):
     """create_text_regions for a group of pages with ONE engine call: ``pages`` = [(art_lines, line_geom), ...].
     The host triangulates every article once (``pool.map`` when a thread pool is given); the circumradii, the boundary
     edges, the walk and the alpha * 1.2 retries run on the device.  Returns per page the regions or the exception the
-    host path raises for it; ``logs[k]`` receives the page's retry lines, one per retry, in the host's order."""
+    host path raises for it; ``logs[k]`` receives the page's retry lines, one per retry, in the host's order.
+    ``device_triangulation``: the point lists go up once and the engine triangulates them too (no scipy); rings in the
+    canonical form, articles the device flags through the host function (module docstring)."""
     import sys
     logs = logs or [print] * len(pages)
     max_retries = sys.getrecursionlimit()
     plans = [_region_jobs(art, geom, alpha) for art, geom in pages]
+    if device_triangulation:
+        return _regions_from_points(plans, alpha, logs, max_retries, device)
     flat = [pts for jobs, _ in plans for pts, _ in jobs]
     tris = iter((pool.map if pool is not None else lambda f, xs: list(map(f, xs)))(_triangulate_or_error, flat))
     tris = [[next(tris) for _ in jobs] for jobs, _ in plans]
@@ -437,6 +459,138 @@ def create_text_regions_pages(pages, alpha=75, logs=None, device=0, pool=None):
                         raise RecursionError(f"alpha_shape: no single boundary after {retries} increases of alpha")
                     bp = points[ring].tolist()
                 bp.append(bp[0])
+                regions.append(("tr_" + str(counter), [[int(j) for j in i] for i in bp], members, counter))
+            if end is not None:
+                raise end
+            out.append(regions)
+        except Exception as e:      # noqa: BLE001 (the page's error, as the host path raises it)
+            out.append(e)
+    return out
+
+
+# ---- text regions (device triangulation and alpha shapes) --------------------------------------------------------------
+
+def canonical_ring(ring):
+    """A closed ring [[x, y], ...] (first vertex repeated at the end) in the canonical form of the device triangulation path:
+    the same cycle from the vertex with the smallest (y, x), in the direction of positive shoelace area."""
+    pts = [[int(x), int(y)] for x, y in ring[:-1]]
+    n = len(pts)
+    area2 = sum(pts[i][0] * pts[(i + 1) % n][1] - pts[(i + 1) % n][0] * pts[i][1] for i in range(n))
+    if area2 < 0:
+        pts.reverse()
+    k = min(range(n), key=lambda i: (pts[i][1], pts[i][0]))
+    pts = pts[k:] + pts[:k]
+    return pts + [list(pts[0])]
+
+
+def delaunay_lds_points():
+    """the largest article (in points) the device triangulates in LDS"""
+    return int(_lib.load_library().asep_delaunay_lds_points())
+
+
+def delaunay_max_extent():
+    """the largest bounding-box extent (max - min, per axis) of an article the device triangulates"""
+    return int(_lib.load_library().asep_delaunay_max_extent())
+
+
+def last_delaunay_kernel_us():
+    """device time of the last triangulation kernel of this thread, microseconds"""
+    return float(_lib.load_library().asep_delaunay_last_kernel_us())
+
+
+def _packed_points(fn, arts):
+    """(pt_off int32 [n + 1], points int32 (max(sum, 1), 2)) of a list of (n, 2) integer arrays"""
+    pt_off = np.zeros(len(arts) + 1, np.int64)
+    pt_off[1:] = np.cumsum([len(a) for a in arts])
+    if pt_off[-1] > np.iinfo(np.int32).max // 20:
+        raise ValueError(f"{fn}: {pt_off[-1]} points exceed one call")
+    pts = np.zeros((max(int(pt_off[-1]), 1), 2), np.int32)
+    for k, p in enumerate(arts):
+        p = np.asarray(p)
+        if p.ndim != 2 or p.shape[1] != 2 or not np.issubdtype(p.dtype, np.integer) \
+                or (p.size and (p.min() < -2 ** 31 or p.max() >= 2 ** 31)):
+            raise ValueError(f"{fn}: article {k} needs (n, 2) integer points within int32")
+        pts[pt_off[k]:pt_off[k + 1]] = p
+    return pt_off.astype(np.int32), pts
+
+
+def delaunay_device(arts, device=0):
+    """One asep_delaunay call.  ``arts``: a list of (n, 2) integer arrays.  Returns per article (simplices (T, 3) int32,
+    neighbors (T, 3) int32, status): scipy.spatial.Delaunay's two tables, or no triangles and a status other than 0."""
+    lib, h = _handle(device)
+    pt_off, pts = _packed_points("delaunay_device", arts)
+    cap_off = (2 * pt_off).astype(np.int32)
+    cap = int(cap_off[-1])
+    simp = np.zeros((max(cap, 1), 3), np.int32)
+    neigh = np.zeros((max(cap, 1), 3), np.int32)
+    res = np.zeros((2, max(len(arts), 1)), np.int32)
+    _lib.check(lib.asep_delaunay(h, len(arts), _ptr(pt_off), _ptr(pts), _ptr(cap_off), _ptr(simp), _ptr(neigh), _ptr(res[0]),
+                                 _ptr(res[1])), "asep_delaunay")
+    return [(simp[cap_off[k]:cap_off[k] + res[0, k]].copy(), neigh[cap_off[k]:cap_off[k] + res[0, k]].copy(), int(res[1, k]))
+            for k in range(len(arts))]
+
+
+def alpha_shapes_points_device(pages, max_retries=None, device=0):
+    """One asep_alpha_shapes_points call.  ``pages``: per page a list of articles (points (n, 2) int, alpha0).  Returns per
+    page a list of (ring: point indices of the boundary cycle without the repeated first one, from the first boundary edge of
+    the device's triangle order; retries; failed; status of the triangulation)."""
+    import sys
+    lib, h = _handle(device)
+    arts = [a for pg in pages for a in pg]
+    art_off = np.zeros(len(pages) + 1, np.int32)
+    art_off[1:] = np.cumsum([len(pg) for pg in pages])
+    pt_off, pts = _packed_points("alpha_shapes_points_device", [a[0] for a in arts])
+    alpha0 = np.array([float(a[1]) for a in arts] + [0.0], np.float64)
+    ring = np.zeros(max(int(pt_off[-1]), 1), np.int32)
+    res = np.zeros((4, max(len(arts), 1)), np.int32)
+    _lib.check(lib.asep_alpha_shapes_points(h, len(pages), _ptr(art_off), _ptr(pt_off), _ptr(pts), _ptr(alpha0),
+                                            int(sys.getrecursionlimit() if max_retries is None else max_retries),
+                                            _ptr(ring), _ptr(res[0]), _ptr(res[1]), _ptr(res[2]), _ptr(res[3])),
+               "asep_alpha_shapes_points")
+    out, k = [], 0
+    for pg in pages:
+        rows = []
+        for _ in pg:
+            rows.append((ring[pt_off[k]:pt_off[k] + res[0, k]].copy(), int(res[1, k]), bool(res[2, k]), int(res[3, k])))
+            k += 1
+        out.append(rows)
+    return out
+
+
+# One workgroup inserts an article's points one after the other, with passes over all its triangles for each: quadratic in the
+# article's points (0.9 ms at 280, 4.4 ms at 896, 22 ms at 2,000, 76 ms at 4,000, 255 ms at 7,681 points on an MI355X, where Qhull
+# takes 0.33 / 1.5 / 3.6 / 7.8 / 15.5 ms).  The device wins by triangulating a call's hundreds of articles side by side, so an
+# article stays on it while it cannot hold up a call of 32 pages for longer than the host needs for a few of those pages.
+DEVICE_TRIANGULATION_MAX_POINTS = 4096
+
+
+def _regions_from_points(plans, alpha, logs, max_retries, device):
+    """create_text_regions_pages behind the plans when the device triangulates too"""
+    def on_device(pts):
+        return 3 < pts.shape[0] <= DEVICE_TRIANGULATION_MAX_POINTS
+    dev_pages = [[(pts, alpha) for pts, _ in jobs if on_device(pts)] if alpha > 0 else [] for jobs, _ in plans]
+    rings = alpha_shapes_points_device(dev_pages, max_retries, device) if any(dev_pages) else [[] for _ in plans]
+    out = []
+    for (jobs, end), got, log in zip(plans, rings, logs):
+        got = iter(got)
+        regions = []
+        try:
+            for counter, (points, members) in enumerate(jobs):
+                assert alpha > 0, "alpha value has to be greater than zero"
+                if points.shape[0] <= 3:
+                    bp = points.tolist()              # util.py:620: returned as they are
+                    bp.append(bp[0])
+                else:
+                    ring, retries, failed, status = next(got) if on_device(points) else (None, 0, False, -1)
+                    if status != 0:                   # not triangulated on the device: the host function, with what it prints or raises
+                        bp = canonical_ring(geo.alpha_shape(points, alpha, log))
+                    else:
+                        for _ in range(retries):
+                            log(RETRY_LINE)
+                        if failed:
+                            raise RecursionError(f"alpha_shape: no single boundary after {retries} increases of alpha")
+                        bp = points[ring].tolist()
+                        bp = canonical_ring(bp + [bp[0]])
                 regions.append(("tr_" + str(counter), [[int(j) for j in i] for i in bp], members, counter))
             if end is not None:
                 raise end

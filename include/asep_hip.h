@@ -525,6 +525,38 @@ double asep_alpha_shapes_last_kernel_us(int which);
 /* The largest article (in points) whose vertex tables the boundary kernel keeps in LDS; larger ones use global scratch. */
 int asep_alpha_shapes_lds_points(void);
 
+/* The triangulation itself on the device: one workgroup per article builds the Delaunay triangulation of the article's
+ * points (incremental Bowyer-Watson in (x, y) order, exact integer predicates) in scipy's two tables: out_simplices[t] the
+ * corners, counter-clockwise, out_neighbors[t][j] the triangle opposite corner j or -1, indices local to the article.
+ * Article a holds the points pt_off[a] .. pt_off[a+1]-1 and owns the triangles tri_off_cap[a] .. tri_off_cap[a+1]-1 of the
+ * two output tables, which must have room for 2n - 5 triangles of its n >= 3 points; out_ntri[a] of them are filled, the rest
+ * are zeros.  Exact duplicates of a point are in no triangle (the first of them is); cocircular points get one of their valid
+ * triangulations, which depends on the article's points alone; collinear points of the hull are corners of proper triangles.
+ * out_status[a]: 0 triangulated; 1 fewer than 3 distinct points; 2 all points on one line; 3 the bounding box is wider or
+ * taller than asep_delaunay_max_extent() (the predicates are exact in int64 up to there); 4 / 5 an inconsistent table / no room
+ * (neither is reachable through this interface).  A status other than 0 leaves out_ntri[a] = 0: the caller triangulates such an
+ * article itself.  Offsets and room are checked before anything is allocated or launched; ASEP_ERR_ARG names the article and the
+ * reason.  A result does not depend on what else shares the call. */
+int asep_delaunay(asep_post* p, int n_articles, const int32_t* pt_off, const int32_t* points, const int32_t* tri_off_cap,
+                  int32_t* out_simplices, int32_t* out_neighbors, int32_t* out_ntri, int32_t* out_status);
+/* asep_alpha_shapes without tri_off / simplices / neighbors: the articles are triangulated on the device as by asep_delaunay
+ * and the circumradius and boundary kernels read those tables where they are.  Same outputs (the ring starts at the first
+ * boundary edge of the DEVICE's triangle order, so it is the reference's cycle, not its start or direction), plus
+ * out_status[a] as above.  An article with a status other than 0 has no triangles: the boundary kernel, which this call leaves
+ * as it is, finds no edge in any of its max_retries rounds, so it comes back with out_failed[a] = 1, out_len[a] = 0 and
+ * out_retries[a] = max_retries, after max_retries short rounds of device time (they run beside the other articles' workgroups).
+ * The call's triangle count never comes to the host: the stream is synchronised once, at the end. */
+int asep_alpha_shapes_points(asep_post* p, int n_pages, const int32_t* art_off, const int32_t* pt_off, const int32_t* points,
+                             const double* alpha0, int max_retries, int32_t* out_ring, int32_t* out_len, int32_t* out_retries,
+                             int32_t* out_failed, int32_t* out_status);
+/* Device time in microseconds of the triangulation kernel of the calling thread's last asep_delaunay or
+ * asep_alpha_shapes_points call (the latter also sets asep_alpha_shapes_last_kernel_us). */
+double asep_delaunay_last_kernel_us(void);
+/* The largest article (in points) whose working tables the triangulation keeps in LDS; larger ones use global scratch. */
+int asep_delaunay_lds_points(void);
+/* The largest bounding-box extent (max - min, per axis) of an article the device triangulates. */
+int asep_delaunay_max_extent(void);
+
 /* ---- article separation measure (eval_measure.py count_rel_hits / count_rel_hits_list, Python path) -------------------
  * Batched over file pairs on the asep_post handle.  Truth and reco (hypothesis) polygons are NORMED baselines in the
  * layout of asep_textblock_interline_dists (points as (x, y) int32 pairs, poly_off, boxes {x, y, w, h}); file k holds
