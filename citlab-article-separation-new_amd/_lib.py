@@ -190,6 +190,10 @@ SIGNATURES = {
     "asep_jpeg_pixels_dev": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P]),
     "asep_jpeg_pixels": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
     "asep_jpeg_last_launches": (C.c_long, [C.c_char_p, C.c_size_t]),
+    "asep_jpeg_entropy_dev": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "asep_jpeg_entropy": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "asep_jpeg_entropy_last_rounds": (C.c_int, [_P]),
+    "asep_jpeg_entropy_set_max_rounds": (None, [C.c_int]),
 }
 
 _lib = None

@@ -408,3 +408,101 @@ int asep_jpeg_entropy_decode(const uint8_t* bytes, size_t n, const asep_jpeg_inf
     memcpy(qt, h.qt, sizeof h.qt);
     return 0;
 }
+
+/* ---- the scan prepared for the device's entropy decode (csrc/jpeg_huffman_kernels.h) ------------------------------------------------ */
+#define MAX_SCAN_FILE ((size_t)1 << 28)                              /* bit positions are 32-bit on the device */
+
+static int64_t segments_of(const asep_jpeg_info* in) {
+    const int64_t mcus = (int64_t)in->mcus_w * in->mcus_h;
+    return in->restart_interval > 0 ? (mcus + in->restart_interval - 1) / in->restart_interval : 1;
+}
+
+int asep_jpeg_scan_sizes(const asep_jpeg_info* info, size_t n, size_t* scan_capacity, size_t* n_segments) {
+    if (!info || !scan_capacity || !n_segments) return ASEP_JPEG_ARG;
+    *scan_capacity = 0, *n_segments = 0;
+    if (info->mcus_w < 1 || info->mcus_h < 1 || info->mcus_w > 8192 || info->mcus_h > 8192 || info->restart_interval < 0) return ASEP_JPEG_ARG;
+    if (n >= MAX_SCAN_FILE) return ASEP_JPEG_REFUSED;
+    *scan_capacity = (n + 3) & ~(size_t)3;                           /* the scan is a part of the file */
+    *n_segments = (size_t)segments_of(info);
+    return 0;
+}
+
+static void copy_table(asep_jpeg_huff* d, const huff_table* t) {
+    memset(d, 0, sizeof *d);
+    memcpy(d->look, t->look, sizeof d->look);
+    memcpy(d->maxcode, t->maxcode, sizeof d->maxcode);
+    memcpy(d->valoff, t->valoff, sizeof t->valoff);                  /* [0..16]; [17] stays 0 */
+    memcpy(d->sym, t->sym, sizeof d->sym);
+    d->nsym = t->nsym;
+}
+
+static int scan_prepare(const uint8_t* b, size_t n, const asep_jpeg_info* info, uint8_t* scan, size_t cap, size_t* scan_bytes,
+                        asep_jpeg_segment* segments, size_t max_segments, size_t* n_segments, asep_jpeg_scan_tables* tables) {
+    jpeg_header h;
+    int rc = parse_header(b, n, &h);
+    if (rc) return rc;
+    if (memcmp(&h.info, info, sizeof *info) != 0) return ASEP_JPEG_ARG;      /* not the probe of these bytes */
+    if (n >= MAX_SCAN_FILE) return ASEP_JPEG_REFUSED;
+    const asep_jpeg_info* in = &h.info;
+    const int64_t mcus = (int64_t)in->mcus_w * in->mcus_h, nseg = segments_of(in);
+    const int64_t per_mcu = in->ncomp == 1 ? 1 : in->hs * in->vs + 2;
+    if ((uint64_t)nseg > max_segments) return ASEP_JPEG_ARG;
+    size_t pos = h.scan_begin, out = 0;
+    int expect = 0;
+    for (int64_t s = 0; s < nseg; ++s) {
+        const size_t first = out;
+        while (pos < n) {                                            /* up to a marker, fill bytes in front of one, or the end */
+            const uint8_t v = b[pos];
+            if (v == 0xFF) {
+                if (n - pos < 2 || b[pos + 1] != 0) break;
+                pos += 2;
+            } else {
+                pos += 1;
+            }
+            if (out >= cap) return ASEP_JPEG_ARG;
+            scan[out++] = v;
+        }
+        if (n - pos < 2) return ASEP_JPEG_DAMAGED;                   /* b[pos] is 0xFF here */
+        while (n - pos >= 2 && b[pos + 1] == 0xFF) ++pos;
+        if (n - pos < 2) return ASEP_JPEG_DAMAGED;
+        const int m = b[pos + 1];
+        pos += 2;
+        const int64_t first_mcu = s * (int64_t)in->restart_interval;
+        const int64_t n_mcus = s == nseg - 1 ? mcus - first_mcu : in->restart_interval;
+        /* a block takes at least two bits, and the decoder wants the last of them in the segment's last byte */
+        if (out == first || (int64_t)(out - first) * 8 < n_mcus * per_mcu * 2) return ASEP_JPEG_DAMAGED;
+        segments[s].byte_offset = (uint32_t)first;
+        segments[s].byte_length = (uint32_t)(out - first);
+        segments[s].first_mcu = (uint32_t)first_mcu;
+        segments[s].n_mcus = (uint32_t)n_mcus;
+        if (s == nseg - 1) {
+            if (m == 0xDA || m == 0xDC || m == 0xC4 || m == 0xDB || m == 0xDD) return ASEP_JPEG_REFUSED;   /* further scans, DNL */
+            if (m != 0xD9) return ASEP_JPEG_DAMAGED;
+        } else {
+            if (m != 0xD0 + expect) return ASEP_JPEG_DAMAGED;
+            expect = (expect + 1) & 7;
+        }
+    }
+    *scan_bytes = out;
+    while (out & 3) {                                                /* whole 32-bit words for the kernels */
+        if (out >= cap) return ASEP_JPEG_ARG;
+        scan[out++] = 0;
+    }
+    *n_segments = (size_t)nseg;
+    for (int c = 0; c < 3; ++c) {
+        const int k = c < in->ncomp ? c : 0;
+        copy_table(&tables->dc[c], &h.dc[h.td[k]]);
+        copy_table(&tables->ac[c], &h.ac[h.ta[k]]);
+    }
+    memcpy(tables->qt, h.qt, sizeof h.qt);
+    return 0;
+}
+
+int asep_jpeg_scan_prepare(const uint8_t* bytes, size_t n, const asep_jpeg_info* info, uint8_t* scan, size_t scan_capacity,
+                           size_t* scan_bytes, asep_jpeg_segment* segments, size_t max_segments, size_t* n_segments,
+                           asep_jpeg_scan_tables* tables) {
+    if (!bytes || !info || !scan || !scan_bytes || !segments || !n_segments || !tables) return ASEP_JPEG_ARG;
+    const int rc = scan_prepare(bytes, n, info, scan, scan_capacity, scan_bytes, segments, max_segments, n_segments, tables);
+    if (rc) *scan_bytes = 0, *n_segments = 0;
+    return rc;
+}

@@ -406,13 +406,16 @@ class HeadingNetPostProcessor(RegionNetPostProcessor):
 
                 decode = DecodePool(self.image_paths, n_workers, register=reg, unregister=unreg,
                                     hold=self.PAGE_GROUP + 1 if pipelined else 3,
-                                    **jpeg_decode_options(self.image_paths, self.device_jpeg))
+                                    **jpeg_decode_options(self.image_paths, self.device_jpeg, self.device_huffman))
                 if pipelined:
                     # behind the GPU: the next group is uploaded and queued before a page's lines are measured (the measuring calls
                     # wait for their small kernels; the chip has the next nets to work on meanwhile)
                     self._run_groups(decode, len(self.image_paths), self.PAGE_GROUP, self.PAGE_LANES, self.enqueue_group, finish)
                 else:
                     for image_path, image in decode:
+                        (_, image), = self._resolve_scans([(image_path, image)])
+                        if isinstance(image, image_io.DevicePage):   # --device_huffman: as below, the device's page comes back
+                            image = image.d_img.cpu().numpy()
                         jpeg = image_io.as_jpeg_page(image)
                         if jpeg is not None:                 # --device_jpeg: this path works on host pages, so the device's page comes back
                             image = image_io.jpeg_page_to_device(jpeg, self.device, "bgr").cpu().numpy()

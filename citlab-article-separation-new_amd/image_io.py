@@ -6,6 +6,8 @@
     load_and_scale_image    helper:28-33                             decode here, scale + gray on the GPU
     load_jpeg_coefficients  (no counterpart)                         baseline JPEG: Huffman decode only, csrc/host_jpeg.c
     jpeg_page_to_device     (no counterpart)                         ... its pixels on the GPU, csrc/jpeg_engine.hip
+    load_jpeg_scan          (no counterpart)                         baseline JPEG: stuffing and markers removed only, csrc/host_jpeg.c
+    jpeg_scan_to_device     (no counterpart)                         ... Huffman decode and pixels on the GPU, csrc/jpeg_huffman_kernels.h
 
 Grayscale files are kept single-channel: ``cv2.imread`` would replicate the channel three times and BGR2GRAY of
 equal channels returns the value itself (3735 + 19235 + 9798 = 2^15), so the net input is identical.
@@ -300,9 +302,227 @@ def jpeg_device_launches():
     """the kernels the calling thread's last device JPEG call launched (asep_jpeg_last_launches)"""
     from . import _lib
     lib = _lib.load_library()
-    buf = C.create_string_buffer(256)
+    buf = C.create_string_buffer(4096)
     lib.asep_jpeg_last_launches(buf, len(buf))
     return buf.value.decode().split()
+
+
+# ---- baseline JPEG scans, entropy decode on the device as well (--device_huffman; csrc/jpeg_huffman_kernels.h) ------------------------------
+class JpegHuff(C.Structure):
+    """asep_jpeg_huff (include/asep_host_jpeg_scan.h)"""
+    _fields_ = [("look", C.c_uint16 * 512), ("maxcode", C.c_int32 * 18), ("valoff", C.c_int32 * 18), ("sym", C.c_uint8 * 256),
+                ("nsym", C.c_int32), ("reserved", C.c_int32)]
+
+
+class JpegScanTables(C.Structure):
+    """asep_jpeg_scan_tables"""
+    _fields_ = [("dc", JpegHuff * 3), ("ac", JpegHuff * 3), ("qt", (C.c_uint16 * 64) * 4)]
+
+
+JPEG_SEGMENT = np.dtype([("byte_offset", "<u4"), ("byte_length", "<u4"), ("first_mcu", "<u4"), ("n_mcus", "<u4")])   # asep_jpeg_segment
+JPEG_STATUS_DAMAGED, JPEG_STATUS_REFUSED, JPEG_STATUS_NOT_CONVERGED = 1, 2, 4     # ASEP_JPEG_STATUS_* of include/asep_hip.h
+_SCAN_MAGIC = b"ASEPJSC1"
+_SCAN_TABLES = 128                   # magic, JpegInfo, scan_bytes, n_segments (two int64), padding; then the tables, the segments, the bytes
+_SCAN_SEGMENTS = _SCAN_TABLES + C.sizeof(JpegScanTables)
+
+
+class JpegScan:
+    """A baseline JPEG scan prepared for the device's entropy decode, in ONE uint8 buffer (``packed``, as a decode worker puts it into
+    its slot): the frame description, the Huffman and quantisation tables, the segments (restart intervals) and the entropy-coded
+    bytes without stuffing and markers.  Views, no copies."""
+
+    def __init__(self, packed):
+        self.packed = packed
+        self.info = JpegInfo.from_buffer(packed, len(_SCAN_MAGIC))
+        counts = packed[8 + C.sizeof(JpegInfo):8 + C.sizeof(JpegInfo) + 16].view(np.int64)
+        self.scan_bytes, self.n_segments = int(counts[0]), int(counts[1])
+        self.tables = JpegScanTables.from_buffer(packed, _SCAN_TABLES)
+        self.qt = packed[_SCAN_SEGMENTS - 512:_SCAN_SEGMENTS].view(np.uint16).reshape(4, 64)
+        first = _SCAN_SEGMENTS + 16 * self.n_segments
+        self.segments = packed[_SCAN_SEGMENTS:first].view(JPEG_SEGMENT)
+        self.scan = packed[first:first + (self.scan_bytes + 3) // 4 * 4]       # whole 32-bit words, zeros behind the last byte
+
+    width = property(lambda self: self.info.width)
+    height = property(lambda self: self.info.height)
+    ncomp = property(lambda self: self.info.ncomp)
+
+
+def as_jpeg_scan(image):
+    """a JpegScan if ``image`` is one or the ``packed`` buffer of one, else None"""
+    if isinstance(image, JpegScan):
+        return image
+    if isinstance(image, np.ndarray) and image.ndim == 1 and image.dtype == np.uint8 and image.size >= _SCAN_SEGMENTS \
+            and image[:8].tobytes() == _SCAN_MAGIC:
+        return JpegScan(np.require(image, requirements=['C', 'W']))
+    return None
+
+
+def _host_scan_lib():
+    """libasep_host.so with asep_jpeg_scan_prepare bound, or False"""
+    lib = _host_jpeg_lib()
+    if lib and not hasattr(lib, "_scan_bound"):
+        try:
+            lib.asep_jpeg_scan_sizes.restype = C.c_int
+            lib.asep_jpeg_scan_sizes.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+            lib.asep_jpeg_scan_prepare.restype = C.c_int
+            lib.asep_jpeg_scan_prepare.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                   C.c_size_t, C.c_void_p, C.c_void_p]
+            lib._scan_bound = True
+        except AttributeError:
+            lib._scan_bound = False
+    return lib if lib and lib._scan_bound else False
+
+
+def prepare_jpeg_scan(raw):
+    """the bytes of a JPEG file -> (JpegScan, 0), or (None, the negative code of asep_jpeg_probe / asep_jpeg_scan_sizes / _prepare)"""
+    lib = _host_scan_lib()
+    if not lib:
+        raise RuntimeError(f"{_HOST_LIB} is not built or does not export asep_jpeg_scan_prepare")
+    info = JpegInfo()
+    rc = lib.asep_jpeg_probe(raw, len(raw), C.byref(info))
+    if rc != 0:
+        return None, rc
+    limit = Image.MAX_IMAGE_PIXELS                                   # as load_jpeg_coefficients
+    if limit is not None and info.width * info.height > limit:
+        return None, -1
+    cap, nseg = C.c_size_t(), C.c_size_t()
+    rc = lib.asep_jpeg_scan_sizes(C.byref(info), len(raw), C.byref(cap), C.byref(nseg))
+    if rc != 0:
+        return None, rc
+    first = _SCAN_SEGMENTS + 16 * nseg.value
+    packed = np.zeros(first + cap.value, dtype=np.uint8)
+    used, got = C.c_size_t(), C.c_size_t()
+    rc = lib.asep_jpeg_scan_prepare(raw, len(raw), C.byref(info), packed.ctypes.data + first, cap.value, C.byref(used),
+                                    packed.ctypes.data + _SCAN_SEGMENTS, nseg.value, C.byref(got), packed.ctypes.data + _SCAN_TABLES)
+    if rc != 0:
+        return None, rc
+    assert got.value == nseg.value and used.value <= cap.value
+    packed[:8] = np.frombuffer(_SCAN_MAGIC, dtype=np.uint8)
+    C.memmove(packed.ctypes.data + 8, C.byref(info), C.sizeof(info))
+    packed[8 + C.sizeof(info):8 + C.sizeof(info) + 16].view(np.int64)[:] = (used.value, got.value)
+    return JpegScan(packed[:first + (used.value + 3) // 4 * 4]), 0
+
+
+def load_jpeg_scan(path):
+    """A baseline JPEG -> JpegScan, after one pass over its markers and bytes; None where ``load_jpeg_coefficients`` returns None
+    before its entropy decode (not a JPEG, a refused flavour, a damaged marker structure, libasep_host.so not built).  What only the
+    entropy decode finds shows in the status of ``jpeg_scan_to_device``."""
+    if not _host_scan_lib():
+        return None
+    try:
+        with open(path, "rb") as f:
+            if f.read(2) != b"\xff\xd8":
+                return None
+            raw = b"\xff\xd8" + f.read()
+    except OSError:
+        return None
+    try:
+        return prepare_jpeg_scan(raw)[0]
+    except MemoryError:
+        return None
+
+
+def jpeg_scan_entropy_to_device(scan, device=0, stream=None, lane=0, subseq_bits=0):
+    """JpegScan -> (int16 coefficients on the device, laid out as ``JpegPage.coef``; int32 status tensor [1] on the device).  The
+    scan's bytes are uploaded and the entropy kernels queued on ``stream``; the call waits for the stream while the fixed-point
+    loop reads its "changed" word (asep_jpeg_entropy_dev)."""
+    import torch
+    from . import _lib
+    tdev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    lib, ws = image_ops._workspace(tdev.index or 0, lane)
+    with torch.cuda.device(tdev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(tdev)):
+        sp = C.c_void_p(torch.cuda.current_stream(tdev).cuda_stream)
+        d_scan = torch.empty(scan.scan.size, dtype=torch.uint8, device=tdev)
+        d_scan.copy_(torch.from_numpy(scan.scan), non_blocking=True)
+        d_coef = torch.empty(scan.info.coef_bytes // 2, dtype=torch.int16, device=tdev)
+        d_status = torch.empty(1, dtype=torch.int32, device=tdev)
+        _lib.check(lib.asep_jpeg_entropy_dev(ws, C.byref(scan.info), d_scan.data_ptr(), scan.scan_bytes, C.byref(scan.tables),
+                                             scan.segments.ctypes.data, scan.n_segments, int(subseq_bits), d_coef.data_ptr(),
+                                             d_status.data_ptr(), sp), "asep_jpeg_entropy_dev")
+        d_scan.record_stream(torch.cuda.current_stream(tdev))
+    return d_coef, d_status
+
+
+def jpeg_scan_to_device(scan, device=0, order="bgr", stream=None, lane=0, subseq_bits=0):
+    """JpegScan -> (uint8 page tensor on ``device`` as ``jpeg_page_to_device`` returns it, int32 status tensor [1] on the device).
+    The entropy kernels and then the pixel kernels are queued on ``stream``.  The page holds Pillow's bytes only where the status is 0:
+    the caller reads it before the page is used and decodes the file through ``load_image_bgr_or_jpeg`` otherwise."""
+    import torch
+    from . import _lib
+    tdev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    lib, ws = image_ops._workspace(tdev.index or 0, lane)
+    with torch.cuda.device(tdev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(tdev)):
+        sp = C.c_void_p(torch.cuda.current_stream(tdev).cuda_stream)
+        d_coef, d_status = jpeg_scan_entropy_to_device(scan, tdev, torch.cuda.current_stream(tdev), lane, subseq_bits)
+        entropy_launches = jpeg_device_launches()
+        shape = (scan.height, scan.width) if scan.ncomp == 1 or order == "gray" else (scan.height, scan.width, 3)
+        out = torch.empty(shape, dtype=torch.uint8, device=tdev)
+        _lib.check(lib.asep_jpeg_pixels_dev(ws, C.byref(scan.info), d_coef.data_ptr(), scan.qt.ctypes.data, _lib.JPEG_ORDERS[order],
+                                            out.data_ptr(), sp), "asep_jpeg_pixels_dev")
+        d_coef.record_stream(torch.cuda.current_stream(tdev))
+    global jpeg_huffman_pages, _scan_launches
+    jpeg_huffman_pages += 1
+    _scan_launches = entropy_launches + jpeg_device_launches()
+    return out, d_status
+
+
+jpeg_huffman_pages = 0               # pages jpeg_scan_to_device has queued in this process
+jpeg_huffman_fallbacks = 0           # ... of which a non-zero status sent the file back to the host decoders
+_scan_launches = []
+
+
+def jpeg_scan_launches():
+    """the kernels of this process's last ``jpeg_scan_to_device``, entropy and pixels"""
+    return list(_scan_launches)
+
+
+def jpeg_entropy_rounds():
+    """(rounds of the calling thread's last device entropy decode until a launch changed nothing, its subsequences)"""
+    from . import _lib
+    n = C.c_int()
+    return _lib.load_library().asep_jpeg_entropy_last_rounds(C.byref(n)), n.value
+
+
+def jpeg_entropy_set_max_rounds(max_rounds):
+    """for tests: cap the rounds of the calling thread's later device entropy decodes (0 = the library's cap alone)"""
+    from . import _lib
+    _lib.load_library().asep_jpeg_entropy_set_max_rounds(int(max_rounds))
+
+
+class DevicePage:
+    """a page that is already on the device ([H, W] or [H, W, 3] uint8): what ``resolve_jpeg_scans`` puts in a JpegScan's place"""
+
+    def __init__(self, d_img):
+        self.d_img = d_img
+
+
+def resolve_jpeg_scans(batch, device, stream=None, lane=0, order="bgr"):
+    """[(path, image)] of a group of decoded pages -> the same list with every JpegScan (or its packed buffer) replaced: by a
+    DevicePage where the device's entropy decode reports status 0, else by what ``load_image_bgr_or_jpeg(path)`` returns.  The
+    statuses of the group are read together, once, before any of its pages is used."""
+    import torch
+    found = [(i, as_jpeg_scan(image)) for i, (_, image) in enumerate(batch)]
+    found = [(i, s) for i, s in found if s is not None]
+    if not found:
+        return batch
+    queued = [jpeg_scan_to_device(s, device, order, stream, lane) for _, s in found]
+    status = torch.cat([st for _, st in queued]).cpu().numpy()
+    out = list(batch)
+    global jpeg_huffman_fallbacks
+    for (i, _), (d_img, _), st in zip(found, queued, status):
+        if st == 0:
+            out[i] = (batch[i][0], DevicePage(d_img))
+        else:
+            jpeg_huffman_fallbacks += 1
+            out[i] = (batch[i][0], load_image_bgr_or_jpeg(batch[i][0]))
+    return out
+
+
+def load_image_bgr_or_jpeg_scan(path_to_image):
+    """DecodePool loader of ``--device_huffman True``: the ``packed`` buffer of a JpegScan where the device path takes the file, else
+    what ``load_image_bgr`` returns"""
+    scan = load_jpeg_scan(path_to_image)
+    return scan.packed if scan is not None else load_image_bgr(path_to_image)
 
 
 def load_image_bgr_or_jpeg(path_to_image):

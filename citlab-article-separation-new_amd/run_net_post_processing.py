@@ -18,12 +18,13 @@ MAX_SUBLIST_SIZE = 50
 
 
 def run_separator(image_list, path_to_pb, fixed_height, scaling_factor, threshold, gpu_devices='0', host_workers=0,
-                  device_jpeg=False):
+                  device_jpeg=False, device_huffman=False):
     from .separator_net_post_processor import SeparatorNetPostProcessor
     import time
     proc = SeparatorNetPostProcessor(image_list, path_to_pb, fixed_height, scaling_factor, threshold,
                                      gpu_devices=gpu_devices, host_workers=host_workers)
     proc.device_jpeg = device_jpeg
+    proc.device_huffman = device_huffman
     t0 = time.perf_counter()
     proc.run()
     _owner_stats(gpu_devices, len(image_list), time.perf_counter() - t0, host_workers, proc)
@@ -43,7 +44,8 @@ def _owner_stats(gpu, n_pages, seconds, host_workers, proc):
 
 
 def run_heading(image_list, path_to_pb, fixed_height=900, scaling_factor=1, is_heading_threshold=0.4,
-                weight_dict=None, thresh_dict=None, text_line_percentage=0.8, gpu_devices='0', host_workers=0, device_jpeg=False):
+                weight_dict=None, thresh_dict=None, text_line_percentage=0.8, gpu_devices='0', host_workers=0, device_jpeg=False,
+                device_huffman=False):
     from .heading_net_post_processor import HeadingNetPostProcessor
     if thresh_dict is None:
         thresh_dict = {'net_thresh': 1.0, 'stroke_width_thresh': 1.0, 'text_height_thresh': 0.9, 'sw_th_thresh': 0.9}
@@ -53,7 +55,9 @@ def run_heading(image_list, path_to_pb, fixed_height=900, scaling_factor=1, is_h
                                    thresh_dict, text_line_percentage)
     proc.host_workers = host_workers
     proc.device_jpeg = device_jpeg
+    proc.device_huffman = device_huffman
     proc.run(gpu_device=gpu_devices)
+    proc.log_huffman_pages()
 
 
 def build_parser():
@@ -75,6 +79,10 @@ def build_parser():
                         help="True: baseline JPEG scans are only Huffman-decoded on the host; dequantisation, inverse DCT, chroma "
                              "upsampling and colour conversion run on the GPU and give the same bytes.  Files that path does not take "
                              "(PNG, TIFF, progressive / CMYK / rotated / damaged JPEG ...) are decoded as without the flag.")
+    parser.add_argument("--device_huffman", type=str2bool, required=False, default=False,
+                        help="True (needs --device_jpeg True): the Huffman decode of such a scan runs on the GPU as well, by "
+                             "self-synchronising subsequences; the host only removes stuffing and markers.  A page whose device "
+                             "status is not 0 is decoded again as with --device_jpeg alone; the log counts those pages.")
     return parser
 
 
@@ -88,20 +96,25 @@ def build_sub_lists(image_path_list, num_processes):
     return [image_path_list[i: i + size_sub_lists] for i in range(0, len(image_path_list), size_sub_lists)]
 
 
-def _worker(mode, sub_lists, path_to_pb, fixed_height, scaling_factor, threshold, gpu, host_workers=0, device_jpeg=False):
+def _worker(mode, sub_lists, path_to_pb, fixed_height, scaling_factor, threshold, gpu, host_workers=0, device_jpeg=False,
+            device_huffman=False):
     # one model per GPU owner: its sub-lists are processed as one stream so that the decode workers never run dry at a
     # sub-list boundary (the 50-page cap of :70 only bounded the memory of the reference's per-run image lists)
     images = [p for sub in sub_lists for p in sub]
     if mode == 'separator':
         run_separator(images, path_to_pb, fixed_height, scaling_factor, threshold, gpu_devices=str(gpu),
-                      host_workers=host_workers, device_jpeg=device_jpeg)
+                      host_workers=host_workers, device_jpeg=device_jpeg, device_huffman=device_huffman)
     else:
         run_heading(images, path_to_pb, fixed_height, scaling_factor, 0.4, None, None, 0.8, gpu_devices=str(gpu),
-                    host_workers=host_workers, device_jpeg=device_jpeg)
+                    host_workers=host_workers, device_jpeg=device_jpeg, device_huffman=device_huffman)
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.device_huffman and not args.device_jpeg:
+        parser.error("--device_huffman True needs --device_jpeg True: the entropy decode feeds the device's pixel kernels, and the pages "
+                     "that fall back are decoded by that path's host decoder")
     mode = args.mode
     image_path_list = load_list_file(args.path_to_image_list)
     if args.fixed_height is None:
@@ -130,11 +143,12 @@ def main(argv=None):
     per_worker = [sub_lists[i::n_workers] for i in range(n_workers)]
     if n_workers == 1:
         _worker(mode, per_worker[0], args.path_to_pb, fixed_height, args.scaling_factor, args.threshold, devices[0], host_workers,
-                args.device_jpeg)
+                args.device_jpeg, args.device_huffman)
         return 0
     ctx = mp.get_context("spawn")
     procs = [ctx.Process(target=_worker, args=(mode, per_worker[i], args.path_to_pb, fixed_height,
-                                               args.scaling_factor, args.threshold, devices[i], host_workers, args.device_jpeg))
+                                               args.scaling_factor, args.threshold, devices[i], host_workers, args.device_jpeg,
+                                               args.device_huffman))
              for i in range(n_workers)]
     for p in procs:
         p.start()

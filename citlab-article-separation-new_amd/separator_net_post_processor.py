@@ -31,6 +31,11 @@ class RegionNetPostProcessor:
         # True: baseline JPEG scans are only entropy-decoded on the host (image_io.load_jpeg_coefficients); their pixels are computed on the
         # device in front of resize + gray.  Every other file, and every JPEG that path refuses, is decoded as without the flag.
         self.device_jpeg = False
+        # True (needs device_jpeg): the host only unstuffs such a scan (image_io.load_jpeg_scan); the Huffman decode runs on the device too.
+        # A page whose device status is not 0 is decoded again as with device_jpeg alone, and counted in huffman_fallbacks.
+        self.device_huffman = False
+        self.huffman_pages = 0
+        self.huffman_fallbacks = 0
         self.device_seconds = 0.0      # wall time this process spent inside the device stages (upload .. results back)
         self.wait_seconds = 0.0        # ... waiting for the next decoded image
         self.first_page_seconds = None # run() start -> first decoded image in hand (worker start-up, slot page-locking)
@@ -112,8 +117,11 @@ class RegionNetPostProcessor:
         with self._on_lane(lane) as (lib, ws, tdev, stream, sp):
             for image in images:
                 jpeg = image_io.as_jpeg_page(image) if reuse is None else None
+                on_device = image.d_img if reuse is None and isinstance(image, image_io.DevicePage) else None
                 if jpeg is not None:                                 # --device_jpeg: coefficients in, the page is computed on the device
                     H, W, Cn = jpeg.height, jpeg.width, jpeg.ncomp
+                elif on_device is not None:                          # --device_huffman: _resolve_scans has computed the page already
+                    H, W, Cn = on_device.shape[0], on_device.shape[1], 1 if on_device.ndim == 2 else 3
                 elif reuse is not None:
                     H, W, Cn = reuse[len(tickets)]["d_img"].shape
                 else:
@@ -131,6 +139,8 @@ class RegionNetPostProcessor:
                     if jpeg is not None:
                         d_img = image_io.jpeg_page_to_device(jpeg, tdev, "bgr", stream, lane=0 if lane == 0 else 10 + lane)
                         d_img = d_img.reshape(H, W, Cn)
+                    elif on_device is not None:
+                        d_img = on_device.reshape(H, W, Cn)
                     else:
                         d_img = torch.empty((H, W, Cn), dtype=torch.uint8, device=tdev)
                         d_img.copy_(torch.from_numpy(image), non_blocking=True)
@@ -161,6 +171,24 @@ class RegionNetPostProcessor:
                     float(self.threshold) if mask else 0.0, sp), "asep_aru_forward_batch_dev2")
         return tickets
 
+    def _resolve_scans(self, batch, lane=0):
+        """--device_huffman: [(path, image)] with every prepared JPEG scan replaced by its page on the device (entropy and pixel kernels on
+        ``lane``'s stream), or, where the device reports a non-zero status, by what the host decoders of --device_jpeg give for the file.
+        The statuses of the group are read once, here, before the pages are used."""
+        if not self.device_huffman:
+            return batch
+        before = image_io.jpeg_huffman_pages, image_io.jpeg_huffman_fallbacks
+        with self._on_lane(lane) as (lib, ws, tdev, stream, sp):
+            batch = image_io.resolve_jpeg_scans(batch, tdev, stream, lane=0 if lane == 0 else 10 + lane)
+        self.huffman_pages += image_io.jpeg_huffman_pages - before[0]
+        self.huffman_fallbacks += image_io.jpeg_huffman_fallbacks - before[1]
+        return batch
+
+    def log_huffman_pages(self):
+        if self.device_huffman:
+            print(f"device_huffman: {self.huffman_pages} pages entropy-decoded on the device, {self.huffman_fallbacks} of them fell back to the "
+                  f"host decoders")
+
     def _run_groups(self, decode, n_paths, group, lanes, enqueue, finish):
         """Drive the device stages over ``decode``, an iterator of ``n_paths`` decoded (path, image) pages: ``group`` consecutive
         pages go through ``enqueue(images, lane) -> tickets`` together, consecutive groups on alternating lanes (streams, model
@@ -177,6 +205,7 @@ class RegionNetPostProcessor:
             self.wait_seconds += t_dev - t_prev
             batch.append((path, image))
             if len(batch) >= group or n_seen == n_paths:   # (the last pages are uploaded HERE: a DecodePool releases its slots when it ends)
+                batch = self._resolve_scans(batch, n_groups % lanes)
                 tickets = enqueue([img for _, img in batch], n_groups % lanes)
                 n_groups += 1
                 self.device_seconds += time.perf_counter() - t_dev
@@ -192,13 +221,14 @@ class RegionNetPostProcessor:
             finish(*item)
 
 
-def jpeg_decode_options(paths, device_jpeg):
+def jpeg_decode_options(paths, device_jpeg, device_huffman=False):
     """DecodePool arguments of ``--device_jpeg``: the loader that hands out coefficients where it can, and slots that hold them (int16
     per sample: up to twice the widest decoded page, plus the padding to whole MCUs and the tables)"""
     if not device_jpeg:
         return {}
     from .host_pipeline import needed_slot_bytes, SLOT_BYTES_MAX
-    return {"loader": "load_image_bgr_or_jpeg", "slot_bytes": min(SLOT_BYTES_MAX, 2 * needed_slot_bytes(paths) + (2 << 20))}
+    # (a prepared scan is smaller than its file; the slots stay sized for the pages that fall back to coefficients or pixels)
+    return {"loader": "load_image_bgr_or_jpeg_scan" if device_huffman else "load_image_bgr_or_jpeg", "slot_bytes": min(SLOT_BYTES_MAX, 2 * needed_slot_bytes(paths) + (2 << 20))}
 
 
 def write_separator_page(page_path, image_path, fixed_height, scaling_factor, polygons_dict):
@@ -355,11 +385,12 @@ class SeparatorNetPostProcessor(RegionNetPostProcessor):
         reg, unreg = pin_callbacks(self.device) if pipelined else (None, None)
         group = self.PAGE_GROUP if pipelined else 1
         decode = DecodePool(self.image_paths, self.host_workers if pipelined else 0, register=reg, unregister=unreg, hold=group + 1,
-                            **jpeg_decode_options(self.image_paths, self.device_jpeg))
+                            **jpeg_decode_options(self.image_paths, self.device_jpeg, self.device_huffman))
         with WritePool(self.host_workers if pipelined else 0) as writers:
             self._run_groups(decode, len(self.image_paths), group, self.PAGE_LANES if pipelined else 1,
                              lambda images, lane: self.enqueue_group(images, edges_only=not self.keep_outputs, lane=lane),
                              lambda path, t: self._finish_page(path, t, writers, pipelined, page_objects))
+        self.log_huffman_pages()
         return page_objects
 
 

@@ -828,6 +828,46 @@ int asep_jpeg_pixels(asep_post* p, const asep_jpeg_info* info, const int16_t* co
  * Copies at most max_bytes - 1 characters and returns the text's length. */
 long asep_jpeg_last_launches(char* buf, size_t max_bytes);
 
+/* ---- JPEG entropy decode (added under ABI 12 as well; csrc/jpeg_huffman_kernels.h, entry points in csrc/jpeg_engine.hip) ------------
+ * The Huffman decode of a scan that asep_jpeg_scan_prepare (asep_host_jpeg.h) unstuffed, by self-synchronising subsequences: every
+ * segment is cut into subsequences of subseq_bits bits (a multiple of 32, >= 64; 0 = ASEP_JPEG_SUBSEQ_BITS_DEFAULT), one thread each.
+ *   speculate   decode from a guessed state (block 0 of the MCU, first AC position); an invalid code skips one bit, nothing is reported
+ *   synchronise entry[s + 1] = exit[s], decode again where the entry changed, until a launch changes nothing.  A launch is
+ *               ASEP_JPEG_SYNC_INNER rounds (doubled per launch up to _MAX) with workgroup barriers between them; no workgroup waits for another.  The host reads one
+ *               "changed" word back after every launch (so this call blocks on `stream` once or a few times) and stops at the cap.
+ *               The cap follows from the subsequences: a launch sees all that earlier launches stored, and inside a launch
+ *               correctness moves one subsequence forward per round within a workgroup, so with n the subsequences of the longest
+ *               segment n - 1 rounds suffice where one workgroup holds the scan, and otherwise ceil(n / _MAX) + 1 launches of _MAX
+ *               rounds, one per workgroup the segment touches, behind the five shorter ones; one more launch of one round has to
+ *               confirm.  Self-synchronisation ends the loop long before wherever blocks end in end-of-block codes.
+ *               asep_jpeg_entropy_set_max_rounds (for tests) lowers the cap.
+ *   place       exclusive sum of the completed blocks per segment -> every subsequence's first block
+ *   write       d_coef zeroed, then decoded once more from the now correct entries: de-zigzagged, at the block's place in its
+ *               component's plane, the DC as its difference; real errors go to the status
+ *   DC, energy  inclusive sum of the DC differences per component and segment with the host's range rule, then the energy bound
+ * d_coef (info->coef_bytes) gets exactly what asep_jpeg_entropy_decode writes; *d_status (device) is 0 then.  Otherwise it is an OR of
+ * ASEP_JPEG_STATUS_*, and d_coef holds no promise except that nothing outside it was written.  d_scan: scan_bytes bytes in an allocation
+ * of scan_bytes rounded up to 4; tables and segments are HOST memory and are copied before the call returns.  Scratch: p's arena.
+ * asep_jpeg_entropy is the blocking form with host pointers throughout; *status is the host's copy. */
+#define ASEP_JPEG_SUBSEQ_BITS_DEFAULT 128
+#define ASEP_JPEG_SYNC_INNER 8
+#define ASEP_JPEG_SYNC_INNER_MAX 256
+#define ASEP_JPEG_STATUS_DAMAGED 1       /* invalid code, index past 63, refused category, segment length or block count off, DC out of range */
+#define ASEP_JPEG_STATUS_REFUSED 2       /* a block above the energy bound (ASEP_JPEG_REFUSED on the host) */
+#define ASEP_JPEG_STATUS_NOT_CONVERGED 4 /* the cap of rounds was reached */
+int asep_jpeg_entropy_dev(asep_post* p, const asep_jpeg_info* info, const uint8_t* d_scan, size_t scan_bytes,
+                          const asep_jpeg_scan_tables* tables, const asep_jpeg_segment* segments, int n_segments, int subseq_bits,
+                          int16_t* d_coef, int32_t* d_status, void* stream);
+int asep_jpeg_entropy(asep_post* p, const asep_jpeg_info* info, const uint8_t* scan, size_t scan_bytes,
+                      const asep_jpeg_scan_tables* tables, const asep_jpeg_segment* segments, int n_segments, int subseq_bits,
+                      int16_t* coef, int32_t* status);
+/* Rounds of the calling thread's last entropy call until a launch changed nothing (a sum of whole launches), and its
+ * subsequence count; for measurements. */
+int asep_jpeg_entropy_last_rounds(int* n_subsequences);
+/* For tests: the calling thread's later entropy calls stop after at most max_rounds rounds (status "not converged" where that is too
+ * few); 0 = the cap above alone. */
+void asep_jpeg_entropy_set_max_rounds(int max_rounds);
+
 #ifdef __cplusplus
 }
 #endif

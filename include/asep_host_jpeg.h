@@ -43,4 +43,6 @@ int asep_jpeg_entropy_decode(const uint8_t* bytes, size_t n, const asep_jpeg_inf
 #ifdef __cplusplus
 }
 #endif
+
+#include "asep_host_jpeg_scan.h" /* the scan prepared for the device's entropy decode */
 #endif
